@@ -6,7 +6,12 @@ For N > 1 it is launched under torch.distributed.run, one rank per GPU (RCCL).
 
   * N = 1 headline workload = BASELINE.json configs[1]: 512^3 uint32 single label, anisotropy
     (6,6,30), black_border=True, labels and output resident in HBM (no PCIe in the timed region).
-    The same line carries a `secondary` list: configs[2] (cfg3: 512^3, 2000 labels, black_border=False), its
+    A plain run sets up, warms up, times EXACTLY K steps and prints the line (`value`, `ms_per_step` = the mean of the K
+    timed steps, `timing`); nothing else.  `--dump-outputs DIR` writes the last timed step's output to DIR/edtsq.npy
+    (a fixed seeded sample where it passes 32 MiB) before the line is printed.  Everything below -- per-kernel times and
+    the roofline, the checks of the timed output, the numpy round trip, the secondaries, the CPU baseline -- runs with
+    `--full` only.
+    With `--full` the same line carries a `secondary` list: configs[2] (cfg3: 512^3, 2000 labels, black_border=False), its
     membrane / anisotropic twin (cfg3m), four large-cell segmentations (cfg3L / cfg3La / cfg3M / cfg3Ma: full-resolution
     Voronoi cells ~130 / ~65 voxels across), the 1024^3 segmentation of configs[3] on ONE GPU (cfg4), configs[4]
     (cfg5: voxel graph) and `snemi_like` (the reference README's 334-label extraction workload) -- each with
@@ -15,13 +20,15 @@ For N > 1 it is launched under torch.distributed.run, one rank per GPU (RCCL).
   * N > 1 workload = ONE global multi-label volume with 512^3 voxels PER GPU (N=8 -> the 1024^3
     segmentation of BASELINE configs[3]), Z-sharded; the X and Y passes are slab-local, ONE all-to-all
     (RCCL send/recv group over xGMI) re-partitions Z-slabs into Y-slabs before the Z pass.  Weak scaling.
+    This leg runs its self-test and its check of the gathered result whatever `--full` says; `--dump-outputs DIR`
+    writes rank 0's share of the last step's output (DIR/edtsq_rank0.npy).
   * a "step" = one complete edtsq of the (local part of the) volume.
-  * roofline: dominant kernel's ALGORITHMIC bytes (pass X reads labels + writes
+  * roofline (--full at N = 1): dominant kernel's ALGORITHMIC bytes (pass X reads labels + writes
     fp32, passes Y/Z read labels + read/write fp32 -> 8 / 12 / 12 B per uint32 voxel) divided
     by its duration measured with hipEvents inside the library on the launch stream; beside that
     model, `real_*`: the bytes the kernels really move (PMC of a committed profile, `traffic_source`)
     over this run's times, against the 8 TB/s spec and the ~6.3 TB/s a streaming kernel reaches.
-  * cpu_baseline: the real reference (oracle/_ref, compiled from the reference sources) on
+  * cpu_baseline (--full): the real reference (oracle/_ref, compiled from the reference sources) on
     this host's cores: the headline volume and the cfg3 volume, 1 thread and all threads,
     1 warm-up + best of 3, CPU model stated.
 """
@@ -117,6 +124,34 @@ def real_traffic_fields(ms_per_step, kernel_ms, dom, config):
 # the arithmetic the column passes compute in: exact 16-bit integer multiples of the voxel sizes' common quantum
 # (csrc/edt_colq16.hip) wherever a tile's values fit, the reference's fp64 envelope arithmetic elsewhere; fp32 storage
 DTYPE = "u16 integer quanta (exact) with f64 envelope fallback / f32 storage / u32 labels"
+
+
+DUMP_MAX_ELEMS = 8 << 20   # --dump-outputs: at most 32 MiB of float32 per array; larger outputs are sampled
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy in float32 (float64 stays float64).  An array of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample: DUMP_MAX_ELEMS flat indices drawn with seed DUMP_SEED and sorted,
+    the same for every run of the same shape, so that two builds can be compared output for output.  Returns what was
+    written, for the result line."""
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.dtype != torch.float64:
+            flat = flat.to(torch.float32)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.sort(torch.randint(n, (DUMP_MAX_ELEMS,), generator=g)).values
+            flat = flat[idx.to(flat.device)]
+            how = f"sample of {DUMP_MAX_ELEMS} of {n} elements (flat indices drawn with seed {DUMP_SEED}, sorted)"
+        else:
+            how = f"all {n} elements"
+        np.save(os.path.join(directory, name + ".npy"), flat.cpu().numpy())
+        written[name] = {"shape": list(t.shape), "written": how}
+    return written
 
 
 def cpu_model():
@@ -252,11 +287,14 @@ class DeviceRun:
             self.turn ^= 1
             if self.turn:
                 self.plan.run(self.alt[0], self.an, black_border=self.bb, sqrt=False, out=self.alt[1], force_generic=generic)
+                self.last_out = self.alt[1]
                 return
         self.plan.run(self.labels, self.an, black_border=self.bb, sqrt=False, out=self.out, force_generic=generic)
+        self.last_out = self.out
 
-    def measure(self, steps, warmup, generic=False):
-        from edt import device
+    def measure(self, steps, warmup, generic=False, per_kernel=True):
+        """`steps` timed steps after the warm-up; per_kernel=False: the timing alone (no profiled steps after it, no
+        per-kernel fields in the summary, and `self.last_out` still holds the output of the last TIMED step)."""
         # Warm-up by TIME, then by count: a handful of sub-millisecond steps does not bring the part to its steady clocks
         # (round 4: the driver's 20-step figure sat 4 % above the 1000-step one).  At least WARM_MS of untimed steps, then
         # the `warmup` steps of the contract.
@@ -282,11 +320,18 @@ class DeviceRun:
                 self.step(generic)
             torch.cuda.synchronize()
             batch_ms.append((time.perf_counter() - t0) / k * 1e3)
-        ms = float(np.dot(batch_ms, sizes) / steps)
+        ms = self.ms = float(np.dot(batch_ms, sizes) / steps)
         self.timing = {"statistic": "mean over all timed steps", "batches": sizes, "batch_ms": [round(b, 4) for b in batch_ms],
                        "mean_ms": round(ms, 4), "median_of_batch_means_ms": round(float(np.median(batch_ms)), 4),
                        "untimed_steps_before": extra + warmup, "warm_ms": WARM_MS}
-        # per-kernel durations with hipEvents on the launch stream (separate profiled steps)
+        if not per_kernel:
+            return {"ms_per_step": round(ms, 4), "mvox_per_s": round(self.vox / (ms * 1e-3) / 1e6, 1)}, None, None
+        return self.kernel_times(ms, steps, generic)
+
+    def kernel_times(self, ms, steps, generic=False):
+        """Per-kernel durations with hipEvents on the launch stream, in profiled steps of their own after the timed ones;
+        returns measure()'s summary (ms_per_step and the whole-job model fields) with them."""
+        from edt import device
         device.set_profiling(True)
         acc = {}
         for _ in range(max(3, min(steps, 10))):
@@ -721,6 +766,9 @@ def sharded_main(args, rank, world, dev):
         }
         if cpu is not None:
             line["cpu_baseline"] = cpu
+    if rank == 0 and args.dump_outputs:
+        line["outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"edtsq_rank0": out}),
+                           "what": "edtsq_rank0: rank 0's (z, y-slab, x) float32 share of the last step's output, flattened"}
     dist.barrier()
     dist.destroy_process_group()
     if rank == 0:
@@ -898,7 +946,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="headline configuration only")
     ap.add_argument("--generic", action="store_true", help="force the size-agnostic fallback kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="--gpus 1: beyond the headline figure, also the per-kernel times and roofline, the check of the timed output, "
+                         "the numpy round trip, the secondary configurations and the CPU baseline (off: set up, warm up, time "
+                         "the steps, print the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; outputs "
+                         "larger than 32 MiB as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -927,181 +984,188 @@ def main():
         return sharded_main(args, rank, world, dev)
 
     head = DeviceRun(args.config, n, dev)
-    summary, kernels, bpv = head.measure(args.steps, args.warmup, args.generic)
-    dom = max((k for k in kernels if k in bpv), key=lambda k: kernels[k])
-    achieved = bpv[dom] * head.vox / (kernels[dom] * 1e-3) / 1e9
-    # `achieved` / `frac`: the WHOLE JOB against SURVEY 8(d)'s 32 B/voxel -- the only fraction of this line that is bounded by 1
-    # whatever the kernels do (VERDICT r5 "What's weak" 4: the dominant pass against its own 12 B/voxel model can read above 1,
-    # because that pass moves fewer bytes than the model charges it -- those per-pass model figures live under `passes` only).
-    roofline = {
-        "bound": "hbm", "kernel": "whole step (x_pass + y_pass + z_bits + z_pass)", "dominant_kernel": dom,
-        "achieved": summary["whole_job_algorithmic_GBs"], "peak": HBM_PEAK_GBS,
-        "unit": "GB/s", "frac": summary["whole_job_frac"], "traffic": whole_step_traffic(args.config),
-        "frac_note": "algorithmic bytes (SURVEY 8(d): 32 B/voxel, the reference's data movement) over the step's time, against the 8 TB/s "
-                     "spec; the kernels really move ~18.4 B/voxel (traffic), so on a fast box this model fraction can pass 1 without "
-                     "any kernel exceeding the memory system: real_* price the bytes that moved",
-        "dominant_kernel_traffic": measured_traffic(dom, args.config), "dominant_kernel_model_GBs": round(achieved, 1),
-        "kernel_ms": summary["kernel_ms"],
-        # every pass against its own model (the `kernel` above is simply the longest one: X and Z are within 2 % of each other
-        # on the headline, so which of them it is can change from run to run)
-        "passes": {k: {"algorithmic_bytes_per_voxel": bpv[k], "ms": round(kernels[k], 4),
-                       "model_GBs": round(bpv[k] * head.vox / (kernels[k] * 1e-3) / 1e9, 1),
-                       "frac": round(bpv[k] * head.vox / (kernels[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)} for k in kernels if k in bpv},
-        "whole_job_algorithmic_GBs": summary["whole_job_algorithmic_GBs"],
-        "whole_job_frac": summary["whole_job_frac"],  # 32 B/voxel model over ms_per_step
-    }
-    # `frac` / `whole_job_frac` are the SURVEY 8(d) model (algorithmic bytes: the reference's data movement).  What the
-    # kernels really move is less (labels are read once, 16-bit indices between X and Y): the real_* fields price that.
-    roofline.update(real_traffic_fields(summary["ms_per_step"], kernels, dom, args.config))
-
-    # sanity: the timed output is the right answer (closed form for the all-ones box)
-    if args.config in ("cfg1", "cfg2"):
-        from synth import box_edtsq_closed_form
-        ok = bool(np.array_equal(head.out.cpu().numpy().T, box_edtsq_closed_form(head.lab_np.shape, head.an)))
-    else:
-        ok = None
-    head_lab, head_an, head_bb = head.lab_np, head.an, head.bb
-    head_timing = getattr(head, "timing", None)
-    # (kept on the host for the comparison with the compiled reference's output on the same volume, below)
-    head_out = head.out.cpu().numpy().reshape(-1) if (not args.no_cpu_baseline and head_lab is not None) else None
-
-    # numpy in -> numpy out through the host-buffer entry point (C ABI, PCIe both ways); reported beside the
-    # device-resident figure, never as `value`
-    end_to_end = None
-    if head_lab is not None and not args.generic:
-        try:
-            end_to_end = host_round_trip(head_lab, head_an, head_bb)
-        except Exception as e:  # pragma: no cover
-            end_to_end = {"error": repr(e)}
-
-    lib = kind = None
-    if not args.no_cpu_baseline:
-        try:
-            lib, kind = reference_lib()
-        except Exception as e:  # pragma: no cover
-            lib, kind = None, f"unavailable: {e}"
-    cores = os.cpu_count() or 1
-    threads = (1, cores) if kind == "reference" else (1,)
-
-    secondary = []
-    cpu_secondary = {}
-    if not args.no_secondary and args.config == "cfg2" and not args.generic:
-        del head
-        torch.cuda.empty_cache()
-        what = {"cfg1": "all-ones labels (BASELINE configs[0]: the reference's own CPU-runnable case, timed beside it with parallel=1)",
-                "cfg3": "2000 labels (up-sampled x4: cells ~34 voxels)", "cfg3m": "2000 labels + 5 % zero membranes",
-                "cfg3f": "the 2000 labels of cfg3 at voxel sizes whose multiples are not exact in fp32",
-                "cfg3L": "~60 full-resolution Voronoi cells (~130 voxels across)", "cfg3La": "~60 full-resolution cells",
-                "cfg3M": "~500 full-resolution Voronoi cells (~65 voxels across)", "cfg3Ma": "~500 full-resolution cells",
-                "cfg4": "the 1024^3 segmentation of configs[3] (16 000 seeds) on ONE GPU"}
-        # the OBJECT-SIZE sweep (tests/synth.py: SWEEP -- its cells ~65 / ~130 are cfg3M / cfg3L above)
-        sweep = {"sw26": "~7600 full-resolution Voronoi cells (~26 voxels across)", "sw256": "8 full-resolution Voronoi cells (~256 voxels across)",
-                 "sphere250": "ONE ball of radius 250 in background", "onesF": "all-ones box WITHOUT a black border (no boundary anywhere: +inf)",
-                 "onebg": "all-ones box with ONE background voxel (every z-column sees one finite row)",
-                 "diag": "two half spaces cut by the plane x + y + z = const", "diagF": "the same two half spaces without a black border",
-                 "sphere_slab": "the ball of radius 250 on the 8-GPU slab shape"}
-        what.update(sweep)
-        # the headline's volume WITHOUT the short cut for tiles that have no structure along the scan axis (debug bit 0x80: every
-        # tile through scans, break bits and blocks): a single-label box is made of nothing but such tiles, so the headline is
-        # also stated as what the same kernels take when they do their whole work on it
-        what["cfg2_scans"] = "the headline's volume with the flat-tile short cut switched off (debug bit 0x80)"
-        todo = [("cfg2_scans", n), ("cfg1", n), ("cfg3", n), ("cfg3f", n), ("cfg3m", n), ("cfg3L", n), ("cfg3La", n), ("cfg3M", n), ("cfg3Ma", n), ("cfg4", 2 * n)]
-        todo += [(k, n) for k in sweep]
-        only = [c for c in args.secondary.split(",") if c]
-        verify = os.environ.get("EDT_BENCH_VERIFY", "1") != "0"
-        for name, size in todo:
-            if only and name not in only:
-                continue
-            try:
-                if name == "cfg2_scans":
-                    from edt import _lib as _edt_lib
-                    _edt_lib.load().edt_hip_set_debug_mode(0x80)
-                run = DeviceRun("cfg2" if name == "cfg2_scans" else name, size, dev)
-                s, kern, _ = run.measure(max(5, min(args.steps, 200) // 2) if size > n else min(args.steps, 100 if name in sweep else 400),
-                                         args.warmup)
-                entry = {"config": name,
-                         "workload": f"{'x'.join(str(v) for v in run.shape)} uint32 {'single-label' if name in ('cfg1', 'cfg2_scans') else 'multi-label'}: {what[name]}, "
-                                     f"anisotropy {tuple(run.an)}, black_border={run.bb}, device-resident in/out, 1 GPU", **s}
-                entry.update(real_traffic_fields(s["ms_per_step"], kern, None, run.name))
-                entry["output_verified"] = None
-                if lib is not None and verify:
-                    # the timed output, bit for bit against the CPU reference on the same volume (all threads), timed as well
-                    # (configs[0] asks for the reference with parallel=1: both thread counts there)
-                    res, want = time_reference(lib, kind, run.host_labels(), tuple(run.an), run.bb,
-                                               threads if name == "cfg1" else threads[-1:])
-                    got = run.out.cpu().numpy().reshape(-1)
-                    entry["output_verified"] = bool(np.array_equal(got, want))
-                    cpu_secondary[name] = {f"{p} thread(s)": round(v, 1) for p, v in res.items()}
-                    del got, want
-                secondary.append(entry)
-                del run
-                torch.cuda.empty_cache()
-            except Exception as e:  # pragma: no cover  (a secondary must never take the headline down)
-                secondary.append({"config": name, "error": repr(e)})
-            finally:
-                if name == "cfg2_scans":
-                    _edt_lib.load().edt_hip_set_debug_mode(int(os.environ.get("EDT_HIP_DEBUG_MODE", "0"), 0))
-        if not only or "cfg5" in only:
-            try:
-                secondary.append(voxel_graph_secondary(n, dev, max(5, min(args.steps, 200) // 4), args.warmup,
-                                                       lib if kind == "reference" else None))
-            except Exception as e:  # pragma: no cover
-                secondary.append({"config": "cfg5", "error": repr(e)})
-        if not only or "cfg5_sdf" in only:
-            try:
-                secondary.append(sdf_secondary(n, dev, max(5, min(args.steps, 200) // 4), args.warmup,
-                                               lib if kind == "reference" else None))
-            except Exception as e:  # pragma: no cover
-                secondary.append({"config": "cfg5_sdf", "error": repr(e)})
-        if not only or "snemi_like" in only:
-            try:
-                secondary.append(snemi_like_secondary(dev, lib, kind))
-            except Exception as e:  # pragma: no cover
-                secondary.append({"config": "snemi_like", "error": repr(e)})
-
+    summary, _, _ = head.measure(args.steps, args.warmup, args.generic, per_kernel=False)
+    outputs = dump_outputs(args.dump_outputs, {"edtsq": head.last_out}) if args.dump_outputs else None
     result = {
         "metric": "Mvox/s edt3dsq 512^3 uint32", "value": summary["mvox_per_s"], "unit": "Mvox/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": summary["ms_per_step"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": DTYPE, "data": "synthetic",
-        "config": {"workload": f"{args.config}: {n}^3 uint32 labels, anisotropy {tuple(head_an)}, "
-                               f"black_border={head_bb}, device-resident in/out",
-                   "path": "generic" if args.generic else "default", "output_verified": ok},
-        "roofline": roofline,
+        "config": {"workload": f"{args.config}: {n}^3 uint32 labels, anisotropy {tuple(head.an)}, "
+                               f"black_border={head.bb}, device-resident in/out",
+                   "path": "generic" if args.generic else "default", "output_verified": None},
+        "timing": head.timing,
     }
-    if head_timing is not None:
-        result["timing"] = head_timing
-    if end_to_end is not None:
-        result["end_to_end"] = end_to_end
-    if secondary:
-        result["secondary"] = secondary
-    if not args.no_cpu_baseline:
-        if lib is None:
-            result["cpu_baseline"] = {"value": None, "unit": "Mvox/s", "cores": 0, "kind": str(kind), "sample": ""}
+    if outputs is not None:
+        result["outputs"] = {"dir": args.dump_outputs, "arrays": outputs,
+                             "what": "edtsq: the (sz, sy, sx) float32 output of the last timed step, flattened"}
+    # --full: everything beyond the headline figure -- the per-kernel steps and the roofline, the check of the timed output,
+    # the numpy round trip, the secondary configurations and the CPU baseline (each verified against the CPU reference)
+    if args.full:
+        summary, kernels, bpv = head.kernel_times(head.ms, args.steps, args.generic)
+        dom = max((k for k in kernels if k in bpv), key=lambda k: kernels[k])
+        achieved = bpv[dom] * head.vox / (kernels[dom] * 1e-3) / 1e9
+        # `achieved` / `frac`: the WHOLE JOB against SURVEY 8(d)'s 32 B/voxel -- the only fraction of this line that is bounded by 1
+        # whatever the kernels do (VERDICT r5 "What's weak" 4: the dominant pass against its own 12 B/voxel model can read above 1,
+        # because that pass moves fewer bytes than the model charges it -- those per-pass model figures live under `passes` only).
+        roofline = {
+            "bound": "hbm", "kernel": "whole step (x_pass + y_pass + z_bits + z_pass)", "dominant_kernel": dom,
+            "achieved": summary["whole_job_algorithmic_GBs"], "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": summary["whole_job_frac"], "traffic": whole_step_traffic(args.config),
+            "frac_note": "algorithmic bytes (SURVEY 8(d): 32 B/voxel, the reference's data movement) over the step's time, against the 8 TB/s "
+                         "spec; the kernels really move ~18.4 B/voxel (traffic), so on a fast box this model fraction can pass 1 without "
+                         "any kernel exceeding the memory system: real_* price the bytes that moved",
+            "dominant_kernel_traffic": measured_traffic(dom, args.config), "dominant_kernel_model_GBs": round(achieved, 1),
+            "kernel_ms": summary["kernel_ms"],
+            # every pass against its own model (the `kernel` above is simply the longest one: X and Z are within 2 % of each other
+            # on the headline, so which of them it is can change from run to run)
+            "passes": {k: {"algorithmic_bytes_per_voxel": bpv[k], "ms": round(kernels[k], 4),
+                           "model_GBs": round(bpv[k] * head.vox / (kernels[k] * 1e-3) / 1e9, 1),
+                           "frac": round(bpv[k] * head.vox / (kernels[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)} for k in kernels if k in bpv},
+            "whole_job_algorithmic_GBs": summary["whole_job_algorithmic_GBs"],
+            "whole_job_frac": summary["whole_job_frac"],  # 32 B/voxel model over ms_per_step
+        }
+        # `frac` / `whole_job_frac` are the SURVEY 8(d) model (algorithmic bytes: the reference's data movement).  What the
+        # kernels really move is less (labels are read once, 16-bit indices between X and Y): the real_* fields price that.
+        roofline.update(real_traffic_fields(summary["ms_per_step"], kernels, dom, args.config))
+
+        # sanity: the timed output is the right answer (closed form for the all-ones box)
+        if args.config in ("cfg1", "cfg2"):
+            from synth import box_edtsq_closed_form
+            ok = bool(np.array_equal(head.out.cpu().numpy().T, box_edtsq_closed_form(head.lab_np.shape, head.an)))
         else:
-            m = min(n, 512)
-            lab = head_lab if head_lab is not None and head_lab.shape[0] == m else np.ones((m, m, m), np.uint32, order="F")
-            res, want = time_reference(lib, kind, lab, tuple(head_an), head_bb, threads)
-            if head_out is not None and lab is head_lab and want is not None:
-                # the timed headline output, bit for bit against what the CPU reference just computed on the very same volume
-                same = bool(np.array_equal(head_out, np.asarray(want).reshape(-1)))
-                result["config"]["output_verified_against_reference"] = same
-                result["config"]["output_verified"] = bool(result["config"]["output_verified"] is not False and same)
-                result["config"]["verified_by"] = ("closed form of the box + " if ok is not None else "") + (
-                    "the compiled CPU reference on the whole volume" if kind == "reference" else "the CPU restatement (oracle port)")
-            del want
-            top = max(res, key=lambda k: res[k])
-            result["cpu_baseline"] = {
-                # cores: the physical cores the fastest figure ran on (all of them when every hardware thread was used);
-                # host_threads: the threads of that run
-                "value": round(res[top], 2), "unit": "Mvox/s",
-                "cores": (physical_cores() if int(top) >= physical_cores() else int(top)), "kind": kind,
-                "cpu": cpu_model(), "host_threads": int(top), "hardware_threads": cores,
-                "sample": f"whole {m}^3 uint32 headline volume ({args.config}), anisotropy {tuple(head_an)}, "
-                          "1 warm-up + best of 3; "
-                          + ", ".join(f"{p} thread(s): {v:.1f} Mvox/s" for p, v in res.items()),
-                "secondary": cpu_secondary,
-            }
+            ok = None
+        head_lab, head_an, head_bb = head.lab_np, head.an, head.bb
+        # (kept on the host for the comparison with the compiled reference's output on the same volume, below)
+        head_out = head.out.cpu().numpy().reshape(-1) if (not args.no_cpu_baseline and head_lab is not None) else None
+
+        # numpy in -> numpy out through the host-buffer entry point (C ABI, PCIe both ways); reported beside the
+        # device-resident figure, never as `value`
+        end_to_end = None
+        if head_lab is not None and not args.generic:
+            try:
+                end_to_end = host_round_trip(head_lab, head_an, head_bb)
+            except Exception as e:  # pragma: no cover
+                end_to_end = {"error": repr(e)}
+
+        lib = kind = None
+        if not args.no_cpu_baseline:
+            try:
+                lib, kind = reference_lib()
+            except Exception as e:  # pragma: no cover
+                lib, kind = None, f"unavailable: {e}"
+        cores = os.cpu_count() or 1
+        threads = (1, cores) if kind == "reference" else (1,)
+
+        secondary = []
+        cpu_secondary = {}
+        if not args.no_secondary and args.config == "cfg2" and not args.generic:
+            del head
+            torch.cuda.empty_cache()
+            what = {"cfg1": "all-ones labels (BASELINE configs[0]: the reference's own CPU-runnable case, timed beside it with parallel=1)",
+                    "cfg3": "2000 labels (up-sampled x4: cells ~34 voxels)", "cfg3m": "2000 labels + 5 % zero membranes",
+                    "cfg3f": "the 2000 labels of cfg3 at voxel sizes whose multiples are not exact in fp32",
+                    "cfg3L": "~60 full-resolution Voronoi cells (~130 voxels across)", "cfg3La": "~60 full-resolution cells",
+                    "cfg3M": "~500 full-resolution Voronoi cells (~65 voxels across)", "cfg3Ma": "~500 full-resolution cells",
+                    "cfg4": "the 1024^3 segmentation of configs[3] (16 000 seeds) on ONE GPU"}
+            # the OBJECT-SIZE sweep (tests/synth.py: SWEEP -- its cells ~65 / ~130 are cfg3M / cfg3L above)
+            sweep = {"sw26": "~7600 full-resolution Voronoi cells (~26 voxels across)", "sw256": "8 full-resolution Voronoi cells (~256 voxels across)",
+                     "sphere250": "ONE ball of radius 250 in background", "onesF": "all-ones box WITHOUT a black border (no boundary anywhere: +inf)",
+                     "onebg": "all-ones box with ONE background voxel (every z-column sees one finite row)",
+                     "diag": "two half spaces cut by the plane x + y + z = const", "diagF": "the same two half spaces without a black border",
+                     "sphere_slab": "the ball of radius 250 on the 8-GPU slab shape"}
+            what.update(sweep)
+            # the headline's volume WITHOUT the short cut for tiles that have no structure along the scan axis (debug bit 0x80: every
+            # tile through scans, break bits and blocks): a single-label box is made of nothing but such tiles, so the headline is
+            # also stated as what the same kernels take when they do their whole work on it
+            what["cfg2_scans"] = "the headline's volume with the flat-tile short cut switched off (debug bit 0x80)"
+            todo = [("cfg2_scans", n), ("cfg1", n), ("cfg3", n), ("cfg3f", n), ("cfg3m", n), ("cfg3L", n), ("cfg3La", n), ("cfg3M", n), ("cfg3Ma", n), ("cfg4", 2 * n)]
+            todo += [(k, n) for k in sweep]
+            only = [c for c in args.secondary.split(",") if c]
+            verify = os.environ.get("EDT_BENCH_VERIFY", "1") != "0"
+            for name, size in todo:
+                if only and name not in only:
+                    continue
+                try:
+                    if name == "cfg2_scans":
+                        from edt import _lib as _edt_lib
+                        _edt_lib.load().edt_hip_set_debug_mode(0x80)
+                    run = DeviceRun("cfg2" if name == "cfg2_scans" else name, size, dev)
+                    s, kern, _ = run.measure(max(5, min(args.steps, 200) // 2) if size > n else min(args.steps, 100 if name in sweep else 400),
+                                             args.warmup)
+                    entry = {"config": name,
+                             "workload": f"{'x'.join(str(v) for v in run.shape)} uint32 {'single-label' if name in ('cfg1', 'cfg2_scans') else 'multi-label'}: {what[name]}, "
+                                         f"anisotropy {tuple(run.an)}, black_border={run.bb}, device-resident in/out, 1 GPU", **s}
+                    entry.update(real_traffic_fields(s["ms_per_step"], kern, None, run.name))
+                    entry["output_verified"] = None
+                    if lib is not None and verify:
+                        # the timed output, bit for bit against the CPU reference on the same volume (all threads), timed as well
+                        # (configs[0] asks for the reference with parallel=1: both thread counts there)
+                        res, want = time_reference(lib, kind, run.host_labels(), tuple(run.an), run.bb,
+                                                   threads if name == "cfg1" else threads[-1:])
+                        got = run.out.cpu().numpy().reshape(-1)
+                        entry["output_verified"] = bool(np.array_equal(got, want))
+                        cpu_secondary[name] = {f"{p} thread(s)": round(v, 1) for p, v in res.items()}
+                        del got, want
+                    secondary.append(entry)
+                    del run
+                    torch.cuda.empty_cache()
+                except Exception as e:  # pragma: no cover  (a secondary must never take the headline down)
+                    secondary.append({"config": name, "error": repr(e)})
+                finally:
+                    if name == "cfg2_scans":
+                        _edt_lib.load().edt_hip_set_debug_mode(int(os.environ.get("EDT_HIP_DEBUG_MODE", "0"), 0))
+            if not only or "cfg5" in only:
+                try:
+                    secondary.append(voxel_graph_secondary(n, dev, max(5, min(args.steps, 200) // 4), args.warmup,
+                                                           lib if kind == "reference" else None))
+                except Exception as e:  # pragma: no cover
+                    secondary.append({"config": "cfg5", "error": repr(e)})
+            if not only or "cfg5_sdf" in only:
+                try:
+                    secondary.append(sdf_secondary(n, dev, max(5, min(args.steps, 200) // 4), args.warmup,
+                                                   lib if kind == "reference" else None))
+                except Exception as e:  # pragma: no cover
+                    secondary.append({"config": "cfg5_sdf", "error": repr(e)})
+            if not only or "snemi_like" in only:
+                try:
+                    secondary.append(snemi_like_secondary(dev, lib, kind))
+                except Exception as e:  # pragma: no cover
+                    secondary.append({"config": "snemi_like", "error": repr(e)})
+
+        result["config"]["output_verified"] = ok
+        result["roofline"] = roofline
+        if end_to_end is not None:
+            result["end_to_end"] = end_to_end
+        if secondary:
+            result["secondary"] = secondary
+        if not args.no_cpu_baseline:
+            if lib is None:
+                result["cpu_baseline"] = {"value": None, "unit": "Mvox/s", "cores": 0, "kind": str(kind), "sample": ""}
+            else:
+                m = min(n, 512)
+                lab = head_lab if head_lab is not None and head_lab.shape[0] == m else np.ones((m, m, m), np.uint32, order="F")
+                res, want = time_reference(lib, kind, lab, tuple(head_an), head_bb, threads)
+                if head_out is not None and lab is head_lab and want is not None:
+                    # the timed headline output, bit for bit against what the CPU reference just computed on the very same volume
+                    same = bool(np.array_equal(head_out, np.asarray(want).reshape(-1)))
+                    result["config"]["output_verified_against_reference"] = same
+                    result["config"]["output_verified"] = bool(result["config"]["output_verified"] is not False and same)
+                    result["config"]["verified_by"] = ("closed form of the box + " if ok is not None else "") + (
+                        "the compiled CPU reference on the whole volume" if kind == "reference" else "the CPU restatement (oracle port)")
+                del want
+                top = max(res, key=lambda k: res[k])
+                result["cpu_baseline"] = {
+                    # cores: the physical cores the fastest figure ran on (all of them when every hardware thread was used);
+                    # host_threads: the threads of that run
+                    "value": round(res[top], 2), "unit": "Mvox/s",
+                    "cores": (physical_cores() if int(top) >= physical_cores() else int(top)), "kind": kind,
+                    "cpu": cpu_model(), "host_threads": int(top), "hardware_threads": cores,
+                    "sample": f"whole {m}^3 uint32 headline volume ({args.config}), anisotropy {tuple(head_an)}, "
+                              "1 warm-up + best of 3; "
+                              + ", ".join(f"{p} thread(s): {v:.1f} Mvox/s" for p, v in res.items()),
+                    "secondary": cpu_secondary,
+                }
     print(json.dumps(result))
 
 

@@ -1,11 +1,12 @@
 """TEST INFRASTRUCTURE: build the reference's UNMODIFIED Cython binding (src/edt.pyx) against this repo's
 drop-in headers (cpp/edt.hpp + cpp/edt_voxel_graph.hpp over the C ABI of include/edt_hip.h).
 
-    python tests/cython_dropin.py            -> tests/_build/cydrop/edt.<EXT_SUFFIX>
+    python tests/cython_dropin.py            -> oracle/_ref/cydrop/edt.<EXT_SUFFIX>
 
-The generated C++ lands in tests/_build/cydrop (NOT next to edt.pyx), so `#include "edt.hpp"` cannot pick
-up the reference's header from src/: the only edt.hpp on the include path is ours.  Needs /root/reference
-(absent on the GPU box: the built module travels with the tree, like every other in-tree .so).
+The generated C++ lands in oracle/_ref/cydrop (NOT next to edt.pyx), so `#include "edt.hpp"` cannot pick
+up the reference's header from src/: the only edt.hpp on the include path is ours.  Needs the reference tree
+(absent on a GPU host: the built module lives beside the compiled reference under oracle/_ref, the one folder of
+reference builds that goes there with a clean checkout).
 """
 import os
 import subprocess
@@ -14,7 +15,7 @@ import sysconfig
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "euclidean-distance-transform-3d_amd")
-OUT = os.path.join(ROOT, "tests", "_build", "cydrop")
+OUT = os.path.join(ROOT, "oracle", "_ref", "cydrop")
 PYX = "/root/reference/src/edt.pyx"
 
 

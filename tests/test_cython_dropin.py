@@ -1,7 +1,7 @@
 """CPU tier: the reference's UNMODIFIED Cython binding (src/edt.pyx) compiles and links against the drop-in
 header pair cpp/edt.hpp + cpp/edt_voxel_graph.hpp (north_star: "Python via the existing Cython binding").
 
-The build is tests/cython_dropin.py (generated C++ under tests/_build/cydrop, outside the reference's src/).
+The build is tests/cython_dropin.py (generated C++ under oracle/_ref/cydrop, outside the reference's src/).
 Without a GPU only the host-side run utilities can be exercised through the built module
 (extract_runs / set_run_voxels / transfer_run_voxels, reference: src/edt_voxel_graph.hpp:238-310); the
 transforms through it are tests/test_gpu_reference_verbatim.py.

@@ -11,6 +11,7 @@ dispatches are sorted into passes by kernel name, summed, and divided by the num
 the bit-plane transposer, one per 3-D transform; voxel graph: of k_vg_rows).  usage: traffic_from_pmc.py <tag> [cfg ...]"""
 import collections, csv, glob, json, os, re, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
+OUT = os.environ.get("OUT", "session_out")   # the output folder of tools/gpu_session.sh
 cfgs = sys.argv[2:] or ["cfg2", "cfg3", "cfg3m", "cfg3L", "cfg3La", "cfg3M", "cfg3Ma", "cfg4", "cfg5"]
 FETCH_FACTOR, WRITE_FACTOR, KIB = 2.0, 1.0, 1024
 
@@ -48,7 +49,7 @@ def read_pass(cfg, i, counter):
     per = collections.defaultdict(float)
     names = collections.defaultdict(set)
     steps = {"t": 0, "vg": 0}
-    files = glob.glob(f"gpurun_out/pmc_{tag}{cfg}_{i}/**/*counter_collection.csv", recursive=True)
+    files = glob.glob(f"{OUT}/pmc_{tag}{cfg}_{i}/**/*counter_collection.csv", recursive=True)
     if not files:
         return None
     with open(files[0]) as f:
@@ -85,6 +86,6 @@ for cfg in cfgs:
 out["_note"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes (tools/gpu_session.sh pmc), every dispatch of the run "
                 "sorted into passes by kernel name and divided by the steps of the run; counter unit KiB; FETCH_SIZE x 2.0, "
                 "WRITE_SIZE x 1.0 -- profiles/r02_counter_calibration.txt; tools/traffic_from_pmc.py")
-os.makedirs("gpurun_out", exist_ok=True)
-json.dump(out, open(f"gpurun_out/{tag}_traffic.json", "w"), indent=1)
+os.makedirs(OUT, exist_ok=True)
+json.dump(out, open(f"{OUT}/{tag}_traffic.json", "w"), indent=1)
 print(json.dumps({c: {p: v["total"] for p, v in r.items() if isinstance(v, dict)} for c, r in out.items() if c != "_note"}))
