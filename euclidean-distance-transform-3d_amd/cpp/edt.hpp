@@ -42,6 +42,12 @@ namespace pyedt {
 template <typename T>
 constexpr int dtype_code() {
   static_assert(std::is_arithmetic<T>::value, "labels must be an arithmetic type");
+  // the ABI carries integers of 1/2/4/8 bytes and IEEE binary32/binary64 only: any other width (long double, a 16-byte
+  // integer) would be read as the wrong element type without any error
+  static_assert(std::is_floating_point<T>::value
+                    ? (sizeof(T) == 4 || sizeof(T) == 8)
+                    : (sizeof(T) == 1 || sizeof(T) == 2 || sizeof(T) == 4 || sizeof(T) == 8),
+                "edt_hip: label type not carried by the C ABI (integers of 1/2/4/8 bytes, float, double)");
   if (std::is_same<T, bool>::value) return EDT_BOOL;
   if (std::is_floating_point<T>::value) return sizeof(T) == 4 ? EDT_F32 : EDT_F64;
   // signed integers are reinterpreted as unsigned, like src/edt.pyx:670-705

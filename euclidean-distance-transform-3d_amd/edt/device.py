@@ -259,6 +259,19 @@ _NP_OF_CODE = {_lib.U8: np.uint8, _lib.BOOL: np.uint8, _lib.U16: np.uint16, _lib
                _lib.U64: np.uint64, _lib.F32: np.float32, _lib.F64: np.float64}
 
 
+def _key_buffer(code: int, key) -> np.ndarray:
+    """The key of :func:`select_label` in the labels' own representation.  Signed labels are compared as their bit
+    patterns, so an integer key may be given signed or unsigned (-1 and 2^64 - 1 both select the all-ones int64 / uint64
+    label); a float key of integer labels is truncated towards zero, as numpy's cast does."""
+    if code in (_lib.U8, _lib.U16, _lib.U32, _lib.U64):
+        bits = 8 * _lib.DTYPE_SIZE[code]
+        k = int(key)
+        if not -(1 << (bits - 1)) <= k < (1 << bits):
+            raise OverflowError(f"key {key!r} does not fit a {bits}-bit label")
+        return np.array([k % (1 << bits)], dtype=_NP_OF_CODE[code])
+    return np.array([key], dtype=_NP_OF_CODE[code])
+
+
 def select_label(labels: torch.Tensor, dt: torch.Tensor, key, out: torch.Tensor = None) -> torch.Tensor:
     """``dt`` where ``labels == key``, 0 elsewhere -- the image :func:`edt.each` yields for one label,
     as one streaming kernel (edt_hip_select_label_device)."""
@@ -269,12 +282,7 @@ def select_label(labels: torch.Tensor, dt: torch.Tensor, key, out: torch.Tensor 
     if out is None:
         out = torch.empty_like(dt)
     code = dtype_code(labels.dtype)
-    # the key in the labels' own representation (signed labels are compared as their bit patterns)
-    if labels.dtype in (torch.int8, torch.int16, torch.int32, torch.int64):
-        signed = {torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64}
-        host = np.array([key], dtype=signed[labels.dtype]).view(_NP_OF_CODE[code])
-    else:
-        host = np.array([key], dtype=_NP_OF_CODE[code])
+    host = _key_buffer(code, key)
     _lib.check(_lib.load().edt_hip_select_label_device(
         ctypes.c_void_p(labels.data_ptr()), code, ctypes.c_void_p(dt.data_ptr()),
         ctypes.c_void_p(host.ctypes.data), ctypes.c_void_p(out.data_ptr()), labels.numel(), _stream_ptr()))

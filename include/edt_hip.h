@@ -20,6 +20,9 @@
  *     with black_border == 0 voxels that see no boundary are +INF.
  *   - `parallel` is accepted for signature compatibility and ignored (the GPU grid
  *     replaces the reference's ThreadPool, src/threadpool.h:46-140).
+ *   - labels are integers of 1/2/4/8 bytes (signed ones read as their unsigned bit patterns), IEEE binary32 /
+ *     binary64 or bool bytes: the dtype codes below.  (Stated deviation: the reference's templates also take
+ *     long double; cpp/edt.hpp refuses it, and every other width, at compile time.)
  *
  * Every function returns EDT_OK (0) or a negative error code and never throws;
  * edt_hip_last_error() describes the last failure on the calling thread.  There is NO

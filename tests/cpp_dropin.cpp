@@ -81,27 +81,36 @@ int run_file(const char* path) {
   if (std::fread(&ncases, 4, 1, f) != 1) return 2;
   int bad = 0;
   for (int c = 0; c < ncases; c++) {
-    int32_t head[7];   // dtype, ndim, sx, sy, sz, bb, mode (0: edtsq, 1: voxel graph follows, 2: binary route)
+    int32_t head[7];   // dtype, ndim, sx, sy, sz, bb, mode (0: edtsq, 1: voxel graph follows, 2: binary route;
+                       // | 4: the template of the signed integer type of that width)
     float w[3];
     if (std::fread(head, 4, 7, f) != 7 || std::fread(w, 4, 3, f) != 3) return 2;
     const int dtype = head[0], ndim = head[1];
     const int64_t sx = head[2], sy = head[3], sz = head[4], vox = sx * sy * sz;
     static const int size_of[] = {1, 2, 4, 8, 4, 8, 1};
     std::vector<char> lab((size_t)vox * size_of[dtype]);
-    std::vector<uint8_t> graph(head[6] == 1 ? vox : 0);
+    const int mode = head[6] & 3;
+    const bool is_signed = (head[6] & 4) != 0;
+    std::vector<uint8_t> graph(mode == 1 ? vox : 0);
     std::vector<float> want(vox);
     if (std::fread(lab.data(), 1, lab.size(), f) != lab.size()) return 2;
-    if (head[6] == 1 && std::fread(graph.data(), 1, graph.size(), f) != graph.size()) return 2;
+    if (mode == 1 && std::fread(graph.data(), 1, graph.size(), f) != graph.size()) return 2;
     if (std::fread(want.data(), 4, vox, f) != (size_t)vox) return 2;
     bool ok = false;
-    switch (dtype) {
-      case EDT_U8: ok = run_case<uint8_t>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
-      case EDT_U16: ok = run_case<uint16_t>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
-      case EDT_U32: ok = run_case<uint32_t>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
-      case EDT_U64: ok = run_case<uint64_t>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
-      case EDT_F32: ok = run_case<float>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
-      case EDT_F64: ok = run_case<double>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
-      case EDT_BOOL: ok = run_case<bool>(lab, graph, head[6], ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+    if (is_signed) switch (dtype) {
+      case EDT_U8: ok = run_case<int8_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_U16: ok = run_case<int16_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_U32: ok = run_case<int32_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_U64: ok = run_case<int64_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+    }
+    else switch (dtype) {
+      case EDT_U8: ok = run_case<uint8_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_U16: ok = run_case<uint16_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_U32: ok = run_case<uint32_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_U64: ok = run_case<uint64_t>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_F32: ok = run_case<float>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_F64: ok = run_case<double>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
+      case EDT_BOOL: ok = run_case<bool>(lab, graph, mode, ndim, sx, sy, sz, w[0], w[1], w[2], head[5], want); break;
     }
     if (!ok) { std::printf("case %d (dtype %d, %dD %lldx%lldx%lld) differs\n", c, dtype, ndim, (long long)sx, (long long)sy, (long long)sz); bad++; }
   }

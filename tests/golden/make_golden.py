@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import sysconfig  # noqa: E402
 
-from synth import blocky_labels, blob_mask  # noqa: E402
+from synth import blocky_labels, blob_mask, palette_labels  # noqa: E402
 
 EXT = sysconfig.get_config_var("EXT_SUFFIX")
 spec = importlib.util.spec_from_file_location("edt", os.path.join(ROOT, "oracle", "_ref", "edt" + EXT))
@@ -102,7 +102,55 @@ def main():
                           black_border=bb,
                           out=ref.edtsq(m, anisotropy=an, black_border=bb, voxel_graph=g)))
     pack(cases, os.path.join(HERE, "edt_sdf_voxel_graph.npz"))
+    label_values()
+
+
+LABEL_DTYPES = [np.uint64, np.int64, np.uint32, np.int32, np.uint16, np.int16, np.uint8, np.int8, np.float64,
+                np.float32, bool]
+
+
+def label_values():
+    """edt_label_values.npz: the reference's Python layer on labels across each dtype's full value range
+    (synth.palette_labels): edtsq / edt, sdf, voxel graph, and each() over the integer and bool palettes."""
+    rng = np.random.default_rng(20261016)
+    anisos = [(1, 1, 1), (6, 6, 30), (0.5, 0.7, 1.3), (3, 1, 2)]
+    cases = []
+    for t, dtype in enumerate(LABEL_DTYPES * 3):
+        dims = 1 + t % 3
+        shape = tuple(int(rng.integers(4, 26)) for _ in range(dims))
+        order = "CF"[(t // 3) % 2]
+        lab = palette_labels(shape, dtype, rng=rng, block=int(rng.integers(1, 5)), order=order)
+        if np.dtype(dtype).kind == "f":
+            # the module is built with the reference's own -ffast-math: it flushes denormal labels to zero and its NaN
+            # comparisons are not IEEE.  Those two values are pinned against the strict build instead
+            # (tests/test_oracle.py, tests/test_gpu_label_values.py); -0.0, +-inf and 1+ulp stay.
+            # (by their bits: this process runs with denormals-are-zero once the module is loaded)
+            bits = lab.view(f"u{lab.itemsize}")
+            nexp = 52 if lab.itemsize == 8 else 23
+            expo, mant = bits >> nexp, bits & ((1 << nexp) - 1)
+            odd = np.isnan(lab) | (((expo & ((1 << (8 * lab.itemsize - 1 - nexp)) - 1)) == 0) & (mant != 0))
+            lab[odd] = lab.dtype.type(2.0)
+        an = anisos[t % len(anisos)][:dims]
+        an_arg = an[0] if dims == 1 else an
+        bb = bool(t % 2)
+        common = dict(labels=lab, order=order, anisotropy=np.array(an, dtype=np.float64), black_border=bb)
+        cases.append(dict(kind="edtsq", edtsq=ref.edtsq(lab, anisotropy=an_arg, black_border=bb),
+                          edt=ref.edt(lab, anisotropy=an_arg, black_border=bb), **common))
+        if dims >= 2:
+            cases.append(dict(kind="sdf", out=ref.sdf(lab, anisotropy=an, black_border=bb), **common))
+            g = rng.integers(0, 64, size=shape).astype(np.uint8)
+            g[rng.random(shape) < 0.6] = 0b00111111
+            g = np.asfortranarray(g) if order == "F" else g
+            cases.append(dict(kind="voxel_graph", graph=g,
+                              out=ref.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=g), **common))
+        if t < len(LABEL_DTYPES) and np.dtype(dtype).kind in "iub":
+            # (float labels left out: the reference keys its runs by a std::map, which NaN cannot be ordered in)
+            dt = ref.edt(lab, anisotropy=an_arg, black_border=bb)
+            pairs = list(ref.each(lab, dt))
+            cases.append(dict(kind="each", dt=dt, keys=np.array([k for k, _ in pairs], dtype=lab.dtype),
+                              images=np.stack([img for _, img in pairs]), **common))
+    pack(cases, os.path.join(HERE, "edt_label_values.npz"))
 
 
 if __name__ == "__main__":
-    main()
+    label_values() if sys.argv[1:] == ["--label-values"] else main()

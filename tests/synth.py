@@ -21,6 +21,80 @@ def blocky_labels(shape, nlabels=5, zero_frac=0.2, block=4, rng=None):
     return np.ascontiguousarray(a[tuple(slice(0, s) for s in shape)])
 
 
+def _nan(bits, dtype):
+    return np.array([bits], dtype=np.uint64 if np.dtype(dtype).itemsize == 8 else np.uint32).view(dtype)[0]
+
+
+# Label values that break narrowed comparisons: neighbouring values are equal under some narrowing (the low half of the
+# bits, float64 -> float32, denormals flushed to zero) and different at full width.  2^32, 0x100, 5e-324 and 1e-45 are
+# non-zero labels whose low bits, or whose narrowed value, are zero.  The NaNs carry different payloads and one is
+# negative; a block of one NaN is still a run of voxels that compare unequal to each other.  -0.0 is background.
+_INT_PALETTES = {
+    8: [1, 1 + 2**32, 2**32, 2**63, 2**63 + 1, 2**64 - 1],                      # uint64
+    -8: [-1, 1, -2**63, 2**40, 2**40 + 1, 1 + 2**32],                           # int64
+    4: [1, 1 + 2**16, 2**16, 2**31, 2**31 + 1, 2**32 - 1],                      # (u)int32 (2^32-1 is -1)
+    2: [1, 0x101, 0x100, 0x8000, 0xFFFF],                                       # (u)int16
+    1: [-128, -1, 1, 127],                                                      # (u)int8
+}
+
+
+def palette(dtype):
+    """The non-zero (except -0.0) label values of :func:`palette_labels` for ``dtype``, as an array of that dtype."""
+    dt = np.dtype(dtype)
+    if dt == np.bool_:
+        return np.array([1], dtype=np.uint8).view(bool)
+    if dt.kind in "iu":
+        vals = _INT_PALETTES[-8 if dt == np.int64 else dt.itemsize]
+        width = 8 * dt.itemsize
+        return np.array([v % (1 << width) for v in vals], dtype=f"u{dt.itemsize}").view(dt)
+    if dt == np.float64:
+        vals = [1.0, 1.0 + 2.0**-52, 5e-324, 1e300, np.inf, -np.inf, -0.0]
+        nans = [0x7FF8000000000000, 0x7FF0000000000001, 0x7FF8DEADBEEF0001, 0xFFF8000000000000]
+    elif dt == np.float32:
+        vals = [1.0, float(np.nextafter(np.float32(1), np.float32(2))), 1e-45, np.inf, -np.inf, -0.0]
+        nans = [0x7FC00000, 0x7F800001, 0x7FC0BEEF, 0xFFC00000]
+    else:
+        raise TypeError(f"no palette for {dt}")
+    return np.concatenate([np.array(vals, dtype=dt), np.array([_nan(b, dt) for b in nans], dtype=dt)])
+
+
+def palette_labels(shape, dtype, rng=None, block=3, zero_frac=0.15, order="C"):
+    """A :func:`blocky_labels` structure whose block ids are mapped onto :func:`palette` of ``dtype`` (0 stays 0).
+
+    bool volumes are built with ``.view(bool)`` from bytes 0 / 1 only: other byte values are undefined for numpy's bool
+    and are left out."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    pal = palette(dtype)
+    ids = blocky_labels(shape, nlabels=len(pal), zero_frac=zero_frac, block=block, rng=rng)
+    if np.dtype(dtype) == np.bool_:
+        lab = (ids != 0).astype(np.uint8).view(bool)
+    else:
+        lab = np.concatenate([np.zeros(1, dtype=pal.dtype), pal])[ids]
+    return np.asfortranarray(lab) if order == "F" else np.ascontiguousarray(lab)
+
+
+def narrowed(labels):
+    out = _narrowed(labels)
+    return np.asfortranarray(out) if labels.flags.f_contiguous and not labels.flags.c_contiguous else out
+
+
+def _narrowed(labels):
+    """``labels`` with every value narrowed the way a kernel could get it wrong, in the original dtype: integers of 16 bits
+    or more cut to their low half, float64 through float32, float32 denormals flushed to (signed) zero."""
+    dt = labels.dtype
+    if dt.kind in "iu":
+        assert dt.itemsize > 1
+        half = labels.view(f"u{dt.itemsize}") & ((1 << (4 * dt.itemsize)) - 1)
+        return half.astype(f"u{dt.itemsize}").view(dt).reshape(labels.shape)
+    if dt == np.float64:
+        with np.errstate(over="ignore", invalid="ignore"):
+            return labels.astype(np.float32).astype(np.float64)
+    if dt == np.float32:
+        tiny = np.finfo(np.float32).tiny
+        return np.where(np.abs(labels) < tiny, np.copysign(np.float32(0), labels), labels).astype(np.float32)
+    raise TypeError(dt)
+
+
 def blob_mask(shape, rng=None, p=0.6, block=4):
     """Binary blobs: a coarse random field up-sampled by `block`."""
     rng = np.random.default_rng(0) if rng is None else rng

@@ -120,6 +120,32 @@ def build_cpp_dropin(tmp_path):
     return exe
 
 
+def _syntax_check(tmp_path, label_type):
+    import subprocess
+    src = tmp_path / "label_type.cpp"
+    src.write_text('#include "edt.hpp"\n'
+                   f"float* f({label_type}* labels) {{ return edt::edt<{label_type}>(labels, 4, 3, 2); }}\n")
+    pkg = os.path.join(ROOT, "euclidean-distance-transform-3d_amd")
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(pkg, "cpp"), str(src)]
+    return subprocess.run(cmd, capture_output=True, text=True)
+
+
+@pytest.mark.parametrize("label_type", ["long double", "__int128"])
+def test_cpp_header_refuses_label_types_the_abi_does_not_carry(tmp_path, label_type):
+    """edt::edt<long double> used to compile and read 16-byte elements as doubles; now a static_assert refuses it."""
+    res = _syntax_check(tmp_path, label_type)
+    assert res.returncode != 0
+    assert "label type not carried by the C ABI" in res.stderr, res.stderr
+
+
+@pytest.mark.parametrize("label_type", ["bool", "int8_t", "uint16_t", "int32_t", "int64_t", "uint64_t", "float",
+                                        "double"])
+def test_cpp_header_takes_the_label_types_of_the_abi(tmp_path, label_type):
+    res = _syntax_check(tmp_path, label_type)
+    assert res.returncode == 0, res.stderr
+
+
 def test_cpp_header_is_a_drop_in(tmp_path):
     """The reference's C++ signatures (edt::edt<T>, pyedt::_edt3dsq<T>, ...) compile and link
     against the C ABI; on a GPU-less host the call fails loudly instead of computing on the CPU."""
@@ -326,3 +352,29 @@ def test_pitch_of_the_index_buffer_follows_the_slice_size(lib, monkeypatch):
     monkeypatch.setenv("EDT_HIP_PLANE_PAD_BYTES", "0")
     assert with_pad_2d == ws((1024, 1024, 1), ndim=2)
     assert with_pad_stack == ws((1024, 1024, 16), flags=_lib.FLAG_BATCH_2D)
+
+
+def test_select_label_key_in_the_labels_representation():
+    """edt.device.select_label's key: an integer label may be named by its signed or its unsigned value (uint64 labels
+    reach torch as int64 views), a whole-number float key still selects the integer label, and a key no label of that
+    width can hold is refused instead of wrapping."""
+    from edt import _lib
+    from edt.device import _key_buffer
+
+    def bits(code, key):
+        return _key_buffer(code, key).tobytes()
+
+    ones64 = b"\xff" * 8
+    for key in (-1, -1.0, 2**64 - 1, np.int64(-1), np.uint64(2**64 - 1)):
+        assert bits(_lib.U64, key) == ones64, key
+    for key in (2**63 + 1, -(2**63 - 1), np.uint64(2**63 + 1)):
+        assert bits(_lib.U64, key) == np.array([2**63 + 1], dtype=np.uint64).tobytes(), key
+    assert bits(_lib.U64, 2**63) == bits(_lib.U64, -(2**63))
+    assert bits(_lib.U32, 7.9) == bits(_lib.U32, 7) and bits(_lib.U32, -2.5) == bits(_lib.U32, -2)
+    assert bits(_lib.U16, 0xFFFF) == bits(_lib.U16, -1) and bits(_lib.U8, -128) == bits(_lib.U8, 0x80)
+    for code, key in ((_lib.U64, 2**64), (_lib.U64, -(2**63) - 1), (_lib.U16, 0x10000), (_lib.U8, -129)):
+        with pytest.raises(OverflowError):
+            _key_buffer(code, key)
+    assert bits(_lib.F64, 5e-324) == np.array([5e-324]).tobytes()
+    assert bits(_lib.F32, -0.0) == np.array([-0.0], dtype=np.float32).tobytes()
+    assert np.isnan(_key_buffer(_lib.F32, float("nan"))[0])

@@ -42,6 +42,31 @@ def test_golden_random(edt_gpu):
         assert same(got, c["edt"]), (n, lab.shape, lab.dtype, explain(got, c["edt"]))
 
 
+def test_golden_label_values(edt_gpu):
+    """tests/golden/edt_label_values.npz: the reference's Python module on labels across each dtype's full value range."""
+    for n, c in enumerate(load_golden("edt_label_values.npz")):
+        lab = c["labels"]
+        lab = np.asfortranarray(lab) if str(c["order"]) == "F" else np.ascontiguousarray(lab)
+        kind, bb = str(c["kind"]), bool(c["black_border"])
+        an = tuple(c["anisotropy"])
+        an = an[0] if lab.ndim == 1 else an
+        if kind == "edtsq":
+            got = edt_gpu.edtsq(lab, anisotropy=an, black_border=bb)
+            assert same(got, c["edtsq"]), (n, lab.shape, lab.dtype, explain(got, c["edtsq"]))
+            got = edt_gpu.edt(lab, anisotropy=an, black_border=bb)
+            assert same(got, c["edt"]), (n, lab.shape, lab.dtype, explain(got, c["edt"]))
+        elif kind == "sdf":
+            got = edt_gpu.sdf(lab, anisotropy=an, black_border=bb)
+            assert same(got, c["out"]), (n, lab.shape, lab.dtype, explain(got, c["out"]))
+        elif kind == "voxel_graph":
+            got = edt_gpu.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=c["graph"])
+            assert same(got, c["out"]), (n, lab.shape, lab.dtype, explain(got, c["out"]))
+        else:
+            got = list(edt_gpu.each(lab, edt_gpu.edt(lab, anisotropy=an, black_border=bb)))
+            assert [k for k, _ in got] == c["keys"].tolist(), n
+            assert all(same(img, want) for (_, img), want in zip(got, c["images"])), n
+
+
 def test_golden_configs(edt_gpu):
     for c in load_golden("edt_configs.npz"):
         lab = np.asfortranarray(c["labels"])
@@ -318,10 +343,30 @@ def test_cpp_drop_in_header_on_gpu(edt_gpu, oracle_port, tmp_path):
         blob.append(lab.tobytes(order="F"))
         blob.append(np.asfortranarray(want).astype(np.float32).tobytes(order="F"))
         nbin += 1
+    # labels across the full value range of uint64_t, int64_t (mode bit 4: the template of the signed type), double and
+    # float (synth.palette_labels), through every entry point of the facade
+    from synth import palette_labels
+    npal = 0
+    for t, dt in enumerate([np.uint64, np.int64, np.float64, np.float32] * 4):
+        dims = 1 + t % 3
+        shape = tuple(int(rng.integers(2, 40)) for _ in range(dims))
+        lab = palette_labels(shape, dt, rng=rng, block=int(rng.integers(1, 5)), order="F")
+        an = tuple(float(a) for a in ANISO[int(rng.integers(0, len(ANISO)))][:dims])
+        bb = bool(rng.integers(0, 2))
+        mode = 2 if dims >= 2 and t % 4 == 3 else 0
+        want = oracle_port.binary_edtsq(lab, an, bb) if mode == 2 else oracle_port.edtsq(lab, an[0] if dims == 1 else an, bb)
+        ext = shape + (1,) * (3 - dims)
+        w = an + (1.0,) * (3 - dims)
+        mode |= 4 if np.dtype(dt).kind == "i" else 0
+        blob.append(struct.pack("<7i3f", harness._DTYPE_CODE[np.dtype(dt)], dims, ext[0], ext[1], ext[2], int(bb), mode, *w))
+        blob.append(lab.tobytes(order="F"))
+        blob.append(np.asfortranarray(want).astype(np.float32).tobytes(order="F"))
+        npal += 1
     path = tmp_path / "cases.bin"
-    path.write_bytes(struct.pack("<i", 60 + nbin) + b"".join(blob))
+    ncases = 60 + nbin + npal
+    path.write_bytes(struct.pack("<i", ncases) + b"".join(blob))
     res = subprocess.run([exe, str(path)], capture_output=True, text=True)
-    assert res.returncode == 0 and f"{60 + nbin} of {60 + nbin}" in res.stdout, res.stdout + res.stderr
+    assert res.returncode == 0 and f"{ncases} of {ncases}" in res.stdout, res.stdout + res.stderr
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.uint64, np.float32, np.float64])

@@ -100,6 +100,24 @@ for c in load('edt_sdf_voxel_graph.npz'):
         got = edt.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=c['graph'])
     assert same(got, c['out']), (n, str(c['kind']))
     n += 1
+for c in load('edt_label_values.npz'):
+    lab = c['labels']
+    lab = np.asfortranarray(lab) if str(c['order']) == 'F' else np.ascontiguousarray(lab)
+    kind, bb = str(c['kind']), bool(c['black_border'])
+    an = tuple(c['anisotropy'])
+    an = an[0] if lab.ndim == 1 else an
+    if kind == 'edtsq':
+        assert same(edt.edtsq(lab, anisotropy=an, black_border=bb), c['edtsq']), n
+        assert same(edt.edt(lab, anisotropy=an, black_border=bb), c['edt']), n
+    elif kind == 'sdf':
+        assert same(edt.sdf(lab, anisotropy=an, black_border=bb), c['out']), n
+    elif kind == 'voxel_graph':
+        assert same(edt.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=c['graph']), c['out']), n
+    else:
+        got = list(edt.each(lab, edt.edt(lab, anisotropy=an, black_border=bb)))
+        assert [k for k, _ in got] == c['keys'].tolist(), n
+        assert all(same(img, want) for (_, img), want in zip(got, c['images'])), n
+    n += 1
 print('ok', n)
 """
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([moddir] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))

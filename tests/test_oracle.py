@@ -1,6 +1,8 @@
 """CPU tests that PIN the oracle (oracle/edt_oracle.c) before anything is compared to it:
 against the golden vectors recorded from the reference, the reference's hand-derivable known
 answers, the brute-force specification, and -- where available -- the compiled reference."""
+import os
+
 import numpy as np
 import pytest
 
@@ -161,14 +163,37 @@ def test_against_compiled_reference(oracle_port, oracle_ref):
         assert same(oracle_port.edtsq(lab, an, bb), oracle_ref.edtsq(lab, an, bb, parallel=1 + t % 2))
 
 
-def test_reference_fast_math_twin_agrees(oracle_ref):
-    # the setup.py-flag build and the strict build agree bit-for-bit
+def _in_fresh_process(call):
+    """Run ``test_oracle.<call>`` in a child interpreter.  For anything that loads the reference built with -ffast-math:
+    that library turns on flush-to-zero / denormals-are-zero for the whole process it is loaded into, and every later
+    computation on denormal labels -- the oracle's and the compiled reference's alike -- would read them as 0."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    code = f"import numpy as np, test_oracle; test_oracle.{call}; print('child ok')"
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests"), ROOT]))
+    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
+    assert res.returncode == 0 and "child ok" in res.stdout, res.stdout + res.stderr
+
+
+def denormals_are_honoured():
+    """False once a -ffast-math library has put this process into denormals-are-zero mode."""
+    return bool(np.array([1e-45], dtype=np.float32)[0] != 0) and bool(np.array([5e-324])[0] != 0)
+
+
+def _fast_math_twin():
     from oracle import harness
-    fast = harness.ref(fast=True)
+    strict, fast = harness.ref(), harness.ref(fast=True)
     rng = np.random.default_rng(13)
     lab = np.asfortranarray(blocky_labels((40, 36, 28), 12, 0.1, 5, rng).astype(np.uint32))
     for an, bb in (((6, 6, 30), True), ((0.5, 0.7, 1.3), False)):
-        assert same(oracle_ref.edtsq(lab, an, bb), fast.edtsq(lab, an, bb))
+        assert same(strict.edtsq(lab, an, bb), fast.edtsq(lab, an, bb))
+
+
+def test_reference_fast_math_twin_agrees(oracle_ref):
+    # SURVEY F3: the setup.py-flag build and the strict build agree bit-for-bit (in a child process: see _in_fresh_process)
+    _in_fresh_process("_fast_math_twin()")
+    assert denormals_are_honoured()
 
 
 def test_binary_route_against_compiled_reference(oracle_port, oracle_ref):
@@ -190,3 +215,99 @@ def test_binary_route_against_compiled_reference(oracle_port, oracle_ref):
         assert same(oracle_port.binary_edtsq(lab, an, bb), want), (t, shape, an, bb)
         differs += not same(want, oracle_ref.edtsq(lab, an, bb))
     assert differs > 10  # the case the facade used to get wrong is really exercised
+
+
+# ---- labels across each dtype's full value range (synth.palette_labels) ---------------------------------------------------
+PALETTE_DTYPES = [np.uint64, np.int64, np.uint32, np.int32, np.uint16, np.int16, np.uint8, np.int8, np.float64,
+                  np.float32, bool]
+
+
+@pytest.mark.parametrize("dtype", PALETTE_DTYPES)
+def test_palette_labels_against_compiled_reference(oracle_port, oracle_ref, dtype):
+    """The oracle port equals the compiled reference bit for bit on labels that differ only beyond a narrowing: every
+    border rule, C / F order, 1-/2-/3-D, an integer and a non-integer voxel size; sdf and the binary route too."""
+    from synth import palette_labels
+    # (1e-45 / 5e-324 are labels here: they must not be read as 0 by both checkers at once)
+    assert denormals_are_honoured(), "denormals-are-zero is on in the test process: a -ffast-math library was loaded"
+    rng = np.random.default_rng(31 + PALETTE_DTYPES.index(dtype))
+    for dims, shape in ((1, (157,)), (2, (37, 29)), (3, (23, 19, 17))):
+        for order in "CF":
+            lab = palette_labels(shape, dtype, rng=rng, block=int(rng.integers(1, 5)), order=order)
+            for an in ((2.0, 1.0, 3.0), (0.5, 0.7, 1.3)):
+                an = an[0] if dims == 1 else an[:dims]
+                for bb in (False, True):
+                    want = oracle_ref.edtsq(lab, an, bb)
+                    assert same(oracle_port.edtsq(lab, an, bb), want), (dims, order, an, bb)
+                    if dims > 1:
+                        assert same(oracle_port.sdf(lab, an, bb), oracle_ref.sdf(lab, an, bb)), (dims, order, an, bb)
+                        assert same(oracle_port.binary_edtsq(lab, an, bb), oracle_ref.binary_edtsq(lab, an, bb))
+
+
+def _narrowing_guard(dtype):
+    from oracle import harness
+    from synth import narrowed, palette_labels
+    ref = harness.ref()
+    rng = np.random.default_rng(41)
+    differs = 0
+    for t in range(6):
+        shape = ((40, 36, 28), (64, 48), (300,))[t % 3]
+        lab = palette_labels(shape, dtype, rng=rng, block=3, order="CF"[t % 2])
+        nar = narrowed(lab)
+        assert nar.dtype == lab.dtype and nar.shape == lab.shape
+        an = 1.0 if len(shape) == 1 else (1.0,) * len(shape)
+        for bb in (False, True):
+            differs += not same(ref.edtsq(lab, an, bb), ref.edtsq(nar, an, bb))
+    assert differs == 12, differs
+    if dtype == np.float32:  # the denormal alone (1e-45 flushed to 0) already changes the answer
+        lab = palette_labels((40, 36, 28), dtype, rng=rng, block=3)
+        den = np.where(lab.view(np.uint32) == 1, np.float32(0), lab)
+        assert (lab.view(np.uint32) == 1).any() and not same(ref.edtsq(lab, (1, 1, 1), False),
+                                                             ref.edtsq(den, (1, 1, 1), False))
+
+
+@pytest.mark.parametrize("dtype", ["uint64", "int64", "uint32", "int32", "uint16", "int16", "float64", "float32"])
+def test_palettes_tell_narrowed_labels_apart(oracle_ref, dtype):
+    """Discrimination guard: on every palette volume the reference's answer changes when the labels are narrowed (low
+    half of the bits, float64 -> float32, float32 denormals -> 0).  A GPU test on these volumes therefore fails for a
+    kernel that compares narrowed labels; keep it so when a palette changes.  (In a fresh process, like every check
+    whose answer depends on denormal labels: see _in_fresh_process.)"""
+    _in_fresh_process(f"_narrowing_guard(np.{dtype})")
+
+
+def _fixture_order(c):
+    lab = c["labels"]
+    return np.asfortranarray(lab) if str(c["order"]) == "F" else np.ascontiguousarray(lab)
+
+
+def test_golden_label_values(oracle_port):
+    """tests/golden/edt_label_values.npz (the reference's Python module on palette volumes of every dtype it takes)."""
+    kinds = set()
+    for n, c in enumerate(load_golden("edt_label_values.npz")):
+        lab, kind, bb = _fixture_order(c), str(c["kind"]), bool(c["black_border"])
+        an = tuple(c["anisotropy"])
+        an = an[0] if lab.ndim == 1 else an
+        kinds.add(kind)
+        if kind == "edtsq":
+            assert same(oracle_port.edtsq(lab, an, bb), c["edtsq"]), n
+            assert same(oracle_port.edt(lab, an, bb), c["edt"]), n
+        elif kind == "sdf":
+            assert same(oracle_port.sdf(lab, an, bb), c["out"]), n
+        elif kind == "voxel_graph":
+            assert same(oracle_port.edtsq(lab, an, bb, voxel_graph=c["graph"]), c["out"]), n
+    assert kinds == {"edtsq", "sdf", "voxel_graph", "each"}
+
+
+def test_golden_label_values_each():
+    """The host-side edt.each over palette labels against the reference's each() (no GPU: it only slices dt)."""
+    import edt
+    count = 0
+    for c in load_golden("edt_label_values.npz"):
+        if str(c["kind"]) != "each":
+            continue
+        lab = _fixture_order(c)
+        got = list(edt.each(lab, c["dt"]))
+        assert len(got) == len(c["keys"])
+        for (k, img), want_k, want in zip(got, c["keys"].tolist(), c["images"]):
+            assert k == want_k and same(img, want), (lab.dtype, k, want_k)
+        count += 1
+    assert count >= 8
