@@ -322,6 +322,43 @@ static int voxel_graph_host(const void *labels, int dtype, const uint8_t *graph,
   return EDT_OK;
 }
 
+// The feature transform and expand_labels on host buffers (kernels: edt_feature.hip): labels up once, the passes on the
+// device, the result down once (ndim int32 planes, or one label per voxel for expand_labels).
+static int feature_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                        float wz, int flags, bool expand, double distance, void *output) {
+  int rc = check_shape(dtype, ndim, sx, sy, sz);
+  if (rc != EDT_OK) return rc;
+  if ((rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
+  if (expand && !(distance >= 0.0)) { set_error("expand_labels: distance must be >= 0 (inf allowed)"); return EDT_ERR_BAD_ARG; }
+  const int64_t voxels = sx * sy * sz;
+  if (voxels == 0) return EDT_OK;
+  if (!labels || !output) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+  if ((rc = require_device()) != EDT_OK) return rc;
+  ListedDevice on_listed_device;
+  const size_t lbytes = (size_t)voxels * dtype_size(dtype);
+  const size_t obytes = expand ? lbytes : (size_t)voxels * ndim * sizeof(int32_t);
+  const size_t wbytes = expand ? edt_hip_expand_labels_workspace_bytes(dtype, ndim, sx, sy, sz)
+                               : edt_hip_feature_workspace_bytes(dtype, ndim, sx, sy, sz, flags);
+  const bool pooled = pool_enabled();
+  DevicePool *pool = pooled ? current_pool() : nullptr;
+  std::unique_lock<std::mutex> pool_lock;
+  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
+  DeviceBuf d_labels(pool), d_out(pool), d_ws(pool);
+  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
+  if ((rc = d_out.alloc(obytes, pooled ? 1 : -1)) != EDT_OK) return rc;
+  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
+  Prefault touch(output, obytes);
+  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
+  rc = expand ? edt_hip_expand_labels_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, distance, d_out.p, d_ws.p,
+                                             wbytes, nullptr)
+              : edt_hip_feature_transform_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags,
+                                                 (int32_t *)d_out.p, d_ws.p, wbytes, nullptr);
+  if (rc != EDT_OK) return rc;
+  touch.join();
+  EDT_HIP_TRY(hipMemcpy(output, d_out.p, obytes, hipMemcpyDeviceToHost));
+  return EDT_OK;
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -455,6 +492,17 @@ int edt_hip_edt3dsq_voxel_graph(const void *labels, int dtype, const uint8_t *gr
                                 int64_t sy, int64_t sz, float wx, float wy, float wz,
                                 int black_border, float *workspace) {
   return voxel_graph_host(labels, dtype, graph, 3, sx, sy, sz, wx, wy, wz, black_border, workspace);
+}
+
+int edt_hip_feature_transform(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
+                              float wy, float wz, int black_border, int32_t *features) {
+  return feature_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, black_border ? EDT_FLAG_BLACK_BORDER : 0, false, 0.0,
+                      features);
+}
+
+int edt_hip_expand_labels(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                          float wz, double distance, void *output) {
+  return feature_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, 0, true, distance, output);
 }
 
 }  // extern "C"

@@ -34,7 +34,7 @@ __all__ = [
     "edt", "edtsq", "sdf", "sdfsq",
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
-    "runs", "draw", "transfer", "erase", "reshape", "nvl",
+    "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
 ]
 
 
@@ -176,6 +176,70 @@ def binary_edt(data, anisotropy=None, black_border=False, parallel=1):
     return _run(data, an, black_border, None, True, ndim=data.ndim, binary=True)
 
 
+def _ft_args(data, anisotropy, name):
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"{name}: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    an = (1.0,) * data.ndim if anisotropy is None else anisotropy
+    return data, an
+
+
+def _planes_to_axes(planes, shape, order):
+    """ABI feature planes (x, y, z of the x-fastest buffer) -> scipy's ``indices`` layout: component k is the coordinate
+    along array axis k."""
+    nd = len(shape)
+    if order == "F":   # x is axis 0
+        return planes.reshape((nd,) + tuple(shape[::-1])).transpose((0,) + tuple(range(nd, 0, -1)))
+    return np.ascontiguousarray(planes.reshape((nd,) + tuple(shape))[::-1])
+
+
+def feature_transform(data, anisotropy=None, black_border=False, parallel=1, return_distances=False):
+    """Feature transform: for every voxel the index of a nearest voxel of another label (scipy's
+    ``distance_transform_edt(..., return_indices=True)`` for multi-label volumes; contract and tie rule:
+    include/edt_hip.h).  Returns int32 of shape ``(data.ndim,) + data.shape``; component k is the coordinate along
+    array axis k.  Background voxels are their own feature.  With ``black_border`` one component may be -1 or the axis
+    length (the border); a voxel without any feature (no border, one label everywhere) gets -1 in every component.
+    ``return_distances=True`` also returns ``edt(data, anisotropy, black_border)``.  The tie rule runs its passes in
+    the order of the array's memory axes, fastest first: axis 0 first for an F-contiguous array (also for one that is
+    C-contiguous as well, e.g. with unit axes, as in every entry point of this module), the last axis first otherwise."""
+    data, an = _ft_args(data, anisotropy, "feature_transform")
+    nd = data.ndim
+    if data.size == 0:
+        feats = np.zeros((nd,) + data.shape, dtype=np.int32)
+        return (feats, np.zeros(data.shape, dtype=np.float32)) if return_distances else feats
+    data, order, code, buf, extents, w = _layout(data, an, nd)
+    e = tuple(extents) + (1,) * (3 - nd)
+    ww = tuple(w) + (1.0,) * (3 - nd)
+    planes = np.empty(nd * data.size, dtype=np.int32)
+    _lib.check(_lib.load().edt_hip_feature_transform(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
+                                                     1 if black_border else 0, _ptr(planes)))
+    feats = _planes_to_axes(planes, data.shape, order)
+    if return_distances:
+        return feats, edt(data, anisotropy=an, black_border=black_border, parallel=parallel)
+    return feats
+
+
+def expand_labels(data, distance=1.0, anisotropy=None, parallel=1):
+    """Grow every label into the background by up to ``distance`` (physical units): each background voxel takes the
+    label of its feature in the feature transform of ``data == 0`` if that voxel lies within ``distance``
+    (skimage.segmentation.expand_labels with anisotropy; contract: include/edt_hip.h).  Same shape, dtype and memory
+    order as ``data``."""
+    data, an = _ft_args(data, anisotropy, "expand_labels")
+    distance = float(distance)
+    if not distance >= 0.0:
+        raise ValueError(f"expand_labels: distance must be >= 0, got {distance}")
+    if data.size == 0:
+        return data.copy()
+    nd = data.ndim
+    data, order, code, buf, extents, w = _layout(data, an, nd)
+    e = tuple(extents) + (1,) * (3 - nd)
+    ww = tuple(w) + (1.0,) * (3 - nd)
+    out = np.empty(data.shape, dtype=data.dtype, order=order)
+    _lib.check(_lib.load().edt_hip_expand_labels(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
+                                                 distance, _ptr(out)))
+    return out
+
+
 def set_devices(devices=None):
     """Z-shard every 3-D transform of host arrays over these GPUs of THIS process (``edt_hip_set_devices``: a host
     thread per device, one peer-to-peer exchange over xGMI, see ``csrc/edt_multi.hip``); ``None`` / ``[]`` = back to
@@ -247,11 +311,9 @@ def _transform(data, anisotropy, black_border, parallel, voxel_graph, take_sqrt,
     return _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim=dims, signed=signed)
 
 
-def _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim, signed=False, binary=False):
-    if data.ndim != ndim:
-        raise TypeError(f"expected a {ndim}-D array, got {data.ndim}-D")
-    if data.size == 0:
-        return np.zeros(shape=data.shape, dtype=np.float32)
+def _layout(data, anisotropy, ndim):
+    """The buffer the kernels read and how it maps onto the C ABI (x the fastest axis of memory): returns
+    (data, order, dtype code, label buffer, x-fastest extents, x-fastest voxel sizes); validates the voxel sizes."""
     if not data.flags.c_contiguous and not data.flags.f_contiguous:
         data = np.ascontiguousarray(data)
     order = "F" if data.flags.f_contiguous else "C"
@@ -276,6 +338,16 @@ def _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim, signed=Fa
         extents, w = tuple(data.shape), weights
     else:
         extents, w = tuple(data.shape[::-1]), weights[::-1]
+
+    return data, order, code, buf, extents, w
+
+
+def _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim, signed=False, binary=False):
+    if data.ndim != ndim:
+        raise TypeError(f"expected a {ndim}-D array, got {data.ndim}-D")
+    if data.size == 0:
+        return np.zeros(shape=data.shape, dtype=np.float32)
+    data, order, code, buf, extents, w = _layout(data, anisotropy, ndim)
 
     lib = _lib.load()
     out = np.empty(data.size, dtype=np.float32)

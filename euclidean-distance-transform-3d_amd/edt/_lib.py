@@ -37,6 +37,7 @@ class EdtHipError(RuntimeError):
 
 _vp, _i, _i64, _f, _sz = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
                           ctypes.c_size_t)
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); one entry per symbol declared in include/edt_hip.h
 SIGNATURES = {
@@ -91,6 +92,12 @@ SIGNATURES = {
     "edt_hip_edtsq_voxel_graph_device": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp, _vp, _sz, _vp]),
     "edt_hip_select_label_device": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "edt_hip_is_background_device": (_i, [_vp, _i, _vp, _i64, _vp]),
+    "edt_hip_feature_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64, _i]),
+    "edt_hip_feature_transform_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp, _vp, _sz, _vp]),
+    "edt_hip_feature_transform": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp]),
+    "edt_hip_expand_labels_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
+    "edt_hip_expand_labels_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _d, _vp, _vp, _sz, _vp]),
+    "edt_hip_expand_labels": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _d, _vp]),
 }
 
 _lib = None

@@ -171,6 +171,66 @@ def edt(labels: torch.Tensor, anisotropy=None, black_border=False) -> torch.Tens
     return _transform(labels, anisotropy, black_border, sqrt=True)
 
 
+def _ft_tensor(labels, anisotropy, name):
+    labels = as_device_tensor(labels)
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"{name}: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    labels = labels.contiguous()
+    nd = labels.dim()
+    an = (1.0,) * nd if anisotropy is None else (
+        (float(anisotropy),) if np.ndim(anisotropy) == 0 else tuple(float(a) for a in anisotropy))
+    if len(an) != nd:
+        raise ValueError(f"anisotropy must have {nd} entries, got {len(an)}")
+    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+    w = tuple(float(np.float32(a)) for a in an[::-1]) + (1.0,) * (3 - nd)
+    return labels, nd, ext, w
+
+
+def feature_transform(labels: torch.Tensor, anisotropy=None, black_border=False, force_generic=False) -> torch.Tensor:
+    """Feature transform of a device tensor (semantics: :func:`edt.feature_transform` on a C-ordered array; anisotropy
+    in tensor axis order).  Returns int32 of shape ``(labels.dim(),) + labels.shape`` on the same device: component k is
+    the coordinate along tensor axis k.  The kernels write the components in ABI order (x, y, z: tensor axes last to
+    first) and the result is a reordered COPY of them: at its peak the call holds twice the output (4 bytes per voxel
+    and component each) besides the workspace, which is freed before the copy."""
+    labels, nd, ext, w = _ft_tensor(labels, anisotropy, "feature_transform")
+    if labels.numel() == 0:
+        return torch.zeros((nd,) + tuple(labels.shape), dtype=torch.int32, device=labels.device)
+    lib = _lib.load()
+    code = dtype_code(labels.dtype)
+    flags = (_lib.FLAG_BLACK_BORDER if black_border else 0) | (_lib.FLAG_FORCE_GENERIC if force_generic else 0)
+    nbytes = lib.edt_hip_feature_workspace_bytes(code, nd, *ext, flags)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)
+    planes = torch.empty((nd,) + tuple(labels.shape), dtype=torch.int32, device=labels.device)  # x, y, z planes
+    _lib.check(lib.edt_hip_feature_transform_device(
+        ctypes.c_void_p(labels.data_ptr()), code, nd, *ext, *w, flags, ctypes.c_void_p(planes.data_ptr()),
+        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr()))
+    del ws
+    return planes.flip(0)  # tensor axis k = plane nd-1-k
+
+
+def expand_labels(labels: torch.Tensor, distance=1.0, anisotropy=None) -> torch.Tensor:
+    """:func:`edt.expand_labels` on a device tensor (anisotropy in tensor axis order); same shape and dtype."""
+    labels, nd, ext, w = _ft_tensor(labels, anisotropy, "expand_labels")
+    distance = float(distance)
+    if not distance >= 0.0:
+        raise ValueError(f"expand_labels: distance must be >= 0, got {distance}")
+    if labels.numel() == 0:
+        return labels.clone()
+    lib = _lib.load()
+    code = dtype_code(labels.dtype)
+    nbytes = lib.edt_hip_expand_labels_workspace_bytes(code, nd, *ext)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)
+    out = torch.empty_like(labels)
+    _lib.check(lib.edt_hip_expand_labels_device(
+        ctypes.c_void_p(labels.data_ptr()), code, nd, *ext, *w, distance, ctypes.c_void_p(out.data_ptr()),
+        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr()))
+    return out
+
+
 def _stack2d(images, anisotropy, black_border, sqrt):
     images = as_device_tensor(images)
     if images.dim() != 3:

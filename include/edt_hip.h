@@ -347,6 +347,56 @@ int edt_hip_edtsq_voxel_graph_device(const void *d_labels, int dtype, const uint
 int edt_hip_select_label_device(const void *d_labels, int dtype, const float *d_dt, const void *key,
                                 float *d_out, int64_t count, void *stream);
 
+/* ---- feature transform (nearest-boundary indices) and expand_labels ------------------------------------------------
+ * Conventions as above: x fastest, idx = x + sx * (y + sy * z), label 0 is background, labels compared at full width with
+ * their type's == (so -0.0 is background and a NaN voxel differs from every voxel).  With the squared voxel sizes
+ * D(p,q) = wx^2 (px-qx)^2 + wy^2 (py-qy)^2 + wz^2 (pz-qz)^2:
+ *   - foreground voxel p of label L != 0: its FEATURE is a voxel q with label(q) != L that minimises D(p,q); edtsq(p) is
+ *     that minimum.  With black_border the one-voxel shell around the volume counts as label 0, so one component (at most)
+ *     may be -1 or s_axis;
+ *   - background voxel: its feature is itself;
+ *   - no feature (black_border off and the whole volume one label): every component is -1.
+ * Tie rule, separable, pass by pass in the order X, Y, Z: among the candidates of minimal pass value, the one with the
+ * smallest coordinate along that pass's axis.
+ *   pass X: for p in the x-run [a,b], the candidates are a-1 (if a > 0 or black border) and b+1 (likewise); a tie takes a-1;
+ *   pass Y: the rows j of p's y-run with a finite pass-X value, with feature (fx(j), j), and the border sites a-1 and b+1,
+ *           which are their own feature (x, j);
+ *   pass Z: the same, carrying (fx, fy).
+ * Where the voxel sizes share a quantum (w_i^2 = a_i q, small integers a_i: (1,1,1), (6,6,30), (4,4,40), (0.5,0.5,1) ...)
+ * the pass values are exact integers (64-bit), so the features are fully determined by the rule.  Otherwise the passes
+ * run in fp64 and the feature satisfies D(p, f(p)) <= (1 + 2^-20) min_q D(p,q).  The same call gives the same output
+ * (no atomics decide a winner).  Limits: extents up to 2^31 - 1 per axis (features are int32), volumes past 2^31 voxels. */
+
+/* Scratch of edt_hip_feature_transform_device: 4 bytes per voxel for ndim = 1, 24 for ndim = 2, 40 for ndim = 3 (pass
+ * values, carried coordinates, hull stacks).  0 for a bad shape or flags. */
+size_t edt_hip_feature_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags);
+/* d_features: ndim planes of sx*sy*sz int32 each -- plane 0 the x coordinate of the feature, plane 1 y, plane 2 z.
+ * flags: EDT_FLAG_BLACK_BORDER, EDT_FLAG_FORCE_GENERIC (accepted; every axis length runs on the size-agnostic column
+ * kernel, so the features are the same); any other flag is EDT_ERR_UNSUPPORTED.  ndim 1..3, unused extents 1, voxel
+ * sizes as for edt_hip_edtsq_device (EDT_ERR_BAD_ARG before any device work).  NULL pointers and a missing or too small
+ * workspace are EDT_ERR_BAD_ARG.  Enqueue-only on `stream`: no allocation, no synchronisation. */
+int edt_hip_feature_transform_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
+                                     float wy, float wz, int flags, int32_t *d_features, void *d_workspace,
+                                     size_t workspace_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device).  `features` holds ndim * sx*sy*sz int32. */
+int edt_hip_feature_transform(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
+                              float wy, float wz, int black_border, int32_t *features);
+
+/* expand_labels: out = labels; for each background voxel p, with f the feature of p in the feature transform of the mask
+ * labels == 0 (black border off): out[p] = labels[f] if f exists and D(p,f) <= distance^2, where
+ *   D = (fl64(wx^2 dx^2) + fl64(wy^2 dy^2)) + fl64(wz^2 dz^2)
+ * in fp64 from the integer offsets and the fp32 voxel sizes widened to fp64 (no fma); otherwise out[p] keeps its own
+ * (background) value.  No foreground at all: out is a copy of labels.  distance >= 0, +inf allowed; NaN or negative is
+ * EDT_ERR_BAD_ARG.  The output has the labels' dtype and may not alias them.  Scratch: one byte per voxel for the mask
+ * plus the feature transform's workspace of the mask. */
+size_t edt_hip_expand_labels_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
+int edt_hip_expand_labels_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
+                                 float wy, float wz, double distance, void *d_out, void *d_workspace, size_t workspace_bytes,
+                                 void *stream);
+int edt_hip_expand_labels(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                          float wz, double distance, void *output);
+
 #ifdef __cplusplus
 }
 #endif
