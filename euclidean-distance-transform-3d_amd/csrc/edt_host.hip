@@ -359,6 +359,65 @@ static int feature_host(const void *labels, int dtype, int ndim, int64_t sx, int
   return EDT_OK;
 }
 
+// label_stats on host buffers (kernels: edt_labelstats.hip): labels up once (and the caller's field, if it brings one; else the
+// ordinary transform runs here, with sqrt), the table pass on the device, and only the table comes back.
+static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                            float wz, int black_border, const float *dt, int64_t max_labels, void *keys, int64_t *counts,
+                            float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels) {
+  int rc = check_shape(dtype, ndim, sx, sy, sz);
+  if (rc != EDT_OK) return rc;
+  if (max_labels < 1) { set_error("label_stats: max_labels must be at least 1"); return EDT_ERR_BAD_ARG; }
+  if (!dt && (rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
+  if (!n_labels) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+  const int64_t voxels = sx * sy * sz;
+  if (voxels == 0) { *n_labels = 0; return EDT_OK; }
+  if (!labels || !keys || !counts || !max || !argmax || !bbox) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+  const int64_t cap = std::min(max_labels, voxels);
+  const size_t sbytes = edt_hip_label_stats_workspace_bytes(dtype, voxels, cap);
+  if (sbytes == 0) { set_error("label_stats: max_labels out of range"); return EDT_ERR_BAD_ARG; }
+  if ((rc = require_device()) != EDT_OK) return rc;
+  ListedDevice on_listed_device;
+  const int flags = (black_border ? EDT_FLAG_BLACK_BORDER : 0) | EDT_FLAG_SQRT | (env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0);
+  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
+  const size_t tbytes = dt ? 0 : edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
+  const size_t wbytes = std::max(sbytes, tbytes);
+  // the table on the device: keys | counts | argmax | n (8-byte items) | max | bbox (4-byte items)
+  const size_t n = (size_t)cap, ksz = (size_t)dtype_size(dtype);
+  const size_t o_counts = align_up(n * ksz, 8), o_argmax = o_counts + 8 * n, o_n = o_argmax + 8 * n, o_max = o_n + 8,
+               o_bbox = o_max + 4 * n, obytes = o_bbox + 24 * n;
+  const bool pooled = pool_enabled();
+  DevicePool *pool = pooled ? current_pool() : nullptr;
+  std::unique_lock<std::mutex> pool_lock;
+  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
+  DeviceBuf d_labels(pool), d_dt(pool), d_ws(pool), d_tab(pool);
+  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
+  if ((rc = d_dt.alloc(fbytes, pooled ? 1 : -1)) != EDT_OK) return rc;
+  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
+  if ((rc = d_tab.alloc(obytes, pooled ? 3 : -1)) != EDT_OK) return rc;
+  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
+  if (dt) {
+    EDT_HIP_TRY(hipMemcpy(d_dt.p, dt, fbytes, hipMemcpyHostToDevice));
+  } else {
+    rc = run_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, (float *)d_dt.p, d_ws.p, wbytes, nullptr);
+    if (rc != EDT_OK) return rc;
+  }
+  char *tab = (char *)d_tab.p;
+  rc = edt_hip_label_stats_device(d_labels.p, dtype, (const float *)d_dt.p, ndim, sx, sy, sz, cap, tab,
+                                  (int64_t *)(tab + o_counts), (float *)(tab + o_max), (int64_t *)(tab + o_argmax),
+                                  (int32_t *)(tab + o_bbox), (int64_t *)(tab + o_n), d_ws.p, wbytes, nullptr);
+  if (rc != EDT_OK) return rc;
+  EDT_HIP_TRY(hipMemcpy(n_labels, tab + o_n, sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (*n_labels > cap) return EDT_OK;  // not an error: the caller retries with more room
+  const size_t m = (size_t)*n_labels;
+  if (m == 0) return EDT_OK;
+  EDT_HIP_TRY(hipMemcpy(keys, tab, m * ksz, hipMemcpyDeviceToHost));
+  EDT_HIP_TRY(hipMemcpy(counts, tab + o_counts, m * 8, hipMemcpyDeviceToHost));
+  EDT_HIP_TRY(hipMemcpy(argmax, tab + o_argmax, m * 8, hipMemcpyDeviceToHost));
+  EDT_HIP_TRY(hipMemcpy(max, tab + o_max, m * 4, hipMemcpyDeviceToHost));
+  EDT_HIP_TRY(hipMemcpy(bbox, tab + o_bbox, m * 24, hipMemcpyDeviceToHost));
+  return EDT_OK;
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -503,6 +562,13 @@ int edt_hip_feature_transform(const void *labels, int dtype, int ndim, int64_t s
 int edt_hip_expand_labels(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
                           float wz, double distance, void *output) {
   return feature_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, 0, true, distance, output);
+}
+
+int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                        float wz, int black_border, const float *dt, int64_t max_labels, void *keys, int64_t *counts,
+                        float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels) {
+  return label_stats_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, black_border, dt, max_labels, keys, counts, max,
+                          argmax, bbox, n_labels);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ Device-resident use (torch tensors on ``cuda``) goes through :mod:`edt.device`.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import multiprocessing
 
@@ -35,6 +36,7 @@ __all__ = [
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
+    "label_stats",
 ]
 
 
@@ -238,6 +240,82 @@ def expand_labels(data, distance=1.0, anisotropy=None, parallel=1):
     _lib.check(_lib.load().edt_hip_expand_labels(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
                                                  distance, _ptr(out)))
     return out
+
+
+LabelStats = collections.namedtuple("LabelStats", ["labels", "counts", "max", "argmax", "bbox_lo", "bbox_hi"])
+
+
+def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, max_labels=None):
+    """One table row per distinct non-zero label of ``data`` (contract: include/edt_hip.h, "label_stats"), as the named
+    tuple ``(labels, counts, max, argmax, bbox_lo, bbox_hi)`` of numpy arrays: the label values ascending (signed dtypes
+    in signed order, as :func:`each` yields them), the voxel count (int64), the largest ``dt`` over the label's voxels
+    (float32), the coordinates ``(n, ndim)`` per array axis of the voxel that attains it (int64) and the inclusive
+    bounding box per array axis (int32, ``(n, ndim)`` each).
+
+    ``dt``: any NaN-free float32 array of ``data``'s shape (``edt``, ``sdf`` ...).  ``dt=None`` computes
+    ``edt(data, anisotropy, black_border)`` on the device inside the same call: the distance field never crosses to the
+    host, only the table does.  ``-0.0`` is background and NaN voxels of float labels belong to no label.
+
+    Ties: among the voxels that attain the maximum, ``argmax`` is the one with the smallest index in the array's MEMORY
+    order.  For a C-contiguous array that is ``np.unravel_index(np.argmax(np.where(data == L, dt, -inf)), data.shape)``;
+    for an F-contiguous one (also one that is C-contiguous as well, e.g. with unit axes, as in every entry point of this
+    module) the first along ``order='F'``, i.e. the first axis runs fastest.
+
+    ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x the room while it proves
+    too small; an explicit ``max_labels`` that proves too small raises ``ValueError``."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"label_stats: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    nd = data.ndim
+    if dt is not None:
+        dt = np.asarray(dt)
+        if dt.shape != data.shape or dt.dtype != np.float32:
+            raise ValueError("dt must be a float32 array of the data's shape")
+    if max_labels is not None and int(max_labels) < 1:
+        raise ValueError(f"label_stats: max_labels must be at least 1, got {max_labels}")
+    an = (1.0,) * nd if anisotropy is None else anisotropy
+    if data.size == 0:
+        _label_code(data)
+        return LabelStats(np.zeros(0, dtype=data.dtype), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32),
+                          np.zeros((0, nd), dtype=np.int64), np.zeros((0, nd), dtype=np.int32),
+                          np.zeros((0, nd), dtype=np.int32))
+    data, order, code, buf, extents, w = _layout(data, an, nd)
+    if dt is not None:
+        dt = np.asfortranarray(dt) if order == "F" else np.ascontiguousarray(dt)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    ww = tuple(w) + (1.0,) * (3 - nd)
+    voxels = data.size
+    if max_labels is not None:
+        cap = min(int(max_labels), voxels)
+    elif _lib.DTYPE_SIZE[code] <= 2:
+        cap = min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1)
+    else:
+        cap = min(voxels, 65536)
+    lib = _lib.load()
+    while True:
+        keys = np.empty(cap, dtype=buf.dtype)
+        counts, arg = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int64)
+        mx, bbox = np.empty(cap, dtype=np.float32), np.empty((cap, 6), dtype=np.int32)
+        n = ctypes.c_int64(0)
+        _lib.check(lib.edt_hip_label_stats(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
+                                           1 if black_border else 0, None if dt is None else _ptr(dt), cap, _ptr(keys),
+                                           _ptr(counts), _ptr(mx), _ptr(arg), _ptr(bbox), ctypes.byref(n)))
+        n = int(n.value)
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"label_stats: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    keys = keys[:n].view(data.dtype)       # (signed dtypes: the bit patterns back under their own type)
+    counts, mx, arg, bbox = counts[:n], mx[:n], arg[:n], bbox[:n]
+    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
+        perm = np.argsort(keys, kind="stable")
+        keys, counts, mx, arg, bbox = keys[perm], counts[perm], mx[perm], arg[perm], bbox[perm]
+    lo, hi = bbox[:, 0:2 * nd:2], bbox[:, 1:2 * nd:2]
+    argmax = np.stack(np.unravel_index(arg, data.shape, order=order), axis=1).astype(np.int64).reshape(n, nd)
+    if order == "C":                       # x is the LAST array axis
+        lo, hi = lo[:, ::-1], hi[:, ::-1]
+    return LabelStats(np.ascontiguousarray(keys), counts, mx, argmax, np.ascontiguousarray(lo), np.ascontiguousarray(hi))
 
 
 def set_devices(devices=None):

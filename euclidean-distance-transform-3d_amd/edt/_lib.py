@@ -98,6 +98,9 @@ SIGNATURES = {
     "edt_hip_expand_labels_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
     "edt_hip_expand_labels_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _d, _vp, _vp, _sz, _vp]),
     "edt_hip_expand_labels": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _d, _vp]),
+    "edt_hip_label_stats_workspace_bytes": (_sz, [_i, _i64, _i64]),
+    "edt_hip_label_stats_device": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "edt_hip_label_stats": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@ before they reach the kernels (reference: src/edt.pyx:651-656).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -424,6 +425,88 @@ def each(labels: torch.Tensor, dt: torch.Tensor, in_place: bool = False):
     skipped.  ``in_place=True`` reuses ONE output tensor for every label (the reference's read-only
     in-place image).  The DT never leaves the device."""
     return _DeviceLabelImages(labels, dt, bool(in_place))
+
+
+LabelStats = collections.namedtuple("LabelStats", ["labels", "counts", "max", "argmax", "bbox_lo", "bbox_hi"])
+
+_SIGNED_TORCH = (torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def default_max_labels(code: int, voxels: int):
+    """(first capacity, whether it is exact) of a ``label_stats`` call without ``max_labels``: 8- and 16-bit labels
+    cannot have more than 255 / 65535 distinct non-zero values; wider ones start at 65536 and are retried."""
+    if _lib.DTYPE_SIZE[code] <= 2:
+        return min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1), True
+    return min(voxels, 65536), False
+
+
+def _label_stats_raw(labels, dt, nd, ext, cap):
+    """One call of edt_hip_label_stats_device: (n_labels, keys, counts, max, argmax, bbox) with ``cap`` rows each."""
+    lib = _lib.load()
+    dev = labels.device
+    code = dtype_code(labels.dtype)
+    nbytes = lib.edt_hip_label_stats_workspace_bytes(code, labels.numel(), cap)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    keys = torch.empty(cap, dtype=labels.dtype, device=dev)
+    counts = torch.empty(cap, dtype=torch.int64, device=dev)
+    mx = torch.empty(cap, dtype=torch.float32, device=dev)
+    arg = torch.empty(cap, dtype=torch.int64, device=dev)
+    bbox = torch.empty((cap, 6), dtype=torch.int32, device=dev)
+    n = torch.empty(1, dtype=torch.int64, device=dev)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    _lib.check(lib.edt_hip_label_stats_device(vp(labels), code, vp(dt), nd, *ext, cap, vp(keys), vp(counts), vp(mx),
+                                              vp(arg), vp(bbox), vp(n), vp(ws), ws.numel(), _stream_ptr()))
+    return int(n.item()), keys, counts, mx, arg, bbox
+
+
+def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> LabelStats:
+    """One table row per distinct non-zero label, in one or two streaming sweeps over ``labels`` and ``dt`` (contract:
+    include/edt_hip.h, "label_stats"): ``(labels, counts, max, argmax, bbox_lo, bbox_hi)`` as device tensors --
+    the label values ascending (signed dtypes in signed order, as :func:`each` yields them), the voxel count (int64), the
+    largest ``dt`` of the label (float32), the coordinates ``(n, ndim)`` along the tensor's axes of the first voxel, in
+    memory order, that attains it (int64), and the inclusive bounding box per tensor axis (int32, ``(n, ndim)`` each).
+    ``dt``: any NaN-free float32 tensor of the labels' shape (edt, sdf ...).  The only host synchronisation is reading
+    the number of labels.  ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x
+    the room while it proves too small; an explicit ``max_labels`` that proves too small raises ``ValueError``."""
+    labels, dt = as_device_tensor(labels), as_device_tensor(dt)
+    if labels.shape != dt.shape or dt.dtype != torch.float32:
+        raise ValueError("dt must be a float32 tensor of the labels' shape")
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"label_stats: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    if max_labels is not None and int(max_labels) < 1:
+        raise ValueError(f"label_stats: max_labels must be at least 1, got {max_labels}")
+    nd = labels.dim()
+    dev = labels.device
+    code = dtype_code(labels.dtype)
+    voxels = labels.numel()
+    if voxels == 0:
+        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+        return LabelStats(z(labels.dtype, 0), z(torch.int64, 0), z(torch.float32, 0), z(torch.int64, 0, nd),
+                          z(torch.int32, 0, nd), z(torch.int32, 0, nd))
+    labels, dt = labels.contiguous(), dt.contiguous()
+    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+    cap = default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
+    while True:
+        n, keys, counts, mx, arg, bbox = _label_stats_raw(labels, dt, nd, ext, cap)
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"label_stats: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    keys, counts, mx, arg, bbox = keys[:n], counts[:n], mx[:n], arg[:n], bbox[:n]
+    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
+        perm = torch.argsort(keys, stable=True)
+        keys, counts, mx, arg, bbox = keys[perm], counts[perm], mx[perm], arg[perm], bbox[perm]
+    coords = []
+    for extent in ext[:nd]:            # x, y, z of the flat index
+        coords.append(arg % extent)
+        arg = arg // extent
+    argmax = torch.stack(coords[::-1], dim=1)
+    lo = bbox[:, 0:2 * nd:2].flip(1).contiguous()
+    hi = bbox[:, 1:2 * nd:2].flip(1).contiguous()
+    return LabelStats(keys, counts, mx, argmax, lo, hi)
 
 
 def pass_times():

@@ -397,6 +397,46 @@ int edt_hip_expand_labels_device(const void *d_labels, int dtype, int ndim, int6
 int edt_hip_expand_labels(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
                           float wz, double distance, void *output);
 
+/* ---- label_stats: per-label count, maximum of a field, its argmax and the bounding box ------------------------------
+ * Conventions as above: x fastest, idx = x + sx * (y + sy * z), label 0 is background, labels compared at full width with
+ * their type's ==.  `dt` is any NaN-free fp32 field of the labels' shape (+inf and negative values included: edt without a
+ * black border, sdf).  The table has one entry for each distinct non-zero label L:
+ *   key     L, in the labels' dtype (signed integers as their unsigned bit patterns, as everywhere at this ABI);
+ *   count   the number of voxels with label L (int64);
+ *   max     the largest dt over those voxels (fp32);
+ *   argmax  the smallest idx among the label's voxels whose dt equals max (int64);
+ *   bbox    inclusive min and max of x, y and z over the label's voxels: int32 x 6 in the order x0,x1,y0,y1,z0,z1
+ *           (unused axes 0,0).
+ * Floating-point labels: -0.0 is background; a NaN voxel equals nothing, so it belongs to no label, has no entry and is in
+ * no count.  Bool: one label, any non-zero byte is key 1.  If dt holds NaN, the max and argmax of the labels it touches are
+ * unspecified (nothing faults).
+ * Order: ascending key -- unsigned order for integers, numeric order for floats.
+ * Determinism: the same call gives the same table, bit for bit (integer min / max / add atomics over an order-preserving
+ * map of dt; nothing depends on which thread won a hash slot).
+ * Capacity: the output arrays hold max_labels entries (bbox: 6 * max_labels).  With at most max_labels distinct non-zero
+ * labels *n_labels is their number and the table is complete.  Otherwise *n_labels is SOME value greater than max_labels,
+ * the arrays' contents are unspecified and the call still returns EDT_OK: the caller retries with more room.
+ * Sizes: offsets are 64-bit throughout (volumes past 2^32 voxels). */
+
+/* Scratch of edt_hip_label_stats_device: nothing per voxel; the label table -- 256 / 65536 direct-indexed slots for 8- /
+ * 16-bit labels, else an open-addressing hash table of the power of two >= max(1024, 2 * max_labels) slots, 52 bytes per
+ * slot, plus 8 bytes per label (a max_labels above `voxels` counts as `voxels`).  0 for a bad dtype or max_labels < 1. */
+size_t edt_hip_label_stats_workspace_bytes(int dtype, int64_t voxels, int64_t max_labels);
+/* ndim 1..3, unused extents 1, max_labels >= 1; NULL pointers and a missing or too small workspace are EDT_ERR_BAD_ARG
+ * before any device work.  Enqueue-only on `stream`: no allocation, no synchronisation; the workspace is cleared by the call
+ * itself (a reused one needs no memset).  d_n_labels: one int64 on the device. */
+int edt_hip_label_stats_device(const void *d_labels, int dtype, const float *d_dt, int ndim, int64_t sx, int64_t sy,
+                               int64_t sz, int64_t max_labels, void *d_keys, int64_t *d_counts, float *d_max,
+                               int64_t *d_argmax, int32_t *d_bbox, int64_t *d_n_labels, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device).  dt: a HOST field, or NULL: the ordinary transform of the labels with
+ * these voxel sizes and this border rule runs on the device first (distances, i.e. with sqrt: edt_hip_edt3d's field; the
+ * voxel-size rules above apply) and never leaves it.  Only the table is copied back. */
+int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                        float wz, int black_border, const float *dt, int64_t max_labels, void *keys, int64_t *counts,
+                        float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels);
+
 #ifdef __cplusplus
 }
 #endif
