@@ -78,12 +78,11 @@ struct Plan {
                               // passes Y and Z then exists there too
   int64_t code_pitch = 0;     // elements between the slices of the index buffer: sx * sy, or padded (plane_pad_elems)
   // the tiles the 16-bit integer column kernel hands to the fp32 kernel (edt_colq16.hip): kQ16Slots counters, one per
-  // column-pass launch of a call, and one array of tile ids (launches are stream-ordered: the array is reused)
-  uint32_t *q16_counts = nullptr, *q16_ids = nullptr;
+  // column-pass launch of a call, and one array of tile ids
+  HandOver q16;
   // which tiles of pass Y left their results in the 16-bit plane (= codes): one bit per (x-tile, z), behind the counters
   uint32_t *q16_map = nullptr;
   int q16_map_words = 0;  // words per x-tile
-  int64_t q16_id_capacity = 0;  // tile ids q16_ids holds
   size_t bytes = 0;
 };
 
@@ -145,7 +144,7 @@ constexpr int kQ16Slots = 256;  // counters of the 16-bit integer column kernel'
 constexpr int EDT_FLAG_NO_INDEX_FORM = 0x8000;  // internal: plan without the index buffer
 static int64_t plan_code_slab(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
   if (ndim < 2 || sx % 4 != 0 || sx * sy > kCodeSlabVoxels || (flags & (EDT_FLAG_NO_INDEX_FORM | EDT_FLAG_SMALL_WORKSPACE))) return 0;
-  if ((flags & EDT_FLAG_FORCE_GENERIC) || env_force_generic() || (g_debug_mode & (0x100000 | 64 | 32))) return 0;
+  if ((flags & EDT_FLAG_FORCE_GENERIC) || env_force_generic() || (g_debug_mode & (kDbgFp32PassX | kDbgTiledColumns | kDbgTiledRows))) return 0;
   if (!row_pass_wave_supported(dtype, sx, sy, sz) || !column_pass_wave_supported(make_geom_y(sx, sy, sz))) return 0;
   int64_t slab = kCodeSlabVoxels / (sx * sy);
   if (slab >= sz) return sz;
@@ -190,13 +189,12 @@ static Plan make_plan(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, v
   if (ndim >= 2 && !(flags & EDT_FLAG_FORCE_GENERIC) && !env_force_generic()) {
     // (ids in the fp32 kernel's geometry: 16-column tiles for axes of more than 512 rows)
     // (pass Y runs over all sz slices at once whenever the index form is not taken at run time: sized for that)
-    const int64_t ty = ceil_div(sx, 16) * (ceil_div(sz, 8) * 8);
-    const int64_t tz = ceil_div(sx, 16) * (ceil_div(sy, 8) * 8);
     p.q16_map_words = (int)ceil_div(sz, 32);
-    p.q16_counts = c.take<uint32_t>(kQ16Slots + (size_t)(ceil_div(sx, 32) * p.q16_map_words));  // (zeroed together)
-    p.q16_map = p.q16_counts ? p.q16_counts + kQ16Slots : nullptr;
-    p.q16_id_capacity = std::max(ty, tz);
-    p.q16_ids = c.take<uint32_t>((size_t)p.q16_id_capacity);
+    p.q16.slots = kQ16Slots;
+    p.q16.counts = c.take<uint32_t>(kQ16Slots + (size_t)(ceil_div(sx, 32) * p.q16_map_words));  // (zeroed together)
+    p.q16_map = p.q16.counts ? p.q16.counts + kQ16Slots : nullptr;
+    p.q16.capacity = std::max(HandOver::ids_of(sx, sz), HandOver::ids_of(sx, sy));
+    p.q16.ids = c.take<uint32_t>((size_t)p.q16.capacity);
   }
   if (ndim == 1) (void)c.take<unsigned char>(line_workspace_bytes(sx));  // block scan + table of the 1-D pipeline
   // rows too long for the row kernels (more than 4096 voxels; more than 2048 where the wave kernel does not apply): pass 1
@@ -208,31 +206,13 @@ static Plan make_plan(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, v
   return p;
 }
 
-// In-place LDS-tiled column pass: the wave-autonomous kernel where the axis fits its register
-// budget, the workgroup-phased kernel for longer axes.  (debug bit 64 forces the latter.)
-bool column_inplace_supported(const AxisGeom &g) {
-  return column_pass_wave_supported(g) || column_pass_tiled_supported(g);
-}
-int launch_column_inplace(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g,
-                          float w, int bb, int epi, hipStream_t stream, const TileList &list) {
-  // (a list -- the tiles the 16-bit integer kernel refused -- only exists for axes of the wave kernel)
-  if (list.count != nullptr) return launch_column_pass_wave(F, nz, rs, g, w, bb, epi, stream, nullptr, ColumnOut(), list);
-  // axes of at most 32 rows with many columns: a thread per column (edt_short.hip); the LDS-tiled kernels would
-  // launch a single-wave workgroup per 32 columns.  (debug bit 0x1000000 keeps them on the wave kernel.)
-  if (column_pass_short_supported(g) && g.sx * g.nouter >= 4096 && !(g_debug_mode & (64 | 0x1000000)))
-    return launch_column_pass_short(F, nz, rs, g, w, bb, epi, stream);
-  if (column_pass_wave_supported(g) && !(g_debug_mode & 64))
-    return launch_column_pass_wave(F, nz, rs, g, w, bb, epi, stream);
-  return launch_column_pass_tiled(F, nz, rs, g, w, bb, epi, stream);
-}
-
 // Pass 1 with the bit planes of the column passes as a by-product: the register-resident wave kernel for rows of up
 // to 4096 voxels (one, two or four waves per row), the LDS-staged workgroup kernel (rows of up to 2048 voxels) where
 // that one does not apply.  (debug bit 32 forces the latter.)
 int launch_row_bits(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
                            uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
                            int to_finite, hipStream_t stream) {
-  if (row_pass_wave_supported(dtype, sx, sy, sz) && !(g_debug_mode & 32))
+  if (row_pass_wave_supported(dtype, sx, sy, sz) && !(g_debug_mode & kDbgTiledRows))
     return launch_row_pass_wave(dtype, labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream);
   return launch_row_pass_tiled(dtype, labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream);
 }
@@ -331,7 +311,7 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
     set_error("EDT_FLAG_SIGNED: shape not served by the one-transform form (edt_hip_signed_supported)");
     return EDT_ERR_UNSUPPORTED;
   }
-  const int last_epi = (bb ? 0 : kEpiToInf) | (want_sqrt ? kEpiSqrt : 0) | kEpiStream;
+  const int last_epi = last_pass_epi(bb, want_sqrt);
   // a stack of 2-D images is a volume without a z pass
   if ((flags & EDT_FLAG_BATCH_2D) && ndim != 3) { set_error("EDT_FLAG_BATCH_2D needs ndim = 3 (sz = image count)"); return EDT_ERR_BAD_ARG; }
   const bool zpass = ndim == 3 && !(flags & EDT_FLAG_BATCH_2D);
@@ -353,63 +333,19 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
   }
 
   // The 16-bit integer form of the column passes (edt_colq16.hip): voxel sizes that share a quantum.  Every column pass
-  // is then two launches: the integer kernel over all tiles, and the fp32 kernel over the list of tiles it refused.
-  float q16_q = 1.0f;
-  uint32_t q16_a[3] = {1u, 1u, 1u};
-  bool q16 = false;
-  int q16_slot = 0;
-  bool q16_counts_zeroed = false;
-  if (ndim >= 2 && p.q16_counts != nullptr) {
+  // is then two launches: the integer kernel over all tiles, and the fp32 kernel over the list of tiles it refused
+  // (run_column_pass, edt_colpass.hip).
+  Quantum Q;
+  if (ndim >= 2 && p.q16.counts != nullptr) {
     const float ws3[3] = {wx, wy, wz};
-    q16 = q16_quantum(ws3, (ndim == 3 && !(flags & EDT_FLAG_BATCH_2D)) ? 3 : 2, &q16_q, q16_a);
+    Q = q16_quantum(ws3, zpass ? 3 : 2);
   }
-  constexpr int kQ16Off = 16 | 64 | 0x2000 | 0x4000 | 0x8000 | 0x10000;
-  // Where the integer kernel provably refuses no tile (index form, bounded values: q16_no_refusals, edt_colq16.hip) and
-  // everything the pass reads was written by pass X or by an integer pass that could not refuse either, the fp32 launch over
-  // the hand-over list has nothing to do and is not made -- nor is the list's counter zeroed.
-  auto q16_cannot_refuse = [&](int axis, const AxisGeom &g) {
-    return q16 && q16_no_refusals(q16_q, q16_a, axis, sx, sy, g.n, bb);
-  };
-  // F in place (codes == nullptr) or from the 16-bit indices of pass X; returns the list for the fp32 launch that follows
-  // (launched: the integer kernel ran; sure: the caller vouches for what the pass reads -- see above)
-  // will q16_pass launch the integer kernel for this axis?  (the shape and mode part of its test; buffers: column_pass_q16_aligned)
-  auto q16_applies = [&](const AxisGeom &g) {
-    return q16 && column_pass_q16_supported(g) && column_pass_wave_supported(g) && !(g_debug_mode & kQ16Off) &&
-           ceil_div(g.sx, 16) * (ceil_div(g.nouter, 8) * 8) <= p.q16_id_capacity;
-  };
-  // map_words_off: the slab's first word in every x-tile's row of the plane's map (pass Y of the slabs after the first)
-  auto q16_pass = [&](float *F, const uint16_t *codes, const uint32_t *rs, const AxisGeom &g, int axis, int epi,
-                      TileList &list, uint16_t *plane, bool sure, bool &launched, int64_t map_words_off = 0,
-                      const uint32_t *signbits = nullptr) -> int {
-    list = TileList();
-    launched = false;
-    // (the bits that force one form of the fp32 kernel on every tile -- the test tiers' way to cover them -- keep the call there)
-    if (!q16 || q16_slot >= kQ16Slots || !column_pass_q16_supported(g) || !column_pass_wave_supported(g) ||
-        !column_pass_q16_aligned(F, codes, plane) || (g_debug_mode & kQ16Off))
-      return EDT_OK;
-    // (the id array was sized for these tile counts: make_plan)
-    if (ceil_div(g.sx, 16) * (ceil_div(g.nouter, 8) * 8) > p.q16_id_capacity) return EDT_OK;
-    sure = sure && q16_cannot_refuse(axis, g);
-    if (!sure && !q16_counts_zeroed) {
-      EDT_HIP_TRY(hipMemsetAsync(p.q16_counts, 0, kQ16Slots * sizeof(uint32_t), stream));
-      q16_counts_zeroed = true;
-    }
-    uint32_t *count = p.q16_counts + q16_slot++;
-    // (the index buffer's own pitch: the outer stride of codes -- and of the plane written over them -- in pass Y, the row stride
-    // of the plane pass Z reads)
-    const bool reads_plane = codes == nullptr && plane != nullptr;
-    const int r = launch_column_pass_q16(F, codes, rs, g, q16_q, q16_a[axis], q16_a[0], bb, epi, count, p.q16_ids, stream,
-                                         nullptr, plane, p.q16_map + map_words_off, p.q16_map_words, nullptr,
-                                         reads_plane ? p.code_pitch : 0, reads_plane ? sx : 0,
-                                         // (pass Y into the plane: may a tile of nothing but +inf stay there for pass Z?)
-                                         (axis == 1 && plane != nullptr && codes != nullptr && q16_value_limit(q16_q, q16_a[2], sz, bb) != 0u) ? 1 : 0,
-                                         signbits, (codes != nullptr && axis == 1) ? p.code_pitch : 0);
-    if (r != EDT_OK) return r;
-    launched = true;
-    list.count = count;
-    list.ids = p.q16_ids;
-    list.none = sure;
-    return EDT_OK;
+  // a column pass of this call over the field at F, in place
+  auto column = [&](float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w, int epi) {
+    ColumnPass cp = column_pass(F, nz, rs, g, w, bb, epi, stream);
+    cp.map = p.q16_map;
+    cp.map_words = p.q16_map_words;
+    return cp;
   };
 
   if (ndim == 1) {
@@ -436,24 +372,23 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
   // volume (one slab), the tiles of pass Y that qualify write their results over their indices -- 2 bytes per voxel out
   // of pass Y and into pass Z instead of 4 -- and pass Z reads every row from wherever pass Y left it.  (debug bit
   // 0x10000000: fp32 between the passes.)
-  bool plane16 = q16 && index_form && zpass && p.codes_whole && !(g_debug_mode & (kQ16Off | 0x10000000)) &&
-                       column_pass_q16_supported(p.gy) && column_pass_q16_supported(p.gz) &&
-                       column_pass_wave_supported(p.gy) && column_pass_wave_supported(p.gz);
-  bool y_sure = true;  // every tile of pass Y was served by the integer kernel, provably (q16_cannot_refuse)
+  bool plane16 = index_form && zpass && p.codes_whole && !(g_debug_mode & kDbgFp32Plane) &&
+                 column_pass_q16_applies(Q, p.gy, p.q16) && column_pass_q16_applies(Q, p.gz, p.q16);
+  bool y_sure = true;  // every tile of pass Y was served by the integer kernel, provably (q16_no_refusals)
   // The signed transform's sign as the EPILOGUE of pass Z (round 6): where both column passes provably run on the integer kernel
   // alone -- it never reads the foreground plane -- pass X keeps the TRUE label != 0 bits there (zero_label = 2), the transposer
   // carries them to the z axis, and the last pass negates the voxels whose bit is clear (kEpiSign): no pass of its own over
   // labels and field (1.2 GB at 512^3).  Anywhere else: all-ones planes and k_negate_background.  (debug bit 0x400: never.)
-  // q16_only: both column passes of the call provably run on the integer kernel alone (what q16_pass will decide, decided here
-  // for the whole call; a pass that left that kernel after all is an internal error below)
-  const bool q16_only = zpass && index_form && tiled_z && q16_applies(p.gy) && q16_applies(p.gz) && q16_cannot_refuse(1, p.gy) &&
-                        q16_cannot_refuse(2, p.gz) && column_pass_q16_aligned(cur, p.codes, p.codes) &&
-                        ceil_div(sz, p.xy_slab > 0 ? p.xy_slab : sz) + 1 <= kQ16Slots;
-  const bool fuse_sign = signed_tf && q16_only && !(g_debug_mode & 0x400);
+  // q16_only: both column passes of the call provably run on the integer kernel alone (what run_column_pass will decide, decided
+  // here for the whole call; a pass that left that kernel after all is an internal error below)
+  const bool q16_only = zpass && index_form && tiled_z && column_pass_q16_applies(Q, p.gy, p.q16) && column_pass_q16_applies(Q, p.gz, p.q16) &&
+                        q16_no_refusals(Q, 1, sx, sy, sy, bb) && q16_no_refusals(Q, 2, sx, sy, sz, bb) &&
+                        column_pass_q16_aligned(cur, p.codes, p.codes) && ceil_div(sz, p.xy_slab > 0 ? p.xy_slab : sz) + 1 <= kQ16Slots;
+  const bool fuse_sign = signed_tf && q16_only && !(g_debug_mode & kDbgKeepPlanes);
   const int zero_label = fuse_sign ? 2 : signed_tf;
   // ... and then nobody reads a foreground plane (the integer kernel knows background as N = 0): pass X does not write one, the
   // transposer carries the run starts alone -- 48 MiB less per 512^3 step (debug bit 0x400 keeps the planes)
-  const bool skip_nz = q16_only && !signed_tf && !binary_yz && !(g_debug_mode & 0x400);
+  const bool skip_nz = q16_only && !signed_tf && !binary_yz && !(g_debug_mode & kDbgKeepPlanes);
   uint32_t *const nzy = skip_nz ? nullptr : p.nz_y, *const nzz = skip_nz ? nullptr : p.nz_z;
   if (index_form) {
     const int64_t sxy = sx * sy, wpl = p.gy.sx * p.gy.nbands;  // voxels / bit words per slice
@@ -481,20 +416,22 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
       }
       {
         ScopedPass t(one ? "y_pass" : nullptr, stream);
-        AxisGeom g = p.gy;
-        g.nouter = zc;
-        TileList list;
-        bool launched = false;
-        rc = q16_pass(cur + z0 * sxy, slab_codes, p.rs_y + z0 * wpl, g, 1, zpass ? 0 : last_epi, list, plane16 ? slab_codes : nullptr,
-                      true, launched, (p.codes_whole && !one) ? z0 / 32 : 0);
+        ColumnPass cp = column(cur + z0 * sxy, p.nz_y + z0 * wpl, p.rs_y + z0 * wpl, p.gy, wy, zpass ? 0 : last_epi);
+        cp.g.nouter = zc;
+        cp.codes = slab_codes;
+        cp.codes_outer = p.code_pitch;  // (the index buffer's own pitch: the outer stride of codes -- and of the plane written over them)
+        cp.wx = wx;
+        cp.plane = plane16 ? slab_codes : nullptr;
+        // (the slab's first word in every x-tile's row of the plane's map: pass Y of the slabs after the first)
+        if (p.codes_whole && !one) cp.map += z0 / 32;
+        // (pass Y into the plane: may a tile of nothing but +inf stay there for pass Z?)
+        cp.plane_inf_ok = (plane16 && q16_value_limit(Q.q, Q.a[2], sz, bb) != 0u) ? 1 : 0;
+        TileList served;
+        rc = run_column_pass(cp, Q, 1, p.q16, Fp32Leg::wave, true, &served);
         if (rc != EDT_OK) return rc;
-        if (!launched) plane16 = false;  // (nothing wrote the plane or said where the rows are: pass Z reads fp32 values)
-        y_sure = y_sure && list.none;
-        if (q16_only && (!launched || !list.none)) { set_error("internal: pass Y left the integer kernel"); return EDT_ERR_HIP; }
-        if (!list.none)
-          rc = launch_column_pass_wave_codes(cur + z0 * sxy, slab_codes, p.nz_y + z0 * wpl, p.rs_y + z0 * wpl, g, wy, bb,
-                                             zpass ? 0 : last_epi, wx, bb ? 0 : 1, stream, nullptr, list, ColumnOut(), p.code_pitch);
-        if (rc != EDT_OK) return rc;
+        if (served.count == nullptr) plane16 = false;  // (nothing wrote the plane or said where the rows are: pass Z reads fp32 values)
+        y_sure = y_sure && served.none;
+        if (q16_only && !served.none) { set_error("internal: pass Y left the integer kernel"); return EDT_ERR_HIP; }
       }
     }
   } else if (tiled_x) {
@@ -532,13 +469,9 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
     ScopedPass t("y_pass", stream);
     const int epi = zpass ? 0 : last_epi;
     if (tiled_y) {
-      TileList list;
-      bool launched = false;
       // (fp32 values of pass X: (k * wx)^2 need not be on the quantum grid for large k -- the list stays)
-      rc = q16_pass(cur, nullptr, p.rs_y, p.gy, 1, epi, list, nullptr, false, launched);
-      if (rc != EDT_OK) return rc;
+      rc = run_column_pass(column(cur, p.nz_y, p.rs_y, p.gy, wy, epi), Q, 1, p.q16, Fp32Leg::inplace);
       y_sure = false;
-      rc = launch_column_inplace(cur, p.nz_y, p.rs_y, p.gy, wy, bb, epi, stream, list);
     } else {
       rc = launch_column_pass_serial(cur, other, p.nz_y, p.rs_y, p.stack, p.gy, wy, bb, epi, stream);
       std::swap(cur, other);
@@ -558,13 +491,16 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
   if (zpass) {
     ScopedPass t("z_pass", stream);
     if (tiled_z) {
-      TileList list;
-      bool launched = false;
-      rc = q16_pass(cur, nullptr, p.rs_z, p.gz, 2, last_epi | (fuse_sign ? kEpiSign : 0), list, plane16 ? p.codes : nullptr,
-                    index_form && y_sure, launched, 0, fuse_sign ? p.nz_z : nullptr);
-      if (rc != EDT_OK) return rc;
-      if (q16_only && (!launched || !list.none)) { set_error("internal: pass Z left the integer kernel"); return EDT_ERR_HIP; }
-      if (!list.none) rc = launch_column_inplace(cur, p.nz_z, p.rs_z, p.gz, wz, bb, last_epi, stream, list);
+      ColumnPass cp = column(cur, p.nz_z, p.rs_z, p.gz, wz, last_epi | (fuse_sign ? kEpiSign : 0));
+      if (plane16) {  // (the index buffer's own pitch: the row stride of the plane pass Z reads)
+        cp.plane = p.codes;
+        cp.plane_stride = p.code_pitch;
+        cp.plane_outer = sx;
+      }
+      cp.signbits = fuse_sign ? p.nz_z : nullptr;
+      TileList served;
+      rc = run_column_pass(cp, Q, 2, p.q16, Fp32Leg::inplace, index_form && y_sure, &served);
+      if (rc == EDT_OK && q16_only && !served.none) { set_error("internal: pass Z left the integer kernel"); return EDT_ERR_HIP; }
     } else {
       rc = launch_column_pass_serial(cur, other, p.nz_z, p.rs_z, p.stack, p.gz, wz, bb, last_epi,
                                      stream);
@@ -585,7 +521,7 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
 // and in-place column passes (their kernels never look at label values: run-start bits and field values only).
 bool signed_transform_supported(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
   if (ndim < 2 || ndim > 3 || dtype_size(dtype) == 0 || sx < 1 || sy < 1 || sz < 1) return false;
-  if ((flags & (EDT_FLAG_FORCE_GENERIC | EDT_FLAG_BINARY_YZ)) || env_force_generic() || (g_debug_mode & 32)) return false;
+  if ((flags & (EDT_FLAG_FORCE_GENERIC | EDT_FLAG_BINARY_YZ)) || env_force_generic() || (g_debug_mode & kDbgTiledRows)) return false;
   if (!row_pass_wave_supported(dtype, sx, sy, sz)) return false;
   if (!column_inplace_supported(make_geom_y(sx, sy, sz))) return false;
   const bool zpass = ndim == 3 && !(flags & EDT_FLAG_BATCH_2D);
@@ -650,11 +586,10 @@ int edt_hip_q16_no_refusals(int64_t sx, int64_t sy, int64_t sz, float wx, float 
   if (pass_z) *pass_z = 0;
   if (ndim < 2 || ndim > 3 || sx < 1 || sy < 1 || (ndim == 3 && sz < 1)) return 0;
   const float w3[3] = {wx, wy, wz};
-  float q = 1.0f;
-  uint32_t a[3] = {1u, 1u, 1u};
-  if (!q16_quantum(w3, ndim, &q, a)) return 0;
-  const bool y = q16_no_refusals(q, a, 1, sx, sy, sy, black_border);
-  const bool z = ndim == 3 && y && q16_no_refusals(q, a, 2, sx, sy, sz, black_border);
+  const Quantum Q = q16_quantum(w3, ndim);
+  if (!Q.ok) return 0;
+  const bool y = q16_no_refusals(Q, 1, sx, sy, sy, black_border);
+  const bool z = ndim == 3 && y && q16_no_refusals(Q, 2, sx, sy, sz, black_border);
   if (pass_y) *pass_y = y ? 1 : 0;
   if (pass_z) *pass_z = z ? 1 : 0;
   return 1;
@@ -705,7 +640,7 @@ int edt_hip_subtract_device(const float *d_a, const float *d_b, float *d_out, in
 // the wave column kernel covers the doubled axes, else the up-sampled form: workspace = [2x uint8 volume |
 // its fp32 transform | the ordinary workspace of the 2x volume].  Debug bit 0x20000 forces the latter.
 static bool vg_use_native(int ndim, int64_t sx, int64_t sy, int64_t sz) {
-  return !(g_debug_mode & 0x20000) && vg_native_supported(ndim, sx, sy, sz);
+  return !(g_debug_mode & kDbgVgUpsampled) && vg_native_supported(ndim, sx, sy, sz);
 }
 
 size_t edt_hip_voxel_graph_workspace_bytes(int ndim, int64_t sx, int64_t sy, int64_t sz) {

@@ -31,10 +31,6 @@ struct Carver {
 
 AxisGeom make_geom_y(int64_t sx, int64_t sy, int64_t sz);
 AxisGeom make_geom_z(int64_t sx, int64_t sy, int64_t sz);
-// In-place LDS-tiled column pass where one applies (edt_api.hip)
-bool column_inplace_supported(const AxisGeom &g);
-int launch_column_inplace(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w, int bb, int epi,
-                          hipStream_t stream, const TileList &list = TileList());
 int launch_row_bits(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y, uint32_t *zs_y, int64_t sx,
                     int64_t sy, int64_t sz, float w, int bb, int to_finite, hipStream_t stream);
 bool env_force_generic();  // EDT_HIP_FORCE_GENERIC=1: every call takes the fallback kernels (test hook)
@@ -67,7 +63,7 @@ struct ScopedPass {
   bool named;
   ScopedPass(const char *name, hipStream_t s) : stream(s), named(name != nullptr) {  // (no name: not a pass of its own)
     if (!named) return;
-    if (debug_mode() & 0x1000) fprintf(stderr, "[edt_hip] pass start: %s\n", name);
+    if (debug_mode() & kDbgNamePasses) fprintf(stderr, "[edt_hip] pass start: %s\n", name);
     if (!g_log.enabled.load(std::memory_order_relaxed)) return;
     std::lock_guard<std::mutex> lock(g_log_mutex);  // (only while profiling is switched on)
     hipEvent_t e = log_event();
@@ -78,7 +74,7 @@ struct ScopedPass {
   }
   ~ScopedPass() {
     if (!named) return;
-    if (debug_mode() & 0x1000) {  // diagnostics: name every pass as it completes
+    if (debug_mode() & kDbgNamePasses) {  // diagnostics: name every pass as it completes
       const hipError_t e = hipStreamSynchronize(stream);
       fprintf(stderr, "[edt_hip] pass done: %s\n", hipGetErrorString(e));
     }

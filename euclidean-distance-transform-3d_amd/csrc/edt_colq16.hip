@@ -905,12 +905,12 @@ bool column_pass_q16_supported(const AxisGeom &g) {
   // whole 16-byte granules per row piece; axes the LDS image fits twice per CU (two workgroups per CU keep the fill of
   // one under the windows of the other); shorter axes than 4 bands leave most of the workgroup without a band
   return g.sx % 4 == 0 && g.stride % 4 == 0 && g.outer_stride % 4 == 0 && g.nbands >= 4 && g.nbands <= 32 &&
-         !(debug_mode() & 0x8000000);
+         !(debug_mode() & kDbgNoQ16);
 }
 
 template <bool BB, int IN, bool O16, bool SC, int T, int S = 1>
-static int launch_q16_kt(float *F, const uint32_t *rs, const AxisGeom &g, const Q16Args &qa, int epi, hipStream_t stream,
-                         const BandScatter *scatter) {
+static int launch_q16_kt(const ColumnPass &cp, const Q16Args &qa) {
+  const AxisGeom &g = cp.g;
   const int NB = (int)g.nbands;
   // (EDT_Q16_EXTRA_LDS: experiments -- bytes of LDS asked for on top, i.e. fewer workgroups per CU)
   static const size_t extra_lds = [] { const char *e = getenv("EDT_Q16_EXTRA_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
@@ -918,69 +918,67 @@ static int launch_q16_kt(float *F, const uint32_t *rs, const AxisGeom &g, const 
   const int64_t tiles_x = ceil_div(g.sx, 32);
   int64_t tiles = tiles_x * g.nouter;
   if (tiles <= 0) return EDT_OK;
-  if (!(debug_mode() & 0x800)) tiles = tiles_x * (ceil_div(g.nouter, 8) * 8);
+  if (!(debug_mode() & kDbgPlainTileOrder)) tiles = tiles_x * (ceil_div(g.nouter, 8) * 8);
   if (tiles > 0x7FFFFFFF) { set_error("too many tiles"); return EDT_ERR_UNSUPPORTED; }
   static std::atomic<uint64_t> attr_done{0};
   EDT_HIP_TRY(EDT_LDS_ATTR_ONCE(attr_done, reinterpret_cast<const void *>(&k_column_pass_q16<BB, IN, O16, SC, T, S>)));
-  hipLaunchKernelGGL((k_column_pass_q16<BB, IN, O16, SC, T, S>), dim3((unsigned)tiles), dim3(T), lds, stream, F, rs, g,
-                     (int)tiles_x, epi, debug_mode(), qa, scatter);
+  hipLaunchKernelGGL((k_column_pass_q16<BB, IN, O16, SC, T, S>), dim3((unsigned)tiles), dim3(T), lds, cp.stream, cp.F, cp.rs,
+                     g, (int)tiles_x, cp.epi, debug_mode(), qa, cp.scatter);
   EDT_HIP_TRY(hipGetLastError());
   return EDT_OK;
 }
 
 template <bool BB, int IN, bool O16, bool SC>
-static int launch_q16_k(float *F, const uint32_t *rs, const AxisGeom &g, const Q16Args &qa, int epi, hipStream_t stream,
-                        const BandScatter *scatter) {
-  if (g.nbands > 16) return launch_q16_kt<BB, IN, O16, SC, 512>(F, rs, g, qa, epi, stream, scatter);
-  return launch_q16_kt<BB, IN, O16, SC, 256>(F, rs, g, qa, epi, stream, scatter);
+static int launch_q16_k(const ColumnPass &cp, const Q16Args &qa) {
+  if (cp.g.nbands > 16) return launch_q16_kt<BB, IN, O16, SC, 512>(cp, qa);
+  return launch_q16_kt<BB, IN, O16, SC, 256>(cp, qa);
 }
 
 template <bool BB>
-static int launch_q16_b(float *F, const uint32_t *rs, const AxisGeom &g, const Q16Args &qa, int in, bool o16, int epi,
-                        hipStream_t stream, const BandScatter *scatter, int out_stride) {
+static int launch_q16_b(const ColumnPass &cp, const Q16Args &qa, int in, bool o16, int out_stride) {
+  const AxisGeom &g = cp.g;
+  const BandScatter *scatter = cp.scatter;
   if (out_stride == 2) {
     if (scatter != nullptr || o16 || in == kQ16InMixed || (in == kQ16InCodes && qa.compact == nullptr)) {
       set_error("internal: output stride 2 takes fp32 values (in place or compact) or indices (compact)");
       return EDT_ERR_BAD_ARG;
     }
     if (in == kQ16InCodes) {
-      if (g.nbands > 16) return launch_q16_kt<BB, kQ16InCodes, false, false, 512, 2>(F, rs, g, qa, epi, stream, nullptr);
-      return launch_q16_kt<BB, kQ16InCodes, false, false, 256, 2>(F, rs, g, qa, epi, stream, nullptr);
+      if (g.nbands > 16) return launch_q16_kt<BB, kQ16InCodes, false, false, 512, 2>(cp, qa);
+      return launch_q16_kt<BB, kQ16InCodes, false, false, 256, 2>(cp, qa);
     }
-    if (g.nbands > 16) return launch_q16_kt<BB, kQ16InF32, false, false, 512, 2>(F, rs, g, qa, epi, stream, nullptr);
-    return launch_q16_kt<BB, kQ16InF32, false, false, 256, 2>(F, rs, g, qa, epi, stream, nullptr);
+    if (g.nbands > 16) return launch_q16_kt<BB, kQ16InF32, false, false, 512, 2>(cp, qa);
+    return launch_q16_kt<BB, kQ16InF32, false, false, 256, 2>(cp, qa);
   }
   if (scatter != nullptr) {
     if (in == kQ16InMixed || (o16 && in != kQ16InCodes)) { set_error("internal: slab records take indices or fp32 rows"); return EDT_ERR_BAD_ARG; }
-    if (o16) return launch_q16_k<BB, kQ16InCodes, true, true>(F, rs, g, qa, epi, stream, scatter);  // 16-bit records
-    return in == kQ16InCodes ? launch_q16_k<BB, kQ16InCodes, false, true>(F, rs, g, qa, epi, stream, scatter)
-                             : launch_q16_k<BB, kQ16InF32, false, true>(F, rs, g, qa, epi, stream, scatter);
+    if (o16) return launch_q16_k<BB, kQ16InCodes, true, true>(cp, qa);  // 16-bit records
+    return in == kQ16InCodes ? launch_q16_k<BB, kQ16InCodes, false, true>(cp, qa)
+                             : launch_q16_k<BB, kQ16InF32, false, true>(cp, qa);
   }
   if (in == kQ16InCodes)
-    return o16 ? launch_q16_k<BB, kQ16InCodes, true, false>(F, rs, g, qa, epi, stream, nullptr)
-               : launch_q16_k<BB, kQ16InCodes, false, false>(F, rs, g, qa, epi, stream, nullptr);
+    return o16 ? launch_q16_k<BB, kQ16InCodes, true, false>(cp, qa)
+               : launch_q16_k<BB, kQ16InCodes, false, false>(cp, qa);
   if (o16) { set_error("internal: 16-bit plane without the index form"); return EDT_ERR_BAD_ARG; }
-  return in == kQ16InMixed ? launch_q16_k<BB, kQ16InMixed, false, false>(F, rs, g, qa, epi, stream, nullptr)
-                           : launch_q16_k<BB, kQ16InF32, false, false>(F, rs, g, qa, epi, stream, nullptr);
+  return in == kQ16InMixed ? launch_q16_k<BB, kQ16InMixed, false, false>(cp, qa)
+                           : launch_q16_k<BB, kQ16InF32, false, false>(cp, qa);
 }
 
-// a: c_d = a * d^2 quanta of this pass; ain: quanta per squared index of pass X (codes != nullptr).
-// plane / map != nullptr: with codes -- the results go to the 16-bit plane (= codes, in place) and the tile's bit is set in
-// map; without -- the rows are taken from the plane wherever map says so (the pass after such a pass).
-// Slab records of 16-bit values (edt_shard_api.hip): with codes, a scatter table AND a plane (any non-null value) the results go to
-// the table's destinations as 16-bit rows, refused tiles are only counted (ids == nullptr); without codes, a map of ones
-// and plane_stride > 0 every row is read from the plane at its own strides (16-bit elements) and F is only written.
-int launch_column_pass_q16(float *F, const uint16_t *codes, const uint32_t *rs, const AxisGeom &g, float q, uint32_t a,
-                           uint32_t ain, int bb, int epi, uint32_t *count, uint32_t *ids, hipStream_t stream,
-                           const BandScatter *scatter, uint16_t *plane, uint32_t *map, int map_words, const ColumnOut *out,
-                           int64_t plane_stride, int64_t plane_outer, int plane_inf_ok, const uint32_t *signbits,
-                           int64_t codes_outer) {
+// (what a pass is: edt_kernels.h, ColumnPass)  a: c_d = a * d^2 quanta of this pass; ain: quanta per squared index of pass X.
+int launch_column_pass_q16(const ColumnPass &cp, const Quantum &Q, int axis, HandOver h) {
+  const AxisGeom &g = cp.g;
+  const uint16_t *codes = cp.codes;
+  uint16_t *plane = cp.plane;
+  const ColumnOut &out = cp.out;
+  const float q = Q.q;
+  const uint32_t a = Q.a[axis], ain = Q.a[0];
+  const int bb = cp.bb;
   Q16Args qa;
-  qa.cd_outer = codes_outer > 0 ? codes_outer : g.outer_stride;
-  qa.plane_inf_ok = plane_inf_ok ? 1u : 0u;
-  qa.signbits = signbits;
-  if ((epi & kEpiSign) && (signbits == nullptr || scatter != nullptr || (out && (out->stride == 2 || out->compact != nullptr)) ||
-                           (codes != nullptr && plane != nullptr))) {
+  qa.cd_outer = cp.codes_outer > 0 ? cp.codes_outer : g.outer_stride;
+  qa.plane_inf_ok = cp.plane_inf_ok ? 1u : 0u;
+  qa.signbits = cp.signbits;
+  if ((cp.epi & kEpiSign) && (cp.signbits == nullptr || cp.scatter != nullptr || out.stride == 2 || out.compact != nullptr ||
+                              (codes != nullptr && plane != nullptr))) {
     set_error("internal: the sign epilogue belongs to a last pass with fp32 results in place");
     return EDT_ERR_BAD_ARG;
   }
@@ -997,7 +995,7 @@ int launch_column_pass_q16(float *F, const uint16_t *codes, const uint32_t *rs, 
   {
     // the wide form's range (nlimw == nlim: there is none)
     edt_q16::WideRange wr = {0u, 0u, false};
-    if (!(debug_mode() & 0x20000000)) wr = edt_q16::q16_wide_range(a, q, g.n, bb != 0, qa.nlim);
+    if (!(debug_mode() & kDbgNoWide)) wr = edt_q16::q16_wide_range(a, q, g.n, bb != 0, qa.nlim);
     qa.dmaxw = wr.nlim ? wr.dmax : qa.dmax;
     qa.nlimw = wr.nlim ? wr.nlim : qa.nlim;
     qa.inf_ok = wr.inf ? 1u : 0u;
@@ -1007,26 +1005,25 @@ int launch_column_pass_q16(float *F, const uint16_t *codes, const uint32_t *rs, 
     const float fw = (float)qa.nlimw * q;  // exact: nlimw * odd(q) < 2^24 (nlim: < 2^16 * 255)
     memcpy(&qa.fwmax_bits, &fw, sizeof(fw));
   }
-  qa.count = count;
-  qa.ids = ids;
+  qa.count = h.counts + h.slot;
+  qa.ids = h.ids;
   qa.list_cols = g.nbands > 16 ? 16 : 32;  // (edt_colwave_lane.h: TileGeom -- 16-column tiles for the 1- and 2-column waves)
   qa.plane = plane;
-  qa.map = map;
-  qa.map_words = map_words;
-  qa.pst = plane_stride > 0 ? plane_stride : g.stride;
-  qa.p_outer = plane_stride > 0 ? plane_outer : g.outer_stride;
-  qa.compact = out ? out->compact : nullptr;
-  qa.c_outer = out ? out->outer : 0;
-  qa.c_row2 = out ? out->row2 : 0;
-  const int ostride = (out && (out->stride == 2 || out->compact != nullptr)) ? 2 : 1;
+  qa.map = cp.map;
+  qa.map_words = cp.map_words;
+  qa.pst = cp.plane_stride > 0 ? cp.plane_stride : g.stride;
+  qa.p_outer = cp.plane_stride > 0 ? cp.plane_outer : g.outer_stride;
+  qa.compact = out.compact;
+  qa.c_outer = out.outer;
+  qa.c_row2 = out.row2;
+  const int ostride = (out.stride == 2 || out.compact != nullptr) ? 2 : 1;
   if (qa.compact != nullptr && ((reinterpret_cast<uintptr_t>(qa.compact) % 8) != 0 || (qa.c_outer % 2) != 0 || (qa.c_row2 % 2) != 0)) {
     set_error("internal: compact destination of the integer kernel must take 8-byte stores");
     return EDT_ERR_BAD_ARG;
   }
   const int in = codes ? kQ16InCodes : (plane ? kQ16InMixed : kQ16InF32);
   const bool o16 = codes != nullptr && plane != nullptr;
-  return bb ? launch_q16_b<true>(F, rs, g, qa, in, o16, epi, stream, scatter, ostride)
-            : launch_q16_b<false>(F, rs, g, qa, in, o16, epi, stream, scatter, ostride);
+  return bb ? launch_q16_b<true>(cp, qa, in, o16, ostride) : launch_q16_b<false>(cp, qa, in, o16, ostride);
 }
 
 // the largest value (in quanta) a tile of a pass with c_d = a * d^2 over columns of n rows may hold without being handed to the
@@ -1034,7 +1031,7 @@ int launch_column_pass_q16(float *F, const uint16_t *codes, const uint32_t *rs, 
 uint32_t q16_value_limit(float q, uint32_t a, int64_t n, int bb) {
   const uint32_t d16 = edt_q16::q16_dmax(a), n16 = a * d16 * d16;
   edt_q16::WideRange wr = {0u, 0u, false};
-  if (!(debug_mode() & 0x20000000)) wr = edt_q16::q16_wide_range(a, q, n, bb != 0, n16);
+  if (!(debug_mode() & kDbgNoWide)) wr = edt_q16::q16_wide_range(a, q, n, bb != 0, n16);
   if (!bb) return wr.inf ? wr.nlim : 0u;
   return wr.nlim ? wr.nlim : n16;
 }
@@ -1048,8 +1045,9 @@ uint32_t q16_value_limit(float q, uint32_t a, int64_t n, int bb) {
 // the pass reads was written by pass X or by an integer pass that could not refuse either (the caller's part), the fp32
 // launch over the hand-over list has nothing to do.  (debug bit 0x20000000: never proven.)
 // tests/test_q16_logic.py plays passes Y and Z of whole volumes through the lane logic and holds this proof against them.
-bool q16_no_refusals(float q, const uint32_t *a, int axis, int64_t sx, int64_t sy, int64_t n, int bb) {
-  if (debug_mode() & 0x20000000) return false;
+bool q16_no_refusals(const Quantum &Q, int axis, int64_t sx, int64_t sy, int64_t n, int bb) {
+  const uint32_t *a = Q.a;
+  if (!Q.ok || (debug_mode() & kDbgNoWide)) return false;
   if (axis != 1 && axis != 2) return false;
   // (the proof stands on its own: extents an index of pass X cannot describe -- 0xFFFF is "no boundary" -- prove nothing, and
   // the products below stay far from 2^64: kmax, sy < 2^16, a <= 16384)
@@ -1057,16 +1055,18 @@ bool q16_no_refusals(float q, const uint32_t *a, int axis, int64_t sx, int64_t s
   const uint64_t kmax = bb ? (uint64_t)((sx + 1) / 2) : (uint64_t)sx;
   uint64_t vmax = kmax * kmax * a[0];
   if (axis == 2 && !bb) vmax += (uint64_t)sy * (uint64_t)sy * a[1];
-  return vmax <= q16_value_limit(q, a[axis], n, bb);
+  return vmax <= q16_value_limit(Q.q, a[axis], n, bb);
 }
 
 // the quantum of a call (edt_colq16_lane.h: quantum_of), host side
-bool q16_quantum(const float *w, int naxes, float *q, uint32_t *a) {
-  const edt_q16::Quantum Q = edt_q16::quantum_of(w, naxes);
-  if (!Q.ok) return false;
-  *q = Q.q;
-  for (int i = 0; i < 3; ++i) a[i] = Q.a[i];
-  return true;
+Quantum q16_quantum(const float *w, int naxes) {
+  const edt_q16::Quantum L = edt_q16::quantum_of(w, naxes);
+  Quantum Q;
+  if (!L.ok) return Q;
+  Q.q = L.q;
+  for (int i = 0; i < 3; ++i) Q.a[i] = L.a[i];
+  Q.ok = true;
+  return Q;
 }
 
 }  // namespace edt_amd

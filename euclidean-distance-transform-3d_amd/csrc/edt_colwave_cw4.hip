@@ -3,7 +3,5 @@
 #include "edt_colwave_kernel.h"
 
 namespace edt_amd {
-template int launch_wave_c<4>(float *, const uint32_t *, const uint32_t *, const AxisGeom &, float, int, int,
-                               const XFuse *, hipStream_t, const BandScatter *, bool, const ColumnOut &,
-                               const TileList &);
+template int launch_wave_c<4>(const ColumnPass &, const TileList &);
 }  // namespace edt_amd

@@ -572,9 +572,12 @@ k_column_pass_wave(float *__restrict__ F, const uint32_t *__restrict__ nzbits,
 // launcher
 // ---------------------------------------------------------------------------------------
 template <int CW, bool BB, bool XF, bool SC>
-static int launch_wave_cbx_sc(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w,
-                           int epi, const XFuse &xf, hipStream_t stream, const BandScatter *scatter,
-                           bool scatter_aligned, const ColumnOut &out_stride, const TileList &list) {
+static int launch_wave_cbx_sc(const ColumnPass &cp, const TileList &list) {
+  const AxisGeom &g = cp.g;
+  const float w = cp.w;
+  const ColumnOut &out_stride = cp.out;
+  XFuse xf = {nullptr, 0, 0.0f, 0};
+  if (XF) xf = {cp.codes, cp.codes_outer > 0 ? cp.codes_outer : g.outer_stride, cp.wx, cp.to_finite() ? 0x7f7fffff : 0x7f800000};
   constexpr int NBP = 64 / CW;
   using TG = edt_lane::TileGeom<CW>;
   constexpr int TC = TG::kCols;
@@ -584,14 +587,14 @@ static int launch_wave_cbx_sc(float *F, const uint32_t *nz, const uint32_t *rs, 
   ba.limit_bits = 0u;
   ba.x32 = 0;
   ba.force = 0;
-  ba.stride = (out_stride.stride == 2 && !EDT_DIAG_BITS(debug_mode(), 0x40000)) ? 2 : 1;  // (debug bit 0x40000: evaluate every row)
+  ba.stride = (out_stride.stride == 2 && !EDT_DIAG_BITS(debug_mode(), kDbgEveryRow)) ? 2 : 1;  // (debug bit 0x40000: evaluate every row)
   ba.compact = (out_stride.stride == 2 && !SC) ? out_stride.compact : nullptr;
   ba.c_outer = out_stride.outer;
   ba.c_row2 = out_stride.row2;
   ba.c_al = (reinterpret_cast<uintptr_t>(out_stride.compact) % 16) == 0 && (out_stride.outer % 4) == 0 && (out_stride.row2 % 4) == 0;
   if (ba.compact != nullptr) ba.stride = 2;  // (a compact destination has room for the even rows only)
-  if (!(debug_mode() & 0x2000) && w * w >= 1.17549435e-38f && (double)w * (double)w < 1.0e30) {
-    const bool force = (debug_mode() & 0x4000) != 0;
+  if (!(debug_mode() & kDbgNoWindow) && w * w >= 1.17549435e-38f && (double)w * (double)w < 1.0e30) {
+    const bool force = (debug_mode() & kDbgAllWindow) != 0;
     // The window limit (edt_colwave.hip: window_limit).  fp32 candidates need c_d exact in
     // fp32 up to the limit (w2 = 900: d <= 136): where exactness ends between 64 rows and the limit, the limit
     // is lowered to it (fp32 candidates are ~25 % cheaper than fp64 ones; the tiles in between go to the hulls).
@@ -602,13 +605,13 @@ static int launch_wave_cbx_sc(float *F, const uint32_t *nz, const uint32_t *rs, 
     // field (g.fmin) and the fp64 sums of the reference are exact on tiles up to c_Tf (brute_f32e_prefix) -- not for a
     // forced tile, whose values are not bounded by c_T.  Failing that, the exact prefix where it is worth a window.
     if (mode == 0 && !force) {
-      const int Tf = (g.fmin > 0.0f && !(debug_mode() & 0x2000000)) ? edt_lane::brute_f32e_prefix(w, g.fmin, T) : 0;
+      const int Tf = (g.fmin > 0.0f && !(debug_mode() & kDbgFp64Inexact)) ? edt_lane::brute_f32e_prefix(w, g.fmin, T) : 0;
       if (Tf >= 64 && Tf > exact) { T = Tf; mode = 2; }
       else if (exact >= 64) { T = exact; mode = 1; }
     }
     // (fp64 candidates walk their far rows one by one: beyond ~190 rows the hull path is the better form for them)
     if (mode == 0 && !force && T > 192) T = 192;
-    if (debug_mode() & 0x8000) mode = 0;  // diagnostics: fp64 candidates
+    if (debug_mode() & kDbgWindowFp64) mode = 0;  // diagnostics: fp64 candidates
     ba.x32 = mode;
     const double cT = (double)(w * w) * (double)T * (double)T;
     float lim = cT < 3.0e38 ? (float)cT : 3.0e38f;
@@ -626,39 +629,30 @@ static int launch_wave_cbx_sc(float *F, const uint32_t *nz, const uint32_t *rs, 
   const int64_t tiles_x = ceil_div(g.sx, TC);
   int64_t tiles = tiles_x * g.nouter;
   if (tiles <= 0) return EDT_OK;
-  if (!(debug_mode() & 0x800)) tiles = tiles_x * (ceil_div(g.nouter, 8) * 8);  // XCD-aware order
+  if (!(debug_mode() & kDbgPlainTileOrder)) tiles = tiles_x * (ceil_div(g.nouter, 8) * 8);  // XCD-aware order
   // 16-byte granules need 16-byte aligned rows; otherwise the tile moves float by float
+  // (the caller of the scattering variant guarantees 16-byte aligned destinations when sx % 4 == 0)
   const int aligned16 = (g.sx % 4) == 0 && (g.stride % 4) == 0 && (g.outer_stride % 4) == 0 &&
-                        (reinterpret_cast<uintptr_t>(F) % 16) == 0 && (scatter == nullptr || scatter_aligned) &&
-                        (!XF || reinterpret_cast<uintptr_t>(xf.codes) % 8 == 0);
+                        (reinterpret_cast<uintptr_t>(cp.F) % 16) == 0 && (!XF || reinterpret_cast<uintptr_t>(xf.codes) % 8 == 0);
   if (tiles > 0x7FFFFFFF) { set_error("too many tiles"); return EDT_ERR_UNSUPPORTED; }
-  hipLaunchKernelGGL((k_column_pass_wave<CW, BB, XF, SC>), dim3((unsigned)tiles), dim3(64 * TC / CW), lds, stream,
-                     F, nz, rs, g, w, (int)tiles_x, epi & (3 | kEpiStream), debug_mode(), aligned16, xf, scatter, ba);
+  hipLaunchKernelGGL((k_column_pass_wave<CW, BB, XF, SC>), dim3((unsigned)tiles), dim3(64 * TC / CW), lds, cp.stream, cp.F, cp.nz,
+                     cp.rs, g, w, (int)tiles_x, cp.epi & (3 | kEpiStream), debug_mode(), aligned16, xf, SC ? cp.scatter : nullptr, ba);
   EDT_HIP_TRY(hipGetLastError());
   return EDT_OK;
 }
 
 template <int CW, bool BB, bool XF>
-static int launch_wave_cbx(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w,
-                           int epi, const XFuse &xf, hipStream_t stream, const BandScatter *scatter,
-                           bool scatter_aligned, const ColumnOut &out_stride, const TileList &list) {
+static int launch_wave_cbx(const ColumnPass &cp, const TileList &list) {
   // the scattering epilogue (Z-sharded path) is a compile-time variant
-  if (scatter != nullptr)
-    return launch_wave_cbx_sc<CW, BB, XF, true>(F, nz, rs, g, w, epi, xf, stream, scatter, scatter_aligned, out_stride, list);
-  return launch_wave_cbx_sc<CW, BB, XF, false>(F, nz, rs, g, w, epi, xf, stream, nullptr, false, out_stride, list);
+  if (cp.scatter != nullptr) return launch_wave_cbx_sc<CW, BB, XF, true>(cp, list);
+  return launch_wave_cbx_sc<CW, BB, XF, false>(cp, list);
 }
 
 template <int CW>
-int launch_wave_c(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w,
-                         int bb, int epi, const XFuse *xf, hipStream_t stream, const BandScatter *scatter,
-                         bool sc_al, const ColumnOut &out_stride, const TileList &list) {
+int launch_wave_c(const ColumnPass &cp, const TileList &list) {
   // the border rule and the index form of pass 1 are compile-time variants, the epilogue a run-time one
-  const XFuse none = {nullptr, 0, 0.0f, 0};
-  if (xf)
-    return bb ? launch_wave_cbx<CW, true, true>(F, nz, rs, g, w, epi, *xf, stream, scatter, sc_al, out_stride, list)
-              : launch_wave_cbx<CW, false, true>(F, nz, rs, g, w, epi, *xf, stream, scatter, sc_al, out_stride, list);
-  return bb ? launch_wave_cbx<CW, true, false>(F, nz, rs, g, w, epi, none, stream, scatter, sc_al, out_stride, list)
-            : launch_wave_cbx<CW, false, false>(F, nz, rs, g, w, epi, none, stream, scatter, sc_al, out_stride, list);
+  if (cp.codes != nullptr) return cp.bb ? launch_wave_cbx<CW, true, true>(cp, list) : launch_wave_cbx<CW, false, true>(cp, list);
+  return cp.bb ? launch_wave_cbx<CW, true, false>(cp, list) : launch_wave_cbx<CW, false, false>(cp, list);
 }
 
 }  // namespace edt_amd

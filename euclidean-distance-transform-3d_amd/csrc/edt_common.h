@@ -28,24 +28,40 @@ void set_error(const std::string &msg);
 // whole parity suite); the bits that switch phases off and produce wrong results (1, 2, 4, 8, 0x200, 0x40000,
 // 0x80000: measuring what a phase costs) exist only in a library built with -DEDT_DIAG and are compiled out of the
 // kernels otherwise.
-//   16 / 0x10000  no all-flat shortcut / no self-owned rows      32 / 64   tiled row pass / tiled column pass
-//   256           plain group order in pass X                    0x800     plain tile order in the column pass
-//   0x1000        name every pass on stderr                      0x2000    no tile takes the windowed path
-//   0x4000        every tile takes the windowed path             0x8000    fp64 candidates on the windowed path
-//   0x20000       voxel graph: up-sampled formulation            0x100000  fp32 form of pass X (no 16-bit indices)
-//   0x200000      voxel graph: separate gather pass              0x400000, 0x800000  (round 3's bracket-path experiment: no effect
-//                 now, experiments/colwave_r03)                  0x1000000 short axes (<= 32 rows) stay on the wave kernel
-//   0x2000000     inexact voxel sizes: fp64 candidates even where fp32 fma candidates are exact
-//   0x4000000     rows of 1025..2048 voxels: the workgroup-phased kernel of pass X, not the two-wave form
-//   0x8000000     no 16-bit integer column kernel (edt_colq16.hip): every tile on the fp32 kernels
-//   0x10000000    integer column kernels: fp32 values between passes Y and Z, not the 16-bit plane
-//   0x20000000    integer column kernels: no wide form (tiles beyond 16 bits go to the fp32 kernel, as in round 4); with it
-//                 the fp32 launch over the hand-over list is never skipped
-//   0x40000000    integer column kernels: a tile beyond 16 bits always as two wide passes over all its columns (no column subset)
-//   0x80          integer column kernels: no short cuts for whole tiles -- a tile of nothing but +inf goes through the wide form like any
-//                 other, a tile without structure along the scan axis through scans, break bits and blocks
-//   0x400         no short cuts from "both column passes provably on the integer kernel": the foreground planes are written and
-//                 transposed although nobody reads them; the signed transform's sign is a pass of its own, not the last pass's epilogue
+enum : int {
+  kDbgNoFlatShortcut = 16, kDbgNoOwnRows = 0x10000,  // no all-flat shortcut / no self-owned rows
+  kDbgTiledRows = 32, kDbgTiledColumns = 64,         // tiled row pass / tiled column pass
+  kDbgPlainGroupOrder = 256,                         // plain group order in pass X
+  kDbgPlainTileOrder = 0x800,                        // plain tile order in the column pass
+  kDbgNamePasses = 0x1000,                           // name every pass on stderr
+  kDbgNoWindow = 0x2000,                             // no tile takes the windowed path
+  kDbgAllWindow = 0x4000,                            // every tile takes the windowed path
+  kDbgWindowFp64 = 0x8000,                           // fp64 candidates on the windowed path
+  kDbgVgUpsampled = 0x20000,                         // voxel graph: up-sampled formulation
+  kDbgEveryRow = 0x40000,                            // (EDT_DIAG) output stride 2: every row evaluated, no integer column kernel
+  kDbgFp32PassX = 0x100000,                          // fp32 form of pass X (no 16-bit indices)
+  kDbgVgGather = 0x200000,                           // voxel graph: separate gather pass
+  // 0x400000, 0x800000: round 3's bracket-path experiment: no effect now, experiments/colwave_r03
+  kDbgShortOnWave = 0x1000000,                       // short axes (<= 32 rows) stay on the wave kernel
+  kDbgFp64Inexact = 0x2000000,   // inexact voxel sizes: fp64 candidates even where fp32 fma candidates are exact
+  kDbgPhasedRows = 0x4000000,    // rows of 1025..2048 voxels: the workgroup-phased kernel of pass X, not the two-wave form
+  kDbgNoQ16 = 0x8000000,         // no 16-bit integer column kernel (edt_colq16.hip): every tile on the fp32 kernels
+  kDbgFp32Plane = 0x10000000,    // integer column kernels: fp32 values between passes Y and Z, not the 16-bit plane
+  // integer column kernels: no wide form (tiles beyond 16 bits go to the fp32 kernel, as in round 4); with it the fp32 launch
+  // over the hand-over list is never skipped
+  kDbgNoWide = 0x20000000,
+  // integer column kernels: a tile beyond 16 bits always as two wide passes over all its columns (no column subset)
+  kDbgWideAllColumns = 0x40000000,
+  // integer column kernels: no short cuts for whole tiles -- a tile of nothing but +inf goes through the wide form like any
+  // other, a tile without structure along the scan axis through scans, break bits and blocks
+  kDbgNoTileShortcuts = 0x80,
+  // no short cuts from "both column passes provably on the integer kernel": the foreground planes are written and transposed
+  // although nobody reads them; the signed transform's sign is a pass of its own, not the last pass's epilogue
+  kDbgKeepPlanes = 0x400,
+};
+// the bits that force one form of the fp32 column kernel on every tile -- the test tiers' way to cover them -- keep every
+// column pass there: no 16-bit integer kernel
+constexpr int kDbgQ16Off = kDbgNoFlatShortcut | kDbgTiledColumns | kDbgNoWindow | kDbgAllWindow | kDbgWindowFp64 | kDbgNoOwnRows;
 constexpr int kDiagFormBits = 16 | 32 | 64 | 0x80 | 256 | 0x400 | 0x800 | 0x1000 | 0x2000 | 0x4000 | 0x8000 | 0x10000 | 0x20000 |
                               0x100000 | 0x200000 | 0x400000 | 0x800000 | 0x1000000 | 0x2000000 | 0x4000000 | 0x8000000 | 0x10000000 |
                               0x20000000 | 0x40000000;
@@ -133,5 +149,7 @@ struct BandScatter {
 // kEpiSign: the signed transform (EDT_FLAG_SIGNED) -- the integer column kernel of the call's last pass negates the results of the
 // voxels whose foreground bit (Q16Args::signbits: the true label != 0 plane of that axis) is clear, instead of a pass of its own
 enum : int { kEpiToInf = 1, kEpiSqrt = 2, kEpiStream = 4, kEpiSign = 8 };
+// the epilogue of a call's last pass (it writes the call's results: streamed)
+inline int last_pass_epi(int bb, bool take_sqrt) { return (bb ? 0 : kEpiToInf) | (take_sqrt ? kEpiSqrt : 0) | kEpiStream; }
 
 }  // namespace edt_amd

@@ -363,14 +363,13 @@ int launch_ft_t(const T *labels, const FtCall &c, const V av[3], const FtBuffers
 // Where the voxel sizes share a quantum and every value of the call (the pass values, and the numerators of the envelope
 // intersections: at most 4 * sum a_i (s_i + 1)^2) stays below 2^62, the passes run on exact int64 quanta.
 bool integer_values(const FtCall &c, int64_t a[3]) {
-  float q = 1.0f;
-  uint32_t qa[3] = {1u, 1u, 1u};
-  if (!q16_quantum(c.w, c.ndim, &q, qa)) return false;
+  const Quantum Q = q16_quantum(c.w, c.ndim);
+  if (!Q.ok) return false;
   const int64_t s[3] = {c.sx, c.sy, c.sz};
   double bound = 0.0;
-  for (int i = 0; i < c.ndim; ++i) bound += (double)qa[i] * (double)(s[i] + 1) * (double)(s[i] + 1);
+  for (int i = 0; i < c.ndim; ++i) bound += (double)Q.a[i] * (double)(s[i] + 1) * (double)(s[i] + 1);
   if (4.0 * bound >= 4.0e18) return false;
-  for (int i = 0; i < 3; ++i) a[i] = qa[i];
+  for (int i = 0; i < 3; ++i) a[i] = Q.a[i];
   return true;
 }
 

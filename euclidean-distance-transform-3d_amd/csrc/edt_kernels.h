@@ -128,48 +128,98 @@ struct ColumnOut {
 struct TileList {
   const uint32_t *count = nullptr;
   const uint32_t *ids = nullptr;
-  bool none = false;  // the integer kernel served EVERY tile and the host can prove it (edt_api.hip): no fp32 launch at all
+  bool none = false;  // the integer kernel served EVERY tile and the host can prove it (edt_colpass.hip): no fp32 launch at all
 };
-// scatter != nullptr (device table): the rows are written to the slab records instead of F
-// out: see ColumnOut (default: every row, in place) -- (tiles on the windowed path evaluate and write
-// just those; tiles on the hull path still write every row)
-int launch_column_pass_wave(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g,
-                            float w, int bb, int epi, hipStream_t stream,
-                            const BandScatter *scatter = nullptr, const ColumnOut &out = ColumnOut(),
-                            const TileList &list = TileList());
-// the same reading pass 1 as 16-bit distance indices (F is write-only): see XFuse
-int launch_column_pass_wave_codes(float *F, const uint16_t *codes, const uint32_t *nz, const uint32_t *rs,
-                                  const AxisGeom &g, float w, int bb, int epi, float wx, int to_finite,
-                                  hipStream_t stream, const BandScatter *scatter = nullptr, const TileList &list = TileList(),
-                                  const ColumnOut &out = ColumnOut(), int64_t codes_outer = 0);
+// One column pass (Y or Z), whichever kernel serves it: the fp32 wave kernel reads F, nz, rs (and codes), the 16-bit integer
+// kernel F, rs (and codes / the plane).
+struct ColumnPass {
+  float *F = nullptr;                         // the field: read and written in place, unless an input form below says otherwise
+  const uint32_t *nz = nullptr, *rs = nullptr;  // foreground / run-start bit planes of the scan axis
+  AxisGeom g;
+  float w = 1.0f;                             // voxel size along the scan axis
+  int bb = 0, epi = 0;
+  hipStream_t stream = nullptr;
+  // input, index form: pass X left 16-bit distance indices (see XFuse) and F is only written
+  const uint16_t *codes = nullptr;
+  int64_t codes_outer = 0;  // outer stride of codes (and of the plane written over them), 0: g.outer_stride
+  float wx = 0.0f;          // voxel size of pass X
+  // the 16-bit plane of the integer kernel (volumes whose indices fit one slab): with codes, the results stay 16-bit -- written
+  // over the indices (plane == codes), the tile's bit set in map [x-tile][map_words]; without codes, every row is read from the
+  // plane where map says so and from F elsewhere (the pass after such a pass).
+  // Slab records of 16-bit values (edt_shard_api.hip): with codes, a scatter table AND a plane (any non-null value) the results go to
+  // the table's destinations as 16-bit rows, refused tiles are only counted (no id array); without codes, a map of ones
+  // and plane_stride > 0 every row is read from the plane at its own strides (16-bit elements) and F is only written.
+  uint16_t *plane = nullptr;
+  uint32_t *map = nullptr;
+  int map_words = 0;
+  int64_t plane_stride = 0, plane_outer = 0;
+  int plane_inf_ok = 0;  // the pass that reads the 16-bit plane this one writes carries +inf
+  // destination: see ColumnOut (default: every row, in place) -- (tiles on the windowed path evaluate and write just those;
+  // tiles on the hull path still write every row); scatter != nullptr (device table): the rows are written to the slab
+  // records instead of F (the caller guarantees 16-byte aligned destinations when sx % 4 == 0)
+  ColumnOut out;
+  const BandScatter *scatter = nullptr;
+  const uint32_t *signbits = nullptr;  // kEpiSign: the true foreground plane of this axis
+  int to_finite() const { return bb ? 0 : 1; }  // pass X left FLT_MAX (tofinite), not +inf, where a row has no boundary
+};
+inline ColumnPass column_pass(float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w, int bb, int epi,
+                              hipStream_t stream) {
+  ColumnPass cp;
+  cp.F = F; cp.nz = nz; cp.rs = rs; cp.g = g; cp.w = w; cp.bb = bb; cp.epi = epi; cp.stream = stream;
+  return cp;
+}
+// the fp32 wave kernel over the tiles of `list`; codes != nullptr: reading pass 1 as 16-bit distance indices (see XFuse)
+int launch_column_pass_wave(const ColumnPass &cp, const TileList &list);
 // ---- 16-bit integer column pass: edt_colq16.hip ---------------------------------------------------
-// the quantum of a call: w_i^2 = a[i] * q (false: the voxel sizes share none, the fp32 kernels keep the call)
-bool q16_quantum(const float *w, int naxes, float *q, uint32_t *a);
+// the quantum of a call: w_i^2 = a[i] * q (ok false: the voxel sizes share none, the fp32 kernels keep the call)
+struct Quantum {
+  float q = 1.0f;
+  uint32_t a[3] = {1u, 1u, 1u};
+  bool ok = false;
+};
+Quantum q16_quantum(const float *w, int naxes);
 bool column_pass_q16_supported(const AxisGeom &g);
 // the largest value, in quanta, a tile of a pass with c_d = a * d^2 may hold and stay on the integer kernel (its 16-bit
 // form, or the wide form: two half-tiles with 32-bit lanes) -- what a host that knows a bound of the field compares with
 uint32_t q16_value_limit(float q, uint32_t a, int64_t n, int bb);
 // the host's proof that the integer kernel refuses NO tile of a column pass of a call in the index form (axis 1: pass Y over
 // columns of n = sy rows; axis 2: pass Z over n = sz rows behind a pass Y that could not refuse either) -- edt_colq16.hip
-bool q16_no_refusals(float q, const uint32_t *a, int axis, int64_t sx, int64_t sy, int64_t n, int bb);
+bool q16_no_refusals(const Quantum &Q, int axis, int64_t sx, int64_t sy, int64_t n, int bb);
 // the kernel's vector accesses: 16-byte loads of fp32 rows, 8-byte stores of result pairs, 8-byte loads of index / plane
 // rows (a 4-byte-aligned view handed in through DLPack stays on the fp32 kernel, which gates its vector accesses itself)
 inline bool column_pass_q16_aligned(const float *F, const uint16_t *codes, const uint16_t *plane, const float *compact = nullptr) {
   return (reinterpret_cast<uintptr_t>(F) % 16) == 0 && (reinterpret_cast<uintptr_t>(codes) % 8) == 0 &&
          (reinterpret_cast<uintptr_t>(plane) % 8) == 0 && (reinterpret_cast<uintptr_t>(compact) % 8) == 0;
 }
-// codes != nullptr: pass X in index form (N = k^2 * ain), F is only written; else F is read (N = F / q, verified) and
-// written in place.  a: c_d = a * d^2 quanta.  Tiles that do not qualify are appended to (count, ids) for the fp32 kernel.
-// plane / map (volumes whose indices fit one slab): with codes, the results stay 16-bit -- written over the indices
-// (plane == codes), the tile's bit set in map [x-tile][map_words]; without codes, every row is read from the plane where
-// map says so and from F elsewhere (the pass after such a pass).
-int launch_column_pass_q16(float *F, const uint16_t *codes, const uint32_t *rs, const AxisGeom &g, float q, uint32_t a,
-                           uint32_t ain, int bb, int epi, uint32_t *count, uint32_t *ids, hipStream_t stream,
-                           const BandScatter *scatter = nullptr, uint16_t *plane = nullptr, uint32_t *map = nullptr,
-                           int map_words = 0, const ColumnOut *out = nullptr, int64_t plane_stride = 0, int64_t plane_outer = 0,
-                           int plane_inf_ok = 0,   // the pass that reads the 16-bit plane this one writes carries +inf
-                           const uint32_t *signbits = nullptr,  // kEpiSign: the true foreground plane of this axis
-                           int64_t codes_outer = 0);  // outer stride of codes (and of the plane written over them), 0: g.outer_stride
+// The hand-over from the integer kernel to the fp32 kernel: counters (one per launch: `slot` is the next free one) and one
+// array of tile ids in the fp32 kernel's geometry (launches are stream-ordered: the array is reused).
+struct HandOver {
+  uint32_t *counts = nullptr, *ids = nullptr;
+  int slots = 0;
+  int64_t capacity = 0;  // tile ids `ids` holds (0 with ids == nullptr: refused tiles are only counted)
+  int slot = 0;
+  bool zeroed = false;   // the counters are zero on the stream (run_column_pass zeroes them before the first launch that needs it)
+  // the ids a pass over nouter outer indices may write (16-column tiles for axes of more than 512 rows, XCD-aware tile order)
+  static int64_t ids_of(int64_t sx, int64_t nouter) { return ceil_div(sx, 16) * (ceil_div(nouter, 8) * 8); }
+  int zero(hipStream_t stream);  // all `slots` counters
+};
+// cp.codes != nullptr: pass X in index form (N = k^2 * Q.a[0]), F is only written; else F is read (N = F / q, verified) and
+// written in place.  c_d = Q.a[axis] * d^2 quanta.  Tiles that do not qualify are appended to h's list (counter h.slot).
+int launch_column_pass_q16(const ColumnPass &cp, const Quantum &Q, int axis, HandOver h);
+// ---- the driver of a column pass: edt_colpass.hip ---------------------------------------------------
+// In-place LDS-tiled column pass where one applies: the fp32 kernel for this axis (short / wave / workgroup-phased), or the
+// wave kernel over `list`
+bool column_inplace_supported(const AxisGeom &g);
+int launch_column_inplace(const ColumnPass &cp, const TileList &list = TileList());
+// will run_column_pass launch the integer kernel for this geometry?  (the shape and mode part of its test)
+bool column_pass_q16_applies(const Quantum &Q, const AxisGeom &g, const HandOver &h);
+// The integer kernel where it applies (Q.ok, modes, shape, alignment, capacity of h), then the fp32 kernel over the tiles it
+// refused -- or over every tile -- through `leg`: the wave kernel, or launch_column_inplace's choice.  sure: the caller vouches
+// for what the pass reads (see edt_colpass.hip).  served: count != nullptr -- the integer kernel ran; none -- its list is
+// provably empty and no fp32 launch was made.  A hand-over without an id array only counts: no fp32 launch.
+enum class Fp32Leg { wave, inplace };
+int run_column_pass(const ColumnPass &cp, const Quantum &Q, int axis, HandOver &h, Fp32Leg leg, bool sure = false,
+                    TileList *served = nullptr);
 }  // namespace edt_amd
 
 namespace edt_amd {

@@ -14,6 +14,12 @@ struct ShardPlan {
   size_t bytes = 0;
 };
 
+static int check_shard_workspace(const void *ws, size_t have, size_t need) {
+  if (ws && have >= need) return EDT_OK;
+  set_error("shard workspace too small: need " + std::to_string(need) + " bytes");
+  return EDT_ERR_BAD_ARG;
+}
+
 static ShardPlan make_shard_plan(int64_t sx, int64_t sy, int64_t sz, void *ws) {
   // sized for the larger of the two phases run on an (sx, sy, sz) block
   ShardPlan p;
@@ -44,7 +50,7 @@ struct RecordPlan {
   uint32_t *nz_y = nullptr, *ys_y = nullptr, *zs_y = nullptr;  // y-packed planes of the slab
   uint32_t *nz_z = nullptr, *rs_z = nullptr;               // z-packed planes (Z phase)
   BandScatter *table = nullptr;
-  uint32_t *q16_counts = nullptr, *q16_ids = nullptr;      // hand-over list of the integer column kernel (one phase per call)
+  HandOver q16;                                            // hand-over list of the integer column kernel (one phase per call)
   uint32_t *ones_map = nullptr;                            // 16-bit records, Z phase: "every row of every tile is in the plane"
   size_t bytes = 0;
 };
@@ -62,11 +68,49 @@ static RecordPlan make_record_plan(int64_t sx, int64_t sy, int64_t sz, void *ws)
   p.nz_z = c.take<uint32_t>(wz);
   p.rs_z = c.take<uint32_t>(wz);
   p.table = c.take<BandScatter>(1);
-  p.q16_counts = c.take<uint32_t>(4);
-  p.q16_ids = c.take<uint32_t>((size_t)(ceil_div(sx, 16) * (ceil_div(std::max(sy, sz), 8) * 8)));
+  p.q16.slots = 4;
+  p.q16.counts = c.take<uint32_t>(4);
+  p.q16.capacity = HandOver::ids_of(sx, std::max(sy, sz));
+  p.q16.ids = c.take<uint32_t>((size_t)p.q16.capacity);
   p.ones_map = c.take<uint32_t>((size_t)(ceil_div(sx, 32) * ceil_div(std::max(sy, sz), 32)));
   p.bytes = align_up(c.off, 256) + 256;
   return p;
+}
+
+// the parts of y a slab's records go to: block h takes rows y_splits[h] .. y_splits[h + 1]
+// (align 8 -- 16-bit records: 4-byte stores of packed pairs and bit words; the Z phase reads 8 bytes at a time: records are an
+// even number of words)
+static int check_y_splits(int nparts, const int64_t *y_splits, void *const *d_blocks, int64_t sy, int align) {
+  if (y_splits[0] != 0 || y_splits[nparts] != sy) { set_error("y_splits must run from 0 to sy"); return EDT_ERR_BAD_ARG; }
+  for (int h = 0; h < nparts; ++h) {
+    if (y_splits[h + 1] <= y_splits[h] || (y_splits[h] % kBandRows) != 0) {
+      set_error("y_splits must be increasing multiples of 32 (the last one is sy)");
+      return EDT_ERR_BAD_ARG;
+    }
+    if (!d_blocks[h] || (align && (reinterpret_cast<uintptr_t>(d_blocks[h]) % align) != 0)) {
+      set_error(align ? "destination blocks must be non-null and 8-byte aligned" : "null destination block");
+      return EDT_ERR_BAD_ARG;
+    }
+  }
+  return EDT_OK;
+}
+
+// destination map: every 32-row band of y lies inside one part.  Records of fp32 rows, or (rows16) in 4-byte words: a record =
+// ylen * sx / 2 words of 16-bit pairs, then the two bit planes
+static BandScatter make_band_scatter(const AxisGeom &gy, const int64_t *y_splits, void *const *d_blocks, bool rows16) {
+  BandScatter sc;
+  const int64_t sx = gy.sx, per_word = rows16 ? 2 : 1;
+  for (int b = 0, h = 0; b < BandScatter::kBands; ++b) {
+    if (b >= gy.nbands) { sc.rows[b] = nullptr; sc.bits[b] = nullptr; sc.ostride[b] = 0; sc.plane[b] = 0; continue; }
+    while ((int64_t)b * kBandRows >= y_splits[h + 1]) ++h;
+    const int64_t ys = y_splits[h], ylen = y_splits[h + 1] - ys, words = ceil_div(ylen, kBandRows);
+    float *blk = static_cast<float *>(d_blocks[h]);
+    sc.rows[b] = blk + (((int64_t)b * kBandRows - ys) * sx) / per_word;
+    sc.bits[b] = reinterpret_cast<uint32_t *>(blk + ylen * sx / per_word) + ((int64_t)b - ys / kBandRows) * sx;
+    sc.ostride[b] = rows16 ? record16_words(sx, ylen) : record_floats(sx, ylen);
+    sc.plane[b] = words * sx;
+  }
+  return sc;
 }
 
 }  // namespace edt_amd
@@ -92,10 +136,7 @@ int edt_hip_shard_xy_device(const void *d_labels, const void *d_halo, int dtype,
   if (sx == 0 || sy == 0 || sz_local == 0) return EDT_OK;
   if (!d_labels || !d_partial || !d_zflags) { set_error("null device pointer"); return EDT_ERR_BAD_ARG; }
   ShardPlan p = make_shard_plan(sx, sy, sz_local, d_workspace);
-  if (!d_workspace || workspace_bytes < p.bytes) {
-    set_error("shard workspace too small: need " + std::to_string(p.bytes) + " bytes");
-    return EDT_ERR_BAD_ARG;
-  }
+  if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
   const bool force_generic = (flags & EDT_FLAG_FORCE_GENERIC) != 0;
   AxisGeom gy = make_geom_y(sx, sy, sz_local);
@@ -118,7 +159,7 @@ int edt_hip_shard_xy_device(const void *d_labels, const void *d_halo, int dtype,
     rc = launch_axis_bits(dtype, d_labels, nullptr, p.nz, p.rs, gy, stream);
     if (rc != EDT_OK) return rc;
   }
-  if (tiled_y) rc = launch_column_inplace(d_partial, p.nz, p.rs, gy, wy, bb, 0, stream);
+  if (tiled_y) rc = launch_column_inplace(column_pass(d_partial, p.nz, p.rs, gy, wy, bb, 0, stream));
   else rc = launch_column_pass_serial(p.bufB, d_partial, p.nz, p.rs, p.stack, gy, wy, bb, 0, stream);
   if (rc != EDT_OK) return rc;
   return launch_zflags(dtype, d_labels, d_halo, d_zflags, sx * sy, sz_local, stream);
@@ -141,18 +182,15 @@ int edt_hip_shard_z_device_ex(float *d_partial, const uint8_t *d_zflags, int64_t
   if (sx == 0 || sy_local == 0 || sz == 0) return EDT_OK;
   if (!d_partial || !d_zflags) { set_error("null device pointer"); return EDT_ERR_BAD_ARG; }
   ShardPlan p = make_shard_plan(sx, sy_local, sz, d_workspace);
-  if (!d_workspace || workspace_bytes < p.bytes) {
-    set_error("shard workspace too small: need " + std::to_string(p.bytes) + " bytes");
-    return EDT_ERR_BAD_ARG;
-  }
+  if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
-  const int epi = (bb ? 0 : kEpiToInf) | ((flags & EDT_FLAG_SQRT) ? kEpiSqrt : 0) | kEpiStream;  // (the Z phase writes the call's results)
+  const int epi = last_pass_epi(bb, (flags & EDT_FLAG_SQRT) != 0);  // (the Z phase writes the call's results)
   AxisGeom gz = make_geom_z(sx, sy_local, sz);
   gz.fmin = field_floor > 0.0f ? field_floor : 0.0f;  // (AxisGeom::fmin; NaN and negatives: unknown)
   rc = launch_bits_from_flags(d_zflags, p.nz, p.rs, gz, stream);
   if (rc != EDT_OK) return rc;
   if (!(flags & EDT_FLAG_FORCE_GENERIC) && column_inplace_supported(gz))
-    return launch_column_inplace(d_partial, p.nz, p.rs, gz, wz, bb, epi, stream);
+    return launch_column_inplace(column_pass(d_partial, p.nz, p.rs, gz, wz, bb, epi, stream));
   rc = launch_column_pass_serial(d_partial, p.bufB, p.nz, p.rs, p.stack, gz, wz, bb, epi, stream);
   if (rc != EDT_OK) return rc;
   EDT_HIP_TRY(hipMemcpyAsync(d_partial, p.bufB, (size_t)(sx * sy_local * sz) * sizeof(float),
@@ -162,7 +200,7 @@ int edt_hip_shard_z_device_ex(float *d_partial, const uint8_t *d_zflags, int64_t
 
 int edt_hip_shard_records_supported(int dtype, int64_t sx, int64_t sy, int64_t sz) {
   if (dtype_size(dtype) == 0 || sx < 1 || sy < 1 || sz < 1) return 0;
-  if (debug_mode() & (32 | 64)) return 0;  // diagnostics: forced fallback kernels
+  if (debug_mode() & (kDbgTiledRows | kDbgTiledColumns)) return 0;  // diagnostics: forced fallback kernels
   // pass 1 by the register-resident row kernel (two waves per row beyond 1024 voxels), both column passes by the wave kernel
   return (sx <= 2048 && row_pass_wave_supported(dtype, sx, sy, sz) && sy <= 2048 && sz <= 2048) ? 1 : 0;
 }
@@ -192,44 +230,23 @@ int edt_hip_shard_xy_records_device(const void *d_labels, const void *d_halo, in
     set_error("slab records need sx <= 2048 and sy <= 2048 (use edt_hip_shard_xy_device)");
     return EDT_ERR_UNSUPPORTED;
   }
-  if (y_splits[0] != 0 || y_splits[nparts] != sy) { set_error("y_splits must run from 0 to sy"); return EDT_ERR_BAD_ARG; }
-  for (int h = 0; h < nparts; ++h) {
-    if (y_splits[h + 1] <= y_splits[h] || (y_splits[h] % kBandRows) != 0) {
-      set_error("y_splits must be increasing multiples of 32 (the last one is sy)");
-      return EDT_ERR_BAD_ARG;
-    }
-    if (!d_blocks[h]) { set_error("null destination block"); return EDT_ERR_BAD_ARG; }
-  }
+  if ((rc = check_y_splits(nparts, y_splits, d_blocks, sy, 0)) != EDT_OK) return rc;
   if (g_log.enabled.load(std::memory_order_relaxed)) {
     std::lock_guard<std::mutex> lock(g_log_mutex);
     if (g_log.used > 2048) log_begin_call();  // nobody is reading the log
   }
   RecordPlan p = make_record_plan(sx, sy, sz_local, d_workspace);
-  if (!d_workspace || workspace_bytes < p.bytes) {
-    set_error("shard workspace too small: need " + std::to_string(p.bytes) + " bytes");
-    return EDT_ERR_BAD_ARG;
-  }
+  if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
   AxisGeom gy = make_geom_y(sx, sy, sz_local);
   gy.fmin = edt_hip_field_floor(wx, wx);  // (pass Y reads the results of pass X: AxisGeom::fmin)
-  // destination map: every 32-row band of y lies inside one part
-  BandScatter sc;
-  bool aligned = (sx % 4) == 0;
-  for (int b = 0, h = 0; b < BandScatter::kBands; ++b) {
-    if (b >= gy.nbands) { sc.rows[b] = nullptr; sc.bits[b] = nullptr; sc.ostride[b] = 0; sc.plane[b] = 0; continue; }
-    while ((int64_t)b * kBandRows >= y_splits[h + 1]) ++h;
-    const int64_t ys = y_splits[h], ylen = y_splits[h + 1] - ys, words = ceil_div(ylen, kBandRows);
-    float *blk = static_cast<float *>(d_blocks[h]);
-    sc.rows[b] = blk + ((int64_t)b * kBandRows - ys) * sx;
-    sc.bits[b] = reinterpret_cast<uint32_t *>(blk + ylen * sx) + ((int64_t)b - ys / kBandRows) * sx;
-    sc.ostride[b] = record_floats(sx, ylen);
-    sc.plane[b] = words * sx;
-    aligned = aligned && (reinterpret_cast<uintptr_t>(blk) % 16) == 0;
-  }
-  if (!aligned && (sx % 4) == 0) { set_error("destination blocks must be 16-byte aligned"); return EDT_ERR_BAD_ARG; }
+  // (the scattering column kernels store 16 bytes at a time where rows are whole granules)
+  for (int h = 0; h < nparts && (sx % 4) == 0; ++h)
+    if ((reinterpret_cast<uintptr_t>(d_blocks[h]) % 16) != 0) { set_error("destination blocks must be 16-byte aligned"); return EDT_ERR_BAD_ARG; }
+  const BandScatter sc = make_band_scatter(gy, y_splits, d_blocks, false);
   // (index form of pass 1 where the voxel size allows it, see run_device: the slab's pass-1 buffer then holds 16-bit
   // indices in its first half)
-  const bool index_form = (sx % 4) == 0 && !(debug_mode() & 0x100000) && row_codes_exact(wx, sx);
+  const bool index_form = (sx % 4) == 0 && !(debug_mode() & kDbgFp32PassX) && row_codes_exact(wx, sx);
   uint16_t *codes = index_form ? reinterpret_cast<uint16_t *>(p.F) : nullptr;
   {
     ScopedPass t("x_pass", stream);
@@ -244,23 +261,12 @@ int edt_hip_shard_xy_records_device(const void *d_labels, const void *d_halo, in
   }
   ScopedPass t("y_pass", stream);
   // the integer column kernel where wx and wy share a quantum (edt_colq16.hip), the tiles it refuses to the fp32 kernel
-  TileList list;
-  {
-    const float w2[2] = {wx, wy};
-    float q = 1.0f;
-    uint32_t a[3];
-    if (!(debug_mode() & (16 | 64 | 0x2000 | 0x4000 | 0x8000 | 0x10000)) && q16_quantum(w2, 2, &q, a) &&
-        column_pass_q16_supported(gy) && column_pass_wave_supported(gy) && aligned) {
-      EDT_HIP_TRY(hipMemsetAsync(p.q16_counts, 0, 4 * sizeof(uint32_t), stream));
-      rc = launch_column_pass_q16(p.F, codes, p.ys_y, gy, q, a[1], a[0], bb, 0, p.q16_counts, p.q16_ids, stream, p.table);
-      if (rc != EDT_OK) return rc;
-      list.count = p.q16_counts;
-      list.ids = p.q16_ids;
-    }
-  }
-  if (index_form)
-    return launch_column_pass_wave_codes(p.F, codes, p.nz_y, p.ys_y, gy, wy, bb, 0, wx, bb ? 0 : 1, stream, p.table, list);
-  return launch_column_pass_wave(p.F, p.nz_y, p.ys_y, gy, wy, bb, 0, stream, p.table, ColumnOut(), list);
+  const float w2[2] = {wx, wy};
+  ColumnPass cp = column_pass(p.F, p.nz_y, p.ys_y, gy, wy, bb, 0, stream);
+  cp.codes = codes;
+  cp.wx = wx;
+  cp.scatter = p.table;
+  return run_column_pass(cp, q16_quantum(w2, 2), 1, p.q16, Fp32Leg::wave);
 }
 
 int edt_hip_shard_z_records_device(float *d_records, int64_t sx, int64_t sy_local, int64_t sz, float wz,
@@ -299,12 +305,9 @@ static int shard_z_records(float *d_records, int64_t sx, int64_t sy_local, int64
     return EDT_ERR_UNSUPPORTED;
   }
   RecordPlan p = make_record_plan(sx, sy_local, sz, d_workspace);
-  if (!d_workspace || workspace_bytes < p.bytes) {
-    set_error("shard workspace too small: need " + std::to_string(p.bytes) + " bytes");
-    return EDT_ERR_BAD_ARG;
-  }
+  if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
-  const int epi = (bb ? 0 : kEpiToInf) | ((flags & EDT_FLAG_SQRT) ? kEpiSqrt : 0) | kEpiStream;  // (the Z phase writes the call's results)
+  const int epi = last_pass_epi(bb, (flags & EDT_FLAG_SQRT) != 0);  // (the Z phase writes the call's results)
   const int64_t rec = record_floats(sx, sy_local), words = ceil_div(sy_local, kBandRows);
   const uint32_t *nz_y = reinterpret_cast<const uint32_t *>(d_records + sy_local * sx);
   {
@@ -317,20 +320,8 @@ static int shard_z_records(float *d_records, int64_t sx, int64_t sy_local, int64
   gz.nbands = ceil_div(sz, kBandRows);
   gz.fmin = field_floor > 0.0f ? field_floor : 0.0f;
   ScopedPass t("z_pass", stream);
-  TileList list;
-  if (w3 != nullptr) {
-    float q = 1.0f;
-    uint32_t a[3];
-    if (!(debug_mode() & (16 | 64 | 0x2000 | 0x4000 | 0x8000 | 0x10000)) && q16_quantum(w3, 3, &q, a) &&
-        column_pass_q16_supported(gz) && column_pass_wave_supported(gz) && (reinterpret_cast<uintptr_t>(d_records) % 16) == 0) {
-      EDT_HIP_TRY(hipMemsetAsync(p.q16_counts, 0, 4 * sizeof(uint32_t), stream));
-      rc = launch_column_pass_q16(d_records, nullptr, p.rs_z, gz, q, a[2], a[0], bb, epi, p.q16_counts, p.q16_ids, stream);
-      if (rc != EDT_OK) return rc;
-      list.count = p.q16_counts;
-      list.ids = p.q16_ids;
-    }
-  }
-  return launch_column_pass_wave(d_records, p.nz_z, p.rs_z, gz, wz, bb, epi, stream, nullptr, ColumnOut(), list);
+  return run_column_pass(column_pass(d_records, p.nz_z, p.rs_z, gz, wz, bb, epi, stream), w3 ? q16_quantum(w3, 3) : Quantum(), 2,
+                         p.q16, Fp32Leg::wave);
 }
 
 // ---- slab records of 16-bit values ---------------------------------------------------------------------------------------
@@ -341,12 +332,10 @@ static int shard_z_records(float *d_records, int64_t sx, int64_t sy_local, int64
 // caller zeroes and reads; it accumulates over calls) and leaves their rows unspecified -- a caller that finds it non-zero
 // repeats the step with the fp32 records above (edt/distributed.py does).
 static bool records16_common_ok(int64_t sx, float wx, float wy, float wz) {
-  if (sx % 4 != 0 || (debug_mode() & (16 | 64 | 0x2000 | 0x4000 | 0x8000 | 0x10000 | 0x100000 | 0x8000000 | 0x10000000))) return false;
+  if (sx % 4 != 0 || (debug_mode() & (kDbgQ16Off | kDbgFp32PassX | kDbgNoQ16 | kDbgFp32Plane))) return false;
   if (!row_codes_exact(wx, sx)) return false;
   const float w3[3] = {wx, wy, wz};
-  float q = 1.0f;
-  uint32_t a[3];
-  return q16_quantum(w3, 3, &q, a);
+  return q16_quantum(w3, 3).ok;
 }
 // the XY phase of a slab of sz_local slices / the Z phase of a slab of sy_local rows: the scan axis on the integer kernel
 static bool records16_xy_ok(int dtype, int64_t sx, int64_t sy, int64_t sz_local, float wx, float wy, float wz) {
@@ -381,44 +370,18 @@ int edt_hip_shard_xy_records16_device(const void *d_labels, const void *d_halo, 
   { float w1 = 1.0f; if ((rc = check_voxel_sizes(2, wx, wy, w1)) != EDT_OK) return rc; }
   if (sx == 0 || sy == 0 || sz_local == 0) return EDT_OK;
   if (!d_labels || !y_splits || !d_blocks || !d_refused || nparts < 1) { set_error("null argument"); return EDT_ERR_BAD_ARG; }
-  if (y_splits[0] != 0 || y_splits[nparts] != sy) { set_error("y_splits must run from 0 to sy"); return EDT_ERR_BAD_ARG; }
-  for (int h = 0; h < nparts; ++h) {
-    if (y_splits[h + 1] <= y_splits[h] || (y_splits[h] % kBandRows) != 0) {
-      set_error("y_splits must be increasing multiples of 32 (the last one is sy)");
-      return EDT_ERR_BAD_ARG;
-    }
-    // (4-byte stores of packed pairs and bit words; the Z phase reads 8 bytes at a time: records are an even number of words)
-    if (!d_blocks[h] || (reinterpret_cast<uintptr_t>(d_blocks[h]) % 8) != 0) {
-      set_error("destination blocks must be non-null and 8-byte aligned");
-      return EDT_ERR_BAD_ARG;
-    }
-  }
+  if ((rc = check_y_splits(nparts, y_splits, d_blocks, sy, 8)) != EDT_OK) return rc;
   const float w3[3] = {wx, wy, wz};
-  float q = 1.0f;
-  uint32_t a[3];
+  const Quantum Q = q16_quantum(w3, 3);
   AxisGeom gy = make_geom_y(sx, sy, sz_local);
-  if (!records16_xy_ok(dtype, sx, sy, sz_local, wx, wy, wz) || !q16_quantum(w3, 3, &q, a)) {
+  if (!records16_xy_ok(dtype, sx, sy, sz_local, wx, wy, wz) || !Q.ok) {
     set_error("16-bit slab records do not apply to these extents / voxel sizes (edt_hip_shard_records16_supported)");
     return EDT_ERR_UNSUPPORTED;
   }
   RecordPlan p = make_record_plan(sx, sy, sz_local, d_workspace);
-  if (!d_workspace || workspace_bytes < p.bytes) {
-    set_error("shard workspace too small: need " + std::to_string(p.bytes) + " bytes");
-    return EDT_ERR_BAD_ARG;
-  }
+  if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
-  // destination map in 4-byte words: a record = ylen * sx / 2 words of 16-bit pairs, then the two bit planes
-  BandScatter sc;
-  for (int b = 0, h = 0; b < BandScatter::kBands; ++b) {
-    if (b >= gy.nbands) { sc.rows[b] = nullptr; sc.bits[b] = nullptr; sc.ostride[b] = 0; sc.plane[b] = 0; continue; }
-    while ((int64_t)b * kBandRows >= y_splits[h + 1]) ++h;
-    const int64_t ys = y_splits[h], ylen = y_splits[h + 1] - ys, words = ceil_div(ylen, kBandRows);
-    float *blk = static_cast<float *>(d_blocks[h]);
-    sc.rows[b] = blk + (((int64_t)b * kBandRows - ys) * sx) / 2;
-    sc.bits[b] = reinterpret_cast<uint32_t *>(blk + ylen * sx / 2) + ((int64_t)b - ys / kBandRows) * sx;
-    sc.ostride[b] = record16_words(sx, ylen);
-    sc.plane[b] = words * sx;
-  }
+  const BandScatter sc = make_band_scatter(gy, y_splits, d_blocks, true);
   uint16_t *codes = reinterpret_cast<uint16_t *>(p.F);
   {
     ScopedPass t("x_pass", stream);
@@ -432,8 +395,16 @@ int edt_hip_shard_xy_records16_device(const void *d_labels, const void *d_halo, 
     if (rc != EDT_OK) return rc;
   }
   ScopedPass t("y_pass", stream);
-  // (plane: any non-null value selects the 16-bit output; the destinations are the table's)
-  return launch_column_pass_q16(p.F, codes, p.ys_y, gy, q, a[1], a[0], bb, 0, d_refused, nullptr, stream, p.table, codes);
+  ColumnPass cp = column_pass(p.F, p.nz_y, p.ys_y, gy, wy, bb, 0, stream);
+  cp.codes = codes;
+  cp.wx = wx;
+  cp.scatter = p.table;
+  cp.plane = codes;  // (any non-null value selects the 16-bit output; the destinations are the table's)
+  HandOver refused;  // (the caller's counter, which it zeroes and reads; no id array: the tiles are only counted)
+  refused.counts = d_refused;
+  refused.slots = 1;
+  refused.zeroed = true;
+  return run_column_pass(cp, Q, 1, refused, Fp32Leg::wave);
 }
 
 int edt_hip_shard_z_records16_device(const void *d_records, float *d_out, int64_t sx, int64_t sy_local, int64_t sz, float wx,
@@ -445,22 +416,18 @@ int edt_hip_shard_z_records16_device(const void *d_records, float *d_out, int64_
   if (sx == 0 || sy_local == 0 || sz == 0) return EDT_OK;
   if (!d_records || !d_out) { set_error("null device pointer"); return EDT_ERR_BAD_ARG; }
   const float w3[3] = {wx, wy, wz};
-  float q = 1.0f;
-  uint32_t a[3];
+  const Quantum Q = q16_quantum(w3, 3);
   AxisGeom gz = make_geom_z(sx, sy_local, sz);  // the dense output: z-columns one (sy_local, sx) slice apart
   gz.fmin = edt_hip_field_floor(wx, wy);
-  if (!records16_z_ok(sx, sy_local, sz, wx, wy, wz) || !q16_quantum(w3, 3, &q, a) ||
+  if (!records16_z_ok(sx, sy_local, sz, wx, wy, wz) || !Q.ok ||
       ((reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_out)) % 16) != 0) {
     set_error("16-bit slab records do not apply to these extents / voxel sizes (edt_hip_shard_records16_supported)");
     return EDT_ERR_UNSUPPORTED;
   }
   RecordPlan p = make_record_plan(sx, sy_local, sz, d_workspace);
-  if (!d_workspace || workspace_bytes < p.bytes) {
-    set_error("shard workspace too small: need " + std::to_string(p.bytes) + " bytes");
-    return EDT_ERR_BAD_ARG;
-  }
+  if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
-  const int epi = (bb ? 0 : kEpiToInf) | ((flags & EDT_FLAG_SQRT) ? kEpiSqrt : 0) | kEpiStream;  // (the Z phase writes the call's results)
+  const int epi = last_pass_epi(bb, (flags & EDT_FLAG_SQRT) != 0);  // (the Z phase writes the call's results)
   const int64_t rec = record16_words(sx, sy_local), words = ceil_div(sy_local, kBandRows);
   const uint32_t *base = static_cast<const uint32_t *>(d_records);
   const uint32_t *nz_y = base + sy_local * sx / 2;
@@ -472,17 +439,17 @@ int edt_hip_shard_z_records16_device(const void *d_records, float *d_out, int64_
   ScopedPass t("z_pass", stream);
   // every row out of the records (16-bit elements: consecutive z are 2 * rec of them apart), results to the dense array; a
   // tile beyond THIS pass's limits gets its rows written there as fp32 values and goes to the fp32 kernel, in place
-  EDT_HIP_TRY(hipMemsetAsync(p.q16_counts, 0, 4 * sizeof(uint32_t), stream));
-  const int map_words = (int)ceil_div(sz, 32);
-  EDT_HIP_TRY(hipMemsetAsync(p.ones_map, 0xFF, (size_t)(ceil_div(sx, 32) * map_words) * sizeof(uint32_t), stream));
-  uint16_t *plane = reinterpret_cast<uint16_t *>(const_cast<void *>(d_records));
-  rc = launch_column_pass_q16(d_out, nullptr, p.rs_z, gz, q, a[2], a[0], bb, epi, p.q16_counts, p.q16_ids, stream, nullptr, plane,
-                              p.ones_map, map_words, nullptr, 2 * rec, sx);
-  if (rc != EDT_OK) return rc;
-  TileList list;
-  list.count = p.q16_counts;
-  list.ids = p.q16_ids;
-  return launch_column_pass_wave(d_out, p.nz_z, p.rs_z, gz, wz, bb, epi, stream, nullptr, ColumnOut(), list);
+  ColumnPass cp = column_pass(d_out, p.nz_z, p.rs_z, gz, wz, bb, epi, stream);
+  cp.plane = reinterpret_cast<uint16_t *>(const_cast<void *>(d_records));
+  cp.map = p.ones_map;
+  cp.map_words = (int)ceil_div(sz, 32);
+  cp.plane_stride = 2 * rec;
+  cp.plane_outer = sx;
+  EDT_HIP_TRY(hipMemsetAsync(p.ones_map, 0xFF, (size_t)(ceil_div(sx, 32) * cp.map_words) * sizeof(uint32_t), stream));
+  TileList served;
+  rc = run_column_pass(cp, Q, 2, p.q16, Fp32Leg::wave, false, &served);
+  if (rc == EDT_OK && served.count == nullptr) { set_error("internal: the Z phase of 16-bit records left the integer kernel"); return EDT_ERR_HIP; }
+  return rc;
 }
 
 }  // extern "C"

@@ -6,8 +6,7 @@
 // 0x01 / 0x04 / 0x10 clear) becomes a background half-voxel, transform that volume at half
 // the voxel size with the ordinary pipeline, keep every other sample.  Expand and gather
 // are two streaming kernels around edt_hip_edtsq_device.
-#include "edt_common.h"
-#include "edt_kernels.h"
+#include "edt_api_internal.h"  // Carver
 
 namespace edt_amd {
 
@@ -463,19 +462,33 @@ bool vg_native_supported(int ndim, int64_t sx, int64_t sy, int64_t sz) {
   return true;
 }
 
-size_t vg_native_workspace_bytes(int ndim, int64_t sx, int64_t sy, int64_t sz) {
-  const int64_t Y2 = 2 * sy, Z2 = ndim == 3 ? 2 * sz : 1;
-  size_t b = align_up((size_t)(sx * Y2 * Z2) * sizeof(float), 256);
-  b += 2 * align_up((size_t)(sx * ceil_div(Y2, kBandRows) * Z2) * sizeof(uint32_t), 256);
-  if (ndim == 3) b += 2 * align_up((size_t)(sx * ceil_div(Z2, kBandRows) * sy) * sizeof(uint32_t), 256);
-  b += align_up((size_t)(2 * sx + 4) * sizeof(float), 256);
-  // hand-over list of the integer column kernel (edt_colq16.hip): two counters + the tile ids of the larger pass
-  b += align_up(8 * sizeof(uint32_t), 256);
-  b += align_up((size_t)(ceil_div(sx, 16) * (ceil_div(std::max<int64_t>(Z2, sy), 8) * 8)) * sizeof(uint32_t), 256);
-  return b + 256;
-}
+// the workspace of the native form (base == nullptr: its size only)
+struct VgWorkspace {
+  float *F1, *ttab;
+  uint32_t *nzY, *rsY, *nzZ = nullptr, *rsZ = nullptr;
+  HandOver q16;  // hand-over list of the integer column kernel (edt_colq16.hip): two counters + the tile ids of the larger pass
+  size_t bytes;
+  VgWorkspace(void *base, int ndim, int64_t sx, int64_t sy, int64_t sz) {
+    const int64_t Y2 = 2 * sy, Z2 = ndim == 3 ? 2 * sz : 1;
+    Carver c(base);
+    F1 = c.take<float>((size_t)(sx * Y2 * Z2));
+    nzY = c.take<uint32_t>((size_t)(sx * ceil_div(Y2, kBandRows) * Z2));
+    rsY = c.take<uint32_t>((size_t)(sx * ceil_div(Y2, kBandRows) * Z2));
+    if (ndim == 3) {
+      nzZ = c.take<uint32_t>((size_t)(sx * ceil_div(Z2, kBandRows) * sy));
+      rsZ = c.take<uint32_t>((size_t)(sx * ceil_div(Z2, kBandRows) * sy));
+    }
+    ttab = c.take<float>((size_t)(2 * sx + 4));
+    q16.slots = 8;
+    q16.counts = c.take<uint32_t>(8);
+    q16.capacity = HandOver::ids_of(sx, std::max<int64_t>(Z2, sy));
+    q16.ids = c.take<uint32_t>((size_t)q16.capacity);
+    bytes = align_up(c.off, 256) + 256;
+  }
+};
+size_t vg_native_workspace_bytes(int ndim, int64_t sx, int64_t sy, int64_t sz) { return VgWorkspace(nullptr, ndim, sx, sy, sz).bytes; }
 
-static bool g_vg_debug_gather() { return (debug_mode() & 0x200000) != 0; }
+static bool g_vg_debug_gather() { return (debug_mode() & kDbgVgGather) != 0; }
 
 template <typename T>
 static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int64_t sx, int64_t sy, int64_t sz,
@@ -483,19 +496,9 @@ static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int6
   const T *labels = static_cast<const T *>(labels_);
   const int64_t Y2 = 2 * sy, Z2 = ndim == 3 ? 2 * sz : 1;
   const int64_t nbY = ceil_div(Y2, kBandRows), nbZ = ceil_div(Z2, kBandRows);
-  char *p = static_cast<char *>(ws);
-  auto take = [&](size_t bytes) { char *q = p; p += align_up(bytes, 256); return q; };
-  float *F1 = reinterpret_cast<float *>(take((size_t)(sx * Y2 * Z2) * sizeof(float)));
-  uint32_t *nzY = reinterpret_cast<uint32_t *>(take((size_t)(sx * nbY * Z2) * sizeof(uint32_t)));
-  uint32_t *rsY = reinterpret_cast<uint32_t *>(take((size_t)(sx * nbY * Z2) * sizeof(uint32_t)));
-  uint32_t *nzZ = nullptr, *rsZ = nullptr;
-  if (ndim == 3) {
-    nzZ = reinterpret_cast<uint32_t *>(take((size_t)(sx * nbZ * sy) * sizeof(uint32_t)));
-    rsZ = reinterpret_cast<uint32_t *>(take((size_t)(sx * nbZ * sy) * sizeof(uint32_t)));
-  }
-  float *ttab = reinterpret_cast<float *>(take((size_t)(2 * sx + 4) * sizeof(float)));
-  uint32_t *q16_counts = reinterpret_cast<uint32_t *>(take(8 * sizeof(uint32_t)));
-  uint32_t *q16_ids = reinterpret_cast<uint32_t *>(take((size_t)(ceil_div(sx, 16) * (ceil_div(std::max<int64_t>(Z2, sy), 8) * 8)) * sizeof(uint32_t)));
+  VgWorkspace W(ws, ndim, sx, sy, sz);
+  float *const F1 = W.F1, *const ttab = W.ttab;
+  uint32_t *const nzY = W.nzY, *const rsY = W.rsY, *const nzZ = W.nzZ, *const rsZ = W.rsZ;
   const int idx_inf = (int)(2 * sx + 2);
   // half voxel size on the doubled grid (src/edt_voxel_graph.hpp:96-101, :189-193)
   const float hx = wx / 2, hy = wy / 2, hz = wz / 2;
@@ -505,7 +508,7 @@ static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int6
   // allocation; the Y pass reads them and writes its even rows -- all the Z pass reads -- compactly into the FIRST half
   // ([z2][y][x], one row per voxel row).  (debug bits 0x100000 / 0x200000: the fp32 form / the separate gather pass.)
   const bool index_form = exact && ndim == 3 && sx % 4 == 0 && idx_inf < 0xFFFF && !g_vg_debug_gather() &&
-                          !(debug_mode() & (0x100000 | 64));
+                          !(debug_mode() & (kDbgFp32PassX | kDbgTiledColumns));
   uint16_t *codes = index_form ? reinterpret_cast<uint16_t *>(F1 + sx * sy * Z2) : nullptr;
   {
     const int64_t nvrows = sy * (ndim == 3 ? sz : 1);  // one wave per voxel row (its 2 or 4 doubled rows)
@@ -530,7 +533,7 @@ static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int6
                        (int)sx, (int)sy, (int)(ndim == 3 ? sz : 1), (int)Y2, ndim == 3 ? 1 : 0, (int)nbY, bb);
   }
   EDT_HIP_TRY(hipGetLastError());
-  const int last_epi = (bb ? 0 : kEpiToInf) | (want_sqrt ? kEpiSqrt : 0) | kEpiStream;  // (the last pass writes the call's results: streamed)
+  const int last_epi = last_pass_epi(bb, want_sqrt != 0);
   AxisGeom gy;
   gy.sx = sx; gy.n = Y2; gy.stride = sx; gy.nouter = Z2; gy.outer_stride = sx * Y2; gy.nbands = nbY;
   // Only the even rows of the doubled columns are read again: by the z pass (in place), or -- last pass -- by the
@@ -544,35 +547,24 @@ static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int6
   if (g_vg_debug_gather()) last = even;     // (diagnostics: debug bit 0x200000 keeps the separate gather pass)
   // The integer column kernel (edt_colq16.hip, output stride 2) where the half voxel sizes share a quantum and pass X left exact
   // multiples; the tiles it refuses go to the fp32 kernel through the list, as everywhere.
-  float q16_q = 1.0f;
-  uint32_t q16_a[3] = {1u, 1u, 1u};
-  bool q16 = false;
-  {
-    const float h3[3] = {hx, hy, hz};
-    q16 = exact && !(debug_mode() & (16 | 64 | 0x2000 | 0x4000 | 0x8000 | 0x10000 | 0x40000)) && q16_quantum(h3, ndim, &q16_q, q16_a) &&
-          (reinterpret_cast<uintptr_t>(out) % 8) == 0;
-    if (q16) EDT_HIP_TRY(hipMemsetAsync(q16_counts, 0, 8 * sizeof(uint32_t), stream));
-  }
+  const float h3[3] = {hx, hy, hz};
+  Quantum Q = q16_quantum(h3, ndim);
+  Q.ok = Q.ok && exact && !(debug_mode() & (kDbgQ16Off | kDbgEveryRow)) && (reinterpret_cast<uintptr_t>(out) % 8) == 0;
+  if (Q.ok && W.q16.zero(stream) != EDT_OK) return EDT_ERR_HIP;
   // in16 != nullptr: the pass reads pass X as 16-bit indices (and writes compactly: co.compact)
-  auto column_pass = [&](const uint16_t *in16, const uint32_t *nzp, const uint32_t *rsp, const AxisGeom &g, float h, int axis, int epi,
-                         const ColumnOut &co, uint32_t *count) -> int {
-    TileList list;
-    if (q16 && column_pass_q16_supported(g) && column_pass_wave_supported(g) && column_pass_q16_aligned(F1, in16, nullptr, co.compact)) {
-      const int r = launch_column_pass_q16(F1, in16, rsp, g, q16_q, q16_a[axis], q16_a[0], bb, epi, count, q16_ids, stream, nullptr,
-                                           nullptr, nullptr, 0, &co);
-      if (r != EDT_OK) return r;
-      list.count = count;
-      list.ids = q16_ids;
-    }
-    if (in16 != nullptr)
-      return launch_column_pass_wave_codes(F1, in16, nzp, rsp, g, h, bb, epi, hx, bb ? 0 : 1, stream, nullptr, list, co);
-    return launch_column_pass_wave(F1, nzp, rsp, g, h, bb, epi, stream, nullptr, co, list);
+  auto column = [&](const uint16_t *in16, const uint32_t *nzp, const uint32_t *rsp, const AxisGeom &g, float h, int epi, const ColumnOut &co) {
+    ColumnPass cp = column_pass(F1, nzp, rsp, g, h, bb, epi, stream);
+    cp.codes = in16;
+    cp.wx = hx;
+    cp.out = co;
+    return cp;
   };
   ColumnOut ycompact = even;  // index form: the even rows of the Y pass, one per voxel row, in the first half of F1
   ycompact.compact = F1;
   ycompact.outer = sx * sy;
   ycompact.row2 = sx;
-  int rc = column_pass(codes, nzY, rsY, gy, hy, 1, ndim == 2 ? last_epi : 0, index_form ? ycompact : (ndim == 2 ? last : even), q16_counts);
+  int rc = run_column_pass(column(codes, nzY, rsY, gy, hy, ndim == 2 ? last_epi : 0, index_form ? ycompact : (ndim == 2 ? last : even)), Q, 1,
+                           W.q16, Fp32Leg::wave);
   if (rc != EDT_OK) return rc;
   if (ndim == 3) {
     const int64_t total = sx * nbZ * sy;
@@ -584,7 +576,7 @@ static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int6
     AxisGeom gz;  // the even rows only: outer index = y, two doubled rows apart (index form: the compact rows of the Y pass)
     gz.sx = sx; gz.n = Z2; gz.stride = sx * Y2; gz.nouter = sy; gz.outer_stride = 2 * sx; gz.nbands = nbZ;
     if (index_form) { gz.stride = sx * sy; gz.outer_stride = sx; }
-    rc = column_pass(nullptr, nzZ, rsZ, gz, hz, 2, last_epi, last, q16_counts + 1);
+    rc = run_column_pass(column(nullptr, nzZ, rsZ, gz, hz, last_epi, last), Q, 2, W.q16, Fp32Leg::wave);
     if (rc != EDT_OK) return rc;
   }
   if (last.compact != nullptr) return EDT_OK;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised CPU parity of passes Y and Z of whole 3-D volumes through the integer kernel's lane logic (tests/q16_emul.cpp, the
-header the HIP kernel is built from) against the oracle, with the host's proof "no tile can be refused" (csrc/edt_api.hip:
-q16_cannot_refuse, restated in tests/test_q16_logic.py) checked on every case.  No GPU.  Test infrastructure, not collected by
+header the HIP kernel is built from) against the oracle, with the host's proof "no tile can be refused" (csrc/edt_colq16.hip:
+q16_no_refusals, restated in tests/test_q16_logic.py) checked on every case.  No GPU.  Test infrastructure, not collected by
 pytest (minutes per seed).  usage: python tests/fuzz_q16_chain.py <seed> <ncases>   (run tests/test_q16_logic.py once before: it
 builds tests/_build/libq16_emul.so)"""
 import sys, os

@@ -457,7 +457,7 @@ def test_quantum_of_voxel_sizes(q16):
 
 
 def host_cannot_refuse(a, q, shape_xyz, bb):
-    """csrc/edt_api.hip: q16_cannot_refuse, restated -- (pass Y, pass Z): the host's proof that the integer kernel refuses no
+    """csrc/edt_colq16.hip: q16_no_refusals, restated -- (pass Y, pass Z): the host's proof that the integer kernel refuses no
     tile of the pass, on which it skips the fp32 launch over the hand-over list"""
     sx, sy, sz = shape_xyz
     kmax = (sx + 1) // 2 if bb else sx
