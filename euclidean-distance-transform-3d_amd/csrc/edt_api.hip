@@ -206,17 +206,6 @@ static Plan make_plan(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, v
   return p;
 }
 
-// Pass 1 with the bit planes of the column passes as a by-product: the register-resident wave kernel for rows of up
-// to 4096 voxels (one, two or four waves per row), the LDS-staged workgroup kernel (rows of up to 2048 voxels) where
-// that one does not apply.  (debug bit 32 forces the latter.)
-int launch_row_bits(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                           uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                           int to_finite, hipStream_t stream) {
-  if (row_pass_wave_supported(dtype, sx, sy, sz) && !(g_debug_mode & kDbgTiledRows))
-    return launch_row_pass_wave(dtype, labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream);
-  return launch_row_pass_tiled(dtype, labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream);
-}
-
 bool env_force_generic() {
   const char *e = std::getenv("EDT_HIP_FORCE_GENERIC");  // test hook: every call takes the fallback kernels
   return e && e[0] == '1';
@@ -348,10 +337,12 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
     return cp;
   };
 
-  if (ndim == 1) {
-    ScopedPass t("x_pass", stream);
-    if (force_generic_1d(flags) || line_without_ws) return launch_row_pass_serial(dtype, d_labels, d_out, sx, 1, wx, bb, 0, want_sqrt, stream);
-    return launch_line_pass(dtype, d_labels, d_out, sx, wx, bb, want_sqrt, d_ws, stream);
+  // pass X of this call: the whole volume into the field at `out` (the index form below works slab by slab)
+  RowPass rp = row_pass(dtype, d_labels, sx, sy, sz, wx, bb, stream);
+
+  if (ndim == 1) {  // (pass X is the call's last pass; one thread for the whole line only where forced, or without scratch)
+    rp.out = d_out; rp.last = true; rp.last_sqrt = want_sqrt != 0;
+    return run_row_pass(rp, false, (force_generic_1d(flags) || line_without_ws) ? nullptr : d_ws, true);
   }
 
   // Column passes are in place when the LDS-tiled kernel applies, otherwise they ping-pong
@@ -363,7 +354,7 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
   float *cur = (swaps % 2 == 0) ? d_out : p.bufB;
   float *other = (cur == d_out) ? p.bufB : d_out;
   // (pass 1 on the row kernels: the wave kernel up to 4096 voxels per row, the workgroup-phased one up to 2048)
-  const bool tiled_x = !force_generic && (row_pass_tiled_supported(sx) || row_pass_wave_supported(dtype, sx, sy, sz));
+  const bool tiled_x = row_pass_on_row_kernels(dtype, sx, sy, sz, force_generic);
   // Index form of pass 1 (see plan_code_slab): pass 1 stores 16-bit distance indices, the first column pass turns
   // them into F while it fills its tile -- 2 B less written and 2 B less read per voxel.  Bit-identical only where
   // every multiple k * wx of the row is exact in fp32 (row_codes_exact); other voxel sizes keep the fp32 form.
@@ -403,10 +394,11 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
       {
         // (slice 0 of a later slab compares against the slice below it through the halo pointer of the sharded path)
         ScopedPass t(one ? "x_pass" : nullptr, stream);
-        rc = launch_row_pass_wave(dtype, lab, nullptr, nzy ? nzy + z0 * wpl : nullptr, p.rs_y + z0 * wpl,
-                                  zpass ? p.zs_y + z0 * wpl : nullptr, sx, sy, zc, wx, bb, bb ? 0 : 1, stream,
-                                  z0 > 0 ? lab - (size_t)sxy * lsz : nullptr, slab_codes, zero_label, p.code_pitch);
-        if (rc != EDT_OK) return rc;
+        RowPass slab = rp;
+        slab.labels = lab; slab.halo = z0 > 0 ? lab - (size_t)sxy * lsz : nullptr; slab.sz = zc;
+        slab.nz_y = nzy ? nzy + z0 * wpl : nullptr; slab.ys_y = p.rs_y + z0 * wpl; slab.zs_y = zpass ? p.zs_y + z0 * wpl : nullptr;
+        slab.codes = slab_codes; slab.codes_pitch = p.code_pitch; slab.zero_label = zero_label;
+        if ((rc = launch_row_pass_wave(slab)) != EDT_OK) return rc;
         if (binary_yz) {
           AxisGeom gb = p.gy;
           gb.nouter = zc;
@@ -434,36 +426,12 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
         if (q16_only && !served.none) { set_error("internal: pass Y left the integer kernel"); return EDT_ERR_HIP; }
       }
     }
-  } else if (tiled_x) {
-    // labels are read once: pass 1 also emits the run bit-planes of the y and z axes
-    {
-      ScopedPass t("x_pass", stream);
-      if (signed_tf)  // (signed_transform_supported: the register kernel of pass X serves this shape)
-        rc = launch_row_pass_wave(dtype, d_labels, cur, p.nz_y, p.rs_y, zpass ? p.zs_y : nullptr, sx, sy, sz, wx, bb, bb ? 0 : 1,
-                                  stream, nullptr, nullptr, 1);
-      else
-        rc = launch_row_bits(dtype, d_labels, cur, p.nz_y, p.rs_y, zpass ? p.zs_y : nullptr, sx, sy, sz,
-                             wx, bb, bb ? 0 : 1, stream);
-      if (rc != EDT_OK) return rc;
-      if (binary_yz) rc = launch_planes_one_run(p.nz_y, p.rs_y, zpass ? p.zs_y : nullptr, p.gy, 0, stream);
-      if (rc != EDT_OK) return rc;
-    }
   } else {
-    {
-      ScopedPass t("x_pass", stream);
-      // rows of more than 2048 voxels: one thread per VOXEL through the line pipeline (edt_line.hip); the
-      // thread-per-row kernel stays behind EDT_FLAG_FORCE_GENERIC as the cross-check it is
-      if (p.line_ws != nullptr) rc = launch_rows_line_pass(dtype, d_labels, cur, sx, sy * sz, wx, bb, bb ? 0 : 1, p.line_ws, stream);
-      else rc = launch_row_pass_serial(dtype, d_labels, cur, sx, sy * sz, wx, bb, bb ? 0 : 1, 0, stream);
-      if (rc != EDT_OK) return rc;
-    }
-    {
-      ScopedPass t("y_bits", stream);
-      rc = launch_axis_bits(dtype, d_labels, nullptr, p.nz_y, p.rs_y, p.gy, stream);
-      if (rc != EDT_OK) return rc;
-      if (binary_yz) rc = launch_planes_one_run(p.nz_y, p.rs_y, nullptr, p.gy, 0, stream);
-      if (rc != EDT_OK) return rc;
-    }
+    // (the signed form -- signed_transform_supported: the register kernel of pass X serves this shape -- measures label 0 too)
+    rp.out = cur; rp.nz_y = p.nz_y; rp.ys_y = p.rs_y; rp.zs_y = (zpass && tiled_x) ? p.zs_y : nullptr; rp.zero_label = signed_tf;
+    if ((rc = run_row_pass(rp, tiled_x, p.line_ws, true)) != EDT_OK) return rc;
+    if (binary_yz) rc = launch_planes_one_run(p.nz_y, p.rs_y, rp.zs_y, p.gy, 0, stream);
+    if (rc != EDT_OK) return rc;
   }
   if (!index_form) {
     ScopedPass t("y_pass", stream);

@@ -1,5 +1,6 @@
-// edt_api_internal.h -- what the three translation units of the C ABI share (edt_api.hip: plan + dispatch on device-resident
-// data; edt_host.hip: host-buffer staging; edt_shard_api.hip: the Z-sharded phases).  Internal: nothing here is exported.
+// edt_api_internal.h -- what the three translation units of the C ABI share: edt_api.hip (plan + dispatch on device-resident
+// data), edt_host.hip (host-buffer staging) and edt_shard_api.hip (the Z-sharded phases).  The pass-X driver, edt_rowpass.hip,
+// includes it too, for ScopedPass and make_geom_y.  Internal: nothing here is exported.
 #pragma once
 
 #include <algorithm>
@@ -31,8 +32,6 @@ struct Carver {
 
 AxisGeom make_geom_y(int64_t sx, int64_t sy, int64_t sz);
 AxisGeom make_geom_z(int64_t sx, int64_t sy, int64_t sz);
-int launch_row_bits(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y, uint32_t *zs_y, int64_t sx,
-                    int64_t sy, int64_t sz, float w, int bb, int to_finite, hipStream_t stream);
 bool env_force_generic();  // EDT_HIP_FORCE_GENERIC=1: every call takes the fallback kernels (test hook)
 int check_shape(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
 int check_voxel_sizes(int naxes, float &wx, float &wy, float &wz);  // (drops the sign of wy / wz: they enter as squares)

@@ -113,6 +113,22 @@ inline int dtype_size(int dtype) {
   }
 }
 
+// The label type of a dtype code, handed to `f` as a tag: f(LabelType<T>{}) -> int.  The one place that knows which codes
+// exist and that EDT_BOOL is read like EDT_U8.  Use:  with_label_type(dtype, [&](auto t) { using T = typename decltype(t)::type; ... });
+template <typename T> struct LabelType { using type = T; };
+template <typename F>
+inline int with_label_type(int dtype, F &&f) {
+  switch (dtype) {
+    case EDT_U8: case EDT_BOOL: return f(LabelType<uint8_t>{});
+    case EDT_U16: return f(LabelType<uint16_t>{});
+    case EDT_U32: return f(LabelType<uint32_t>{});
+    case EDT_U64: return f(LabelType<uint64_t>{});
+    case EDT_F32: return f(LabelType<float>{});
+    case EDT_F64: return f(LabelType<double>{});
+    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
+  }
+}
+
 // Geometry of one separable pass over a volume whose x axis is contiguous.
 //   column c = (x, o):  first voxel at  x + o * outer_stride,  rows `stride` apart.
 //   Y pass: n = sy, stride = sx,    outer = z (nouter = sz, outer_stride = sx*sy)

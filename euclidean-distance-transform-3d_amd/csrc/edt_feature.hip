@@ -496,13 +496,12 @@ int edt_hip_expand_labels_device(const void *d_labels, int dtype, int ndim, int6
     ScopedPass sp("expand mask", s);
     if ((rc = launch_is_background(dtype, d_labels, mask, voxels, s)) != EDT_OK) return rc;
   }
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: return launch_expand_t<uint8_t>(mask, d_labels, d_out, c, b, distance, s);
-    case EDT_U16: return launch_expand_t<uint16_t>(mask, d_labels, d_out, c, b, distance, s);
-    case EDT_U32: case EDT_F32: return launch_expand_t<uint32_t>(mask, d_labels, d_out, c, b, distance, s);
-    case EDT_U64: case EDT_F64: return launch_expand_t<uint64_t>(mask, d_labels, d_out, c, b, distance, s);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
+  return with_label_type(dtype, [&](auto t) {
+    // (labels are only copied: a float label travels as the unsigned integer of its size)
+    using T = typename decltype(t)::type;
+    using U = std::conditional_t<sizeof(T) == 4, uint32_t, std::conditional_t<sizeof(T) == 8, uint64_t, T>>;
+    return launch_expand_t<U>(mask, d_labels, d_out, c, b, distance, s);
+  });
 }
 
 }  // extern "C"

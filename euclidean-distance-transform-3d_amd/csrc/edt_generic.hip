@@ -85,18 +85,11 @@ static int launch_row_serial_t(const void *labels, float *out, int64_t sx, int64
   return EDT_OK;
 }
 
-int launch_row_pass_serial(int dtype, const void *labels, float *out, int64_t sx, int64_t nrows,
-                           float w, int bb, int to_finite, int take_sqrt, hipStream_t stream) {
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL:
-      return launch_row_serial_t<uint8_t>(labels, out, sx, nrows, w, bb, to_finite, take_sqrt, stream);
-    case EDT_U16: return launch_row_serial_t<uint16_t>(labels, out, sx, nrows, w, bb, to_finite, take_sqrt, stream);
-    case EDT_U32: return launch_row_serial_t<uint32_t>(labels, out, sx, nrows, w, bb, to_finite, take_sqrt, stream);
-    case EDT_U64: return launch_row_serial_t<uint64_t>(labels, out, sx, nrows, w, bb, to_finite, take_sqrt, stream);
-    case EDT_F32: return launch_row_serial_t<float>(labels, out, sx, nrows, w, bb, to_finite, take_sqrt, stream);
-    case EDT_F64: return launch_row_serial_t<double>(labels, out, sx, nrows, w, bb, to_finite, take_sqrt, stream);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
+int launch_row_pass_serial(const RowPass &rp) {
+  return with_label_type(rp.dtype, [&](auto t) {
+    return launch_row_serial_t<typename decltype(t)::type>(rp.labels, rp.out, rp.sx, rp.nrows(), rp.w, rp.bb, rp.to_finite(),
+                                                           rp.take_sqrt(), rp.stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------
@@ -151,15 +144,9 @@ static int launch_bits_t(const void *labels, const void *halo, uint32_t *nz, uin
 
 int launch_axis_bits(int dtype, const void *labels, const void *halo, uint32_t *nz, uint32_t *rs,
                      const AxisGeom &g, hipStream_t stream) {
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: return launch_bits_t<uint8_t>(labels, halo, nz, rs, g, stream);
-    case EDT_U16: return launch_bits_t<uint16_t>(labels, halo, nz, rs, g, stream);
-    case EDT_U32: return launch_bits_t<uint32_t>(labels, halo, nz, rs, g, stream);
-    case EDT_U64: return launch_bits_t<uint64_t>(labels, halo, nz, rs, g, stream);
-    case EDT_F32: return launch_bits_t<float>(labels, halo, nz, rs, g, stream);
-    case EDT_F64: return launch_bits_t<double>(labels, halo, nz, rs, g, stream);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
+  return with_label_type(dtype, [&](auto t) {
+    return launch_bits_t<typename decltype(t)::type>(labels, halo, nz, rs, g, stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------
@@ -374,21 +361,12 @@ int launch_negate_background(int dtype, const void *labels, float *f, int64_t co
   const int threads = 256;
   int64_t blocks = ceil_div(ceil_div(count, 4), threads);
   if (blocks > 16384) blocks = 16384;
-#define LAUNCH_NB(T)                                                                              \
-  hipLaunchKernelGGL(k_negate_background<T>, dim3((unsigned)blocks), dim3(threads), 0, stream,   \
-                     (const T *)labels, f, count)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: LAUNCH_NB(uint8_t); break;
-    case EDT_U16: LAUNCH_NB(uint16_t); break;
-    case EDT_U32: LAUNCH_NB(uint32_t); break;
-    case EDT_U64: LAUNCH_NB(uint64_t); break;
-    case EDT_F32: LAUNCH_NB(float); break;
-    case EDT_F64: LAUNCH_NB(double); break;
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef LAUNCH_NB
-  EDT_HIP_TRY(hipGetLastError());
-  return EDT_OK;
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(k_negate_background<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, f, count);
+    EDT_HIP_TRY(hipGetLastError());
+    return EDT_OK;
+  });
 }
 
 template <typename T>
@@ -405,21 +383,12 @@ int launch_is_background(int dtype, const void *labels, uint8_t *mask, int64_t c
   const int threads = 256;
   int64_t blocks = ceil_div(count, threads);
   if (blocks > 8192) blocks = 8192;
-#define LAUNCH_BG(T)                                                                          \
-  hipLaunchKernelGGL(k_is_background<T>, dim3((unsigned)blocks), dim3(threads), 0, stream,    \
-                     (const T *)labels, mask, count)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: LAUNCH_BG(uint8_t); break;
-    case EDT_U16: LAUNCH_BG(uint16_t); break;
-    case EDT_U32: LAUNCH_BG(uint32_t); break;
-    case EDT_U64: LAUNCH_BG(uint64_t); break;
-    case EDT_F32: LAUNCH_BG(float); break;
-    case EDT_F64: LAUNCH_BG(double); break;
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef LAUNCH_BG
-  EDT_HIP_TRY(hipGetLastError());
-  return EDT_OK;
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(k_is_background<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, mask, count);
+    EDT_HIP_TRY(hipGetLastError());
+    return EDT_OK;
+  });
 }
 
 // each(): the distance transform restricted to ONE label (src/edt.pyx:950-994 builds this image on
@@ -451,21 +420,12 @@ int launch_select_label(int dtype, const void *labels, const float *dt, float *o
   const int threads = 256;
   int64_t blocks = ceil_div(ceil_div(count, 4), threads);
   if (blocks > 16384) blocks = 16384;
-#define LAUNCH_SEL(T)                                                                         \
-  hipLaunchKernelGGL(k_select_label<T>, dim3((unsigned)blocks), dim3(threads), 0, stream,     \
-                     (const T *)labels, dt, out, *(const T *)key, count)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: LAUNCH_SEL(uint8_t); break;
-    case EDT_U16: LAUNCH_SEL(uint16_t); break;
-    case EDT_U32: LAUNCH_SEL(uint32_t); break;
-    case EDT_U64: LAUNCH_SEL(uint64_t); break;
-    case EDT_F32: LAUNCH_SEL(float); break;
-    case EDT_F64: LAUNCH_SEL(double); break;
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef LAUNCH_SEL
-  EDT_HIP_TRY(hipGetLastError());
-  return EDT_OK;
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(k_select_label<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, dt, out, *(const T *)key, count);
+    EDT_HIP_TRY(hipGetLastError());
+    return EDT_OK;
+  });
 }
 
 }  // namespace edt_amd

@@ -16,10 +16,12 @@ namespace edt_amd {
 // 512^3 uint32 call with fresh allocations, of which 2 x 9.5 ms are PCIe and 0.7 ms kernels).  One
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
+// what a pooled buffer is for -- one slot each, so two roles never share memory within a call
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table */, kSecondField, kSlotCount };
 struct DevicePool {
-  static constexpr int kSlots = 6;
-  void *p[kSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t cap[kSlots] = {0, 0, 0, 0, 0, 0};
+  static constexpr int kSlots = kSlotCount;
+  void *p[kSlots] = {};
+  size_t cap[kSlots] = {};
   std::mutex m;
   void release() {  // (call with the owning device current)
     for (int i = 0; i < kSlots; ++i) {
@@ -41,46 +43,6 @@ static DevicePool *current_pool() {
   return (dev >= 0 && dev < kMaxDevices) ? &g_pools[dev] : nullptr;
 }
 
-struct DeviceBuf {
-  DevicePool *pool;  // nullptr: private allocations only
-  void *p = nullptr;
-  bool owned = false;
-  explicit DeviceBuf(DevicePool *pl) : pool(pl) {}
-  ~DeviceBuf() { if (p && owned) (void)hipFree(p); }
-  // slot < 0 (or no pool): private allocation, freed with the object; otherwise the pool slot is (re)used.
-  // The caller holds pool->m when it uses slots.
-  int alloc(size_t bytes, int slot = -1) {
-    if (bytes == 0) bytes = 256;
-    if (slot >= 0 && pool) {
-      if (pool->cap[slot] < bytes) {
-        if (pool->p[slot]) (void)hipFree(pool->p[slot]);
-        pool->p[slot] = nullptr;
-        pool->cap[slot] = 0;
-        const hipError_t e = hipMalloc(&pool->p[slot], bytes);
-        if (e != hipSuccess) {
-          pool->p[slot] = nullptr;
-          (void)hipGetLastError();
-          pool->release();  // give everything back and let the caller see the failure
-          set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
-          return EDT_ERR_NOMEM;
-        }
-        pool->cap[slot] = bytes;
-      }
-      p = pool->p[slot];
-      owned = false;
-      return EDT_OK;
-    }
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      p = nullptr;
-      set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
-      return EDT_ERR_NOMEM;
-    }
-    owned = true;
-    return EDT_OK;
-  }
-};
-
 static bool pool_enabled() {
   const char *e = std::getenv("EDT_HIP_NO_CACHE");
   return !(e && e[0] == '1');
@@ -93,7 +55,7 @@ static bool pool_enabled() {
 // back then proceeds at PCIe speed.  (Every byte of the buffer is overwritten by the result afterwards.)
 struct Prefault {
   std::vector<std::thread> threads;
-  Prefault(void *buf, size_t bytes) {
+  void start(void *buf, size_t bytes) {
     constexpr size_t kPage = 4096, kMin = size_t(32) << 20;
     const char *off = std::getenv("EDT_HIP_NO_PREFAULT");
     if (bytes < kMin || (off && off[0] == '1')) return;
@@ -131,6 +93,56 @@ struct Prefault {
   ~Prefault() { join(); }
 };
 
+// The device side of one host-buffer call on the current device: the pool decision (EDT_HIP_NO_CACHE=1: private allocations,
+// freed at return), the pool's lock for the whole call, the buffers by role, and the transfers.
+struct Staging {
+  DevicePool *pool = pool_enabled() ? current_pool() : nullptr;
+  std::unique_lock<std::mutex> lock;
+  void *p[kSlotCount] = {};
+  Prefault touch;
+  Staging() { if (pool) lock = std::unique_lock<std::mutex>(pool->m); }
+  ~Staging() {
+    if (!pool) for (void *q : p) if (q) (void)hipFree(q);
+  }
+  template <typename T = void> T *at(Slot s) const { return static_cast<T *>(p[s]); }
+  // the pool's slot grows where it is too small; a failure gives everything back and lets the caller see it
+  int alloc(Slot s, size_t bytes) {
+    if (bytes == 0) bytes = 256;
+    void **q = pool ? &pool->p[s] : &p[s];
+    if (!pool || pool->cap[s] < bytes) {
+      if (*q) (void)hipFree(*q);
+      *q = nullptr;
+      if (pool) pool->cap[s] = 0;
+      const hipError_t e = hipMalloc(q, bytes);
+      if (e != hipSuccess) {
+        *q = nullptr;
+        if (pool) { (void)hipGetLastError(); pool->release(); }
+        set_error(std::string("hipMalloc failed: ") + hipGetErrorString(e));
+        return EDT_ERR_NOMEM;
+      }
+      if (pool) pool->cap[s] = bytes;
+    }
+    p[s] = *q;
+    return EDT_OK;
+  }
+  int alloc(std::initializer_list<std::pair<Slot, size_t>> want) {
+    for (const auto &w : want)
+      if (const int rc = alloc(w.first, w.second)) return rc;
+    return EDT_OK;
+  }
+  int up(Slot s, const void *host, size_t bytes) {
+    EDT_HIP_TRY(hipMemcpy(p[s], host, bytes, hipMemcpyHostToDevice));
+    return EDT_OK;
+  }
+  // the result pages are touched while the labels travel and the kernels run (expect), and read back once they are (down)
+  void expect(void *host, size_t bytes) { touch.start(host, bytes); }
+  int down(void *host, Slot s, size_t bytes, size_t offset = 0) {
+    touch.join();
+    EDT_HIP_TRY(hipMemcpy(host, at<char>(s) + offset, bytes, hipMemcpyDeviceToHost));
+    return EDT_OK;
+  }
+};
+
 // Devices of the one-process multi-GPU route (edt_multi.hip); empty = single device.
 static std::mutex g_devices_mutex;
 static std::vector<int> g_devices = [] {
@@ -148,215 +160,181 @@ static std::vector<int> g_devices = [] {
   return v;
 }();
 
-constexpr int EDT_FLAG_SINGLE_DEVICE = 0x4000;  // internal: do not take the multi-GPU route
-
-// The first device of the list (edt_hip_set_devices / EDT_HIP_DEVICES) for the duration of one host-buffer call that
-// is not sharded; no list: the caller's current device stays.
+// `device` (or, by default, the first device of the list: edt_hip_set_devices / EDT_HIP_DEVICES) for the duration of one
+// host-buffer call that is not sharded; no list: the caller's current device stays.  rc: the switch failed -- the call returns it.
 struct ListedDevice {
-  int prev = -1;
+  int prev = -1, rc = EDT_OK;
   bool switched = false;
-  ListedDevice() {
-    int first = -1;
-    {
-      std::lock_guard<std::mutex> lock(g_devices_mutex);
-      if (!g_devices.empty()) first = g_devices[0];
-    }
-    if (first >= 0 && hipGetDevice(&prev) == hipSuccess && prev != first && hipSetDevice(first) == hipSuccess) switched = true;
+  static int first_listed() {
+    std::lock_guard<std::mutex> lock(g_devices_mutex);
+    return g_devices.empty() ? -1 : g_devices[0];
+  }
+  explicit ListedDevice(int device = first_listed()) {
+    if (device >= 0) rc = enter(device);
+  }
+  int enter(int device) {
+    EDT_HIP_TRY(hipGetDevice(&prev));
+    if (prev == device) return EDT_OK;
+    EDT_HIP_TRY(hipSetDevice(device));
+    switched = true;
+    return EDT_OK;
   }
   ~ListedDevice() {
     if (switched) (void)hipSetDevice(prev);
   }
 };
 
+// What every host-buffer entry point checks before it touches the device, in this order: shape, voxel sizes (w == nullptr: the
+// call has none to check), empty volume (*empty: nothing to do), null pointers, device.  `own(After)`: the checks that belong to
+// one entry point, made where they always were.
+enum class After { shape, voxel_sizes, pointers };
+static int no_own_checks(After) { return EDT_OK; }
+template <typename Own = int (*)(After)>
+static int host_prologue(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float *const *w, bool null_pointer, bool *empty,
+                         Own own = no_own_checks) {
+  *empty = false;
+  int rc = check_shape(dtype, ndim, sx, sy, sz);
+  if (rc != EDT_OK || (rc = own(After::shape)) != EDT_OK) return rc;
+  if (w && (rc = check_voxel_sizes(ndim, *w[0], *w[1], *w[2])) != EDT_OK) return rc;
+  if ((rc = own(After::voxel_sizes)) != EDT_OK) return rc;
+  if (sx * sy * sz == 0) { *empty = true; return EDT_OK; }
+  if (null_pointer) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+  if ((rc = own(After::pointers)) != EDT_OK) return rc;
+  return require_device();
+}
+
+// labels up, the transform on the current device, the field down
+static int run_on_current_device(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                                 float wz, int flags, float *output) {
+  if (env_force_generic()) flags |= EDT_FLAG_FORCE_GENERIC;
+  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype), obytes = (size_t)(sx * sy * sz) * sizeof(float);
+  const size_t wbytes = edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
+  Staging st;
+  int rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}});
+  if (rc != EDT_OK) return rc;
+  st.expect(output, obytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = run_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, flags, st.at<float>(kOut), st.p[kWorkspace], wbytes, nullptr);
+  return rc != EDT_OK ? rc : st.down(output, kOut, obytes);
+}
+
 static int run_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
                     float wx, float wy, float wz, int flags, float *output) {
-  int rc = check_shape(dtype, ndim, sx, sy, sz);
-  if (rc != EDT_OK) return rc;
-  if ((rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
-  const int64_t voxels = sx * sy * sz;
-  if (voxels == 0) return EDT_OK;
-  if (!labels || !output) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-  rc = require_device();
-  if (rc != EDT_OK) return rc;
-  if (env_force_generic()) flags |= EDT_FLAG_FORCE_GENERIC;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  const int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !output, &empty);
+  if (rc != EDT_OK || empty) return rc;
   // The device list (edt_hip_set_devices / EDT_HIP_DEVICES) is honoured by EVERY host-buffer call: a 3-D volume the
   // slab-record form can cut is Z-sharded over the listed devices, everything else (1-D, 2-D, stacks of images, the binary
   // route, the forced generic kernels, volumes that cannot be cut) runs on the FIRST listed device.
-  if (!(flags & EDT_FLAG_SINGLE_DEVICE)) {
-    std::vector<int> devs;
-    {
-      std::lock_guard<std::mutex> lock(g_devices_mutex);
-      devs = g_devices;
-    }
-    const bool shardable = ndim == 3 && !(flags & (EDT_FLAG_FORCE_GENERIC | EDT_FLAG_BATCH_2D | EDT_FLAG_BINARY_YZ));
-    if (shardable && devs.size() >= 2 && multi_supported(dtype, sx, sy, sz, (int)devs.size())) {
-      Prefault touch(output, (size_t)voxels * sizeof(float));
-      touch.join();
-      return run_multi(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devs.data(), (int)devs.size());
-    }
-    if (!devs.empty()) {
-      // a one-entry list, or a call the slab-record form does not cover: the FIRST listed device does it alone
-      if (shardable && devs.size() >= 2) {
-        static std::atomic<bool> said{false};
-        if (!said.exchange(true))
-          fprintf(stderr, "[edt_hip] note: a %lld x %lld x %lld volume cannot be Z-sharded over %zu devices (slab records: "
-                          "sx, sy and sz <= 2048, >= 1 z-slice and >= 32 y-rows per device); device %d runs it alone\n",
-                  (long long)sx, (long long)sy, (long long)sz, devs.size(), devs[0]);
-      }
-      int prev = 0;
-      EDT_HIP_TRY(hipGetDevice(&prev));
-      if (prev != devs[0]) {
-        EDT_HIP_TRY(hipSetDevice(devs[0]));
-        rc = run_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags | EDT_FLAG_SINGLE_DEVICE, output);
-        (void)hipSetDevice(prev);
-        return rc;
-      }
-    }
+  std::vector<int> devs;
+  {
+    std::lock_guard<std::mutex> lock(g_devices_mutex);
+    devs = g_devices;
   }
-
-  const size_t lbytes = (size_t)voxels * dtype_size(dtype);
-  const size_t obytes = (size_t)voxels * sizeof(float);
-  const size_t wbytes = edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
-  const bool pooled = pool_enabled();
-  DevicePool *pool = pooled ? current_pool() : nullptr;
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
-  DeviceBuf d_labels(pool), d_out(pool), d_ws(pool);
-  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
-  if ((rc = d_out.alloc(obytes, pooled ? 1 : -1)) != EDT_OK) return rc;
-  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
-  Prefault touch(output, obytes);  // the result pages, while the labels travel and the kernels run
-  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
-  rc = run_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, (float *)d_out.p, d_ws.p,
-                  wbytes, nullptr);
-  if (rc != EDT_OK) return rc;
-  touch.join();
-  EDT_HIP_TRY(hipMemcpy(output, d_out.p, obytes, hipMemcpyDeviceToHost));
-  return EDT_OK;
+  const bool shardable = ndim == 3 && !env_force_generic() &&
+                         !(flags & (EDT_FLAG_FORCE_GENERIC | EDT_FLAG_BATCH_2D | EDT_FLAG_BINARY_YZ)) && devs.size() >= 2;
+  if (shardable && multi_supported(dtype, sx, sy, sz, (int)devs.size())) {
+    Prefault touch;
+    touch.start(output, (size_t)(sx * sy * sz) * sizeof(float));
+    touch.join();
+    return run_multi(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devs.data(), (int)devs.size());
+  }
+  // a one-entry list, or a call the slab-record form does not cover: the FIRST listed device does it alone
+  if (shardable) {
+    static std::atomic<bool> said{false};
+    if (!said.exchange(true))
+      fprintf(stderr, "[edt_hip] note: a %lld x %lld x %lld volume cannot be Z-sharded over %zu devices (slab records: "
+                      "sx, sy and sz <= 2048, >= 1 z-slice and >= 32 y-rows per device); device %d runs it alone\n",
+              (long long)sx, (long long)sy, (long long)sz, devs.size(), devs[0]);
+  }
+  ListedDevice on_listed_device(devs.empty() ? -1 : devs[0]);
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  return run_on_current_device(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, output);
 }
-
 
 // sdf / sdfsq on host buffers in ONE round trip (reference: src/edt.pyx:121-202, two transforms and a
 // subtraction on the host): labels up once, the SIGNED transform on the device (one transform: EDT_FLAG_SIGNED; shapes it does
 // not serve: edt(labels), the background mask, edt(mask) and the subtraction), the difference down once.
 static int sdf_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
                     float wy, float wz, int flags, float *output) {
-  int rc = check_shape(dtype, ndim, sx, sy, sz);
-  if (rc != EDT_OK) return rc;
-  if ((rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
-  const int64_t voxels = sx * sy * sz;
-  if (voxels == 0) return EDT_OK;
-  if (!labels || !output) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-  if ((rc = require_device()) != EDT_OK) return rc;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !output, &empty);
+  if (rc != EDT_OK || empty) return rc;
   ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
   if (env_force_generic()) flags |= EDT_FLAG_FORCE_GENERIC;
+  const int64_t voxels = sx * sy * sz;
   const size_t lbytes = (size_t)voxels * dtype_size(dtype), obytes = (size_t)voxels * sizeof(float);
   const size_t wbytes = std::max(edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags),
                                  edt_hip_workspace_bytes_flags(EDT_U8, ndim, sx, sy, sz, flags));
-  const bool pooled = pool_enabled();
-  DevicePool *pool = pooled ? current_pool() : nullptr;
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
-  DeviceBuf d_labels(pool), d_a(pool), d_ws(pool), d_mask(pool), d_b(pool);
-  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
-  if ((rc = d_a.alloc(obytes, pooled ? 1 : -1)) != EDT_OK) return rc;
-  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
-  if (signed_transform_supported(dtype, ndim, sx, sy, sz, flags)) {
-    // ONE transform (EDT_FLAG_SIGNED, edt_api.hip): label 0 measured like every label, its voxels negated at the end
-    Prefault touch(output, obytes);
-    EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
-    rc = run_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags | EDT_FLAG_SIGNED, (float *)d_a.p, d_ws.p, wbytes, nullptr);
-    if (rc != EDT_OK) return rc;
-    touch.join();
-    EDT_HIP_TRY(hipMemcpy(output, d_a.p, obytes, hipMemcpyDeviceToHost));
-    return EDT_OK;
+  // ONE transform where the shape allows (EDT_FLAG_SIGNED, edt_api.hip): label 0 measured like every label, its voxels negated
+  // at the end
+  const bool one = signed_transform_supported(dtype, ndim, sx, sy, sz, flags);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}})) != EDT_OK) return rc;
+  if (!one && (rc = st.alloc({{kAux, (size_t)voxels}, {kSecondField, obytes}})) != EDT_OK) return rc;
+  float *const a = st.at<float>(kOut);
+  st.expect(output, obytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = run_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, one ? flags | EDT_FLAG_SIGNED : flags, a, st.p[kWorkspace], wbytes, nullptr);
+  if (rc == EDT_OK && !one) {
+    rc = launch_is_background(dtype, st.p[kLabels], st.at<uint8_t>(kAux), voxels, nullptr);
+    if (rc == EDT_OK)
+      rc = run_device(st.p[kAux], EDT_U8, ndim, sx, sy, sz, wx, wy, wz, flags, st.at<float>(kSecondField), st.p[kWorkspace], wbytes, nullptr);
+    if (rc == EDT_OK) rc = launch_subtract(a, st.at<float>(kSecondField), a, voxels, nullptr);
   }
-  if ((rc = d_mask.alloc((size_t)voxels, pooled ? 3 : -1)) != EDT_OK) return rc;
-  if ((rc = d_b.alloc(obytes, pooled ? 4 : -1)) != EDT_OK) return rc;
-  Prefault touch(output, obytes);
-  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
-  rc = run_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, (float *)d_a.p, d_ws.p, wbytes, nullptr);
-  if (rc != EDT_OK) return rc;
-  rc = launch_is_background(dtype, d_labels.p, (uint8_t *)d_mask.p, voxels, nullptr);
-  if (rc != EDT_OK) return rc;
-  rc = run_device(d_mask.p, EDT_U8, ndim, sx, sy, sz, wx, wy, wz, flags, (float *)d_b.p, d_ws.p, wbytes, nullptr);
-  if (rc != EDT_OK) return rc;
-  rc = launch_subtract((const float *)d_a.p, (const float *)d_b.p, (float *)d_a.p, voxels, nullptr);
-  if (rc != EDT_OK) return rc;
-  touch.join();
-  EDT_HIP_TRY(hipMemcpy(output, d_a.p, obytes, hipMemcpyDeviceToHost));
-  return EDT_OK;
+  return rc != EDT_OK ? rc : st.down(output, kOut, obytes);
 }
 
 static int voxel_graph_host(const void *labels, int dtype, const uint8_t *graph, int ndim, int64_t sx,
                             int64_t sy, int64_t sz, float wx, float wy, float wz, int black_border,
                             float *output) {
-  int rc = check_shape(dtype, ndim, sx, sy, sz);
-  if (rc != EDT_OK) return rc;
-  if ((rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
-  const int64_t voxels = sx * sy * sz;
-  if (voxels == 0) return EDT_OK;
-  if (!labels || !graph || !output) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-  if ((rc = require_device()) != EDT_OK) return rc;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !graph || !output, &empty);
+  if (rc != EDT_OK || empty) return rc;
   ListedDevice on_listed_device;
-  const size_t lbytes = (size_t)voxels * dtype_size(dtype);
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), obytes = voxels * sizeof(float);
   const size_t wbytes = edt_hip_voxel_graph_workspace_bytes(ndim, sx, sy, sz);
-  const bool pooled = pool_enabled();
-  DevicePool *pool = pooled ? current_pool() : nullptr;
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
-  DeviceBuf d_labels(pool), d_graph(pool), d_ws(pool), d_out(pool);
-  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
-  if ((rc = d_out.alloc((size_t)voxels * sizeof(float), pooled ? 1 : -1)) != EDT_OK) return rc;
-  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
-  if ((rc = d_graph.alloc((size_t)voxels, pooled ? 3 : -1)) != EDT_OK) return rc;
-  Prefault touch(output, (size_t)voxels * sizeof(float));
-  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
-  EDT_HIP_TRY(hipMemcpy(d_graph.p, graph, (size_t)voxels, hipMemcpyHostToDevice));
-  rc = edt_hip_edtsq_voxel_graph_device(d_labels.p, dtype, (const uint8_t *)d_graph.p, ndim, sx, sy, sz, wx, wy, wz,
-                                        black_border ? EDT_FLAG_BLACK_BORDER : 0, (float *)d_out.p, d_ws.p, wbytes,
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}, {kAux, voxels}})) != EDT_OK) return rc;
+  st.expect(output, obytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK || (rc = st.up(kAux, graph, voxels)) != EDT_OK) return rc;
+  rc = edt_hip_edtsq_voxel_graph_device(st.p[kLabels], dtype, st.at<const uint8_t>(kAux), ndim, sx, sy, sz, wx, wy, wz,
+                                        black_border ? EDT_FLAG_BLACK_BORDER : 0, st.at<float>(kOut), st.p[kWorkspace], wbytes,
                                         nullptr);
-  if (rc != EDT_OK) return rc;
-  touch.join();
-  EDT_HIP_TRY(hipMemcpy(output, d_out.p, (size_t)voxels * sizeof(float), hipMemcpyDeviceToHost));
-  return EDT_OK;
+  return rc != EDT_OK ? rc : st.down(output, kOut, obytes);
 }
 
 // The feature transform and expand_labels on host buffers (kernels: edt_feature.hip): labels up once, the passes on the
 // device, the result down once (ndim int32 planes, or one label per voxel for expand_labels).
 static int feature_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
                         float wz, int flags, bool expand, double distance, void *output) {
-  int rc = check_shape(dtype, ndim, sx, sy, sz);
-  if (rc != EDT_OK) return rc;
-  if ((rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
-  if (expand && !(distance >= 0.0)) { set_error("expand_labels: distance must be >= 0 (inf allowed)"); return EDT_ERR_BAD_ARG; }
-  const int64_t voxels = sx * sy * sz;
-  if (voxels == 0) return EDT_OK;
-  if (!labels || !output) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-  if ((rc = require_device()) != EDT_OK) return rc;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !output, &empty, [&](After what) -> int {
+    if (what == After::voxel_sizes && expand && !(distance >= 0.0)) { set_error("expand_labels: distance must be >= 0 (inf allowed)"); return EDT_ERR_BAD_ARG; }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
   ListedDevice on_listed_device;
-  const size_t lbytes = (size_t)voxels * dtype_size(dtype);
-  const size_t obytes = expand ? lbytes : (size_t)voxels * ndim * sizeof(int32_t);
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype);
+  const size_t obytes = expand ? lbytes : voxels * ndim * sizeof(int32_t);
   const size_t wbytes = expand ? edt_hip_expand_labels_workspace_bytes(dtype, ndim, sx, sy, sz)
                                : edt_hip_feature_workspace_bytes(dtype, ndim, sx, sy, sz, flags);
-  const bool pooled = pool_enabled();
-  DevicePool *pool = pooled ? current_pool() : nullptr;
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
-  DeviceBuf d_labels(pool), d_out(pool), d_ws(pool);
-  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
-  if ((rc = d_out.alloc(obytes, pooled ? 1 : -1)) != EDT_OK) return rc;
-  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
-  Prefault touch(output, obytes);
-  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
-  rc = expand ? edt_hip_expand_labels_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, distance, d_out.p, d_ws.p,
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}})) != EDT_OK) return rc;
+  st.expect(output, obytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = expand ? edt_hip_expand_labels_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, distance, st.p[kOut], st.p[kWorkspace],
                                              wbytes, nullptr)
-              : edt_hip_feature_transform_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags,
-                                                 (int32_t *)d_out.p, d_ws.p, wbytes, nullptr);
-  if (rc != EDT_OK) return rc;
-  touch.join();
-  EDT_HIP_TRY(hipMemcpy(output, d_out.p, obytes, hipMemcpyDeviceToHost));
-  return EDT_OK;
+              : edt_hip_feature_transform_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, flags, st.at<int32_t>(kOut),
+                                                 st.p[kWorkspace], wbytes, nullptr);
+  return rc != EDT_OK ? rc : st.down(output, kOut, obytes);
 }
 
 // label_stats on host buffers (kernels: edt_labelstats.hip): labels up once (and the caller's field, if it brings one; else the
@@ -364,19 +342,26 @@ static int feature_host(const void *labels, int dtype, int ndim, int64_t sx, int
 static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
                             float wz, int black_border, const float *dt, int64_t max_labels, void *keys, int64_t *counts,
                             float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels) {
-  int rc = check_shape(dtype, ndim, sx, sy, sz);
-  if (rc != EDT_OK) return rc;
-  if (max_labels < 1) { set_error("label_stats: max_labels must be at least 1"); return EDT_ERR_BAD_ARG; }
-  if (!dt && (rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
-  if (!n_labels) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-  const int64_t voxels = sx * sy * sz;
-  if (voxels == 0) { *n_labels = 0; return EDT_OK; }
-  if (!labels || !keys || !counts || !max || !argmax || !bbox) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-  const int64_t cap = std::min(max_labels, voxels);
-  const size_t sbytes = edt_hip_label_stats_workspace_bytes(dtype, voxels, cap);
-  if (sbytes == 0) { set_error("label_stats: max_labels out of range"); return EDT_ERR_BAD_ARG; }
-  if ((rc = require_device()) != EDT_OK) return rc;
+  int64_t cap = 0;
+  size_t sbytes = 0;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, dt ? nullptr : w, !labels || !keys || !counts || !max || !argmax || !bbox, &empty,
+                         [&](After what) -> int {
+    if (what == After::shape && max_labels < 1) { set_error("label_stats: max_labels must be at least 1"); return EDT_ERR_BAD_ARG; }
+    if (what == After::voxel_sizes && !n_labels) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    if (what == After::pointers) {  // (the volume is not empty here)
+      cap = std::min(max_labels, sx * sy * sz);
+      sbytes = edt_hip_label_stats_workspace_bytes(dtype, sx * sy * sz, cap);
+      if (sbytes == 0) { set_error("label_stats: max_labels out of range"); return EDT_ERR_BAD_ARG; }
+    }
+    return EDT_OK;
+  });
+  if (rc == EDT_OK && empty) *n_labels = 0;
+  if (rc != EDT_OK || empty) return rc;
   ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const int64_t voxels = sx * sy * sz;
   const int flags = (black_border ? EDT_FLAG_BLACK_BORDER : 0) | EDT_FLAG_SQRT | (env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0);
   const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
   const size_t tbytes = dt ? 0 : edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
@@ -385,37 +370,24 @@ static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx,
   const size_t n = (size_t)cap, ksz = (size_t)dtype_size(dtype);
   const size_t o_counts = align_up(n * ksz, 8), o_argmax = o_counts + 8 * n, o_n = o_argmax + 8 * n, o_max = o_n + 8,
                o_bbox = o_max + 4 * n, obytes = o_bbox + 24 * n;
-  const bool pooled = pool_enabled();
-  DevicePool *pool = pooled ? current_pool() : nullptr;
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) pool_lock = std::unique_lock<std::mutex>(pool->m);
-  DeviceBuf d_labels(pool), d_dt(pool), d_ws(pool), d_tab(pool);
-  if ((rc = d_labels.alloc(lbytes, pooled ? 0 : -1)) != EDT_OK) return rc;
-  if ((rc = d_dt.alloc(fbytes, pooled ? 1 : -1)) != EDT_OK) return rc;
-  if ((rc = d_ws.alloc(wbytes, pooled ? 2 : -1)) != EDT_OK) return rc;
-  if ((rc = d_tab.alloc(obytes, pooled ? 3 : -1)) != EDT_OK) return rc;
-  EDT_HIP_TRY(hipMemcpy(d_labels.p, labels, lbytes, hipMemcpyHostToDevice));
-  if (dt) {
-    EDT_HIP_TRY(hipMemcpy(d_dt.p, dt, fbytes, hipMemcpyHostToDevice));
-  } else {
-    rc = run_device(d_labels.p, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, (float *)d_dt.p, d_ws.p, wbytes, nullptr);
-    if (rc != EDT_OK) return rc;
-  }
-  char *tab = (char *)d_tab.p;
-  rc = edt_hip_label_stats_device(d_labels.p, dtype, (const float *)d_dt.p, ndim, sx, sy, sz, cap, tab,
-                                  (int64_t *)(tab + o_counts), (float *)(tab + o_max), (int64_t *)(tab + o_argmax),
-                                  (int32_t *)(tab + o_bbox), (int64_t *)(tab + o_n), d_ws.p, wbytes, nullptr);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, fbytes}, {kWorkspace, wbytes}, {kAux, obytes}})) != EDT_OK) return rc;
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = dt ? st.up(kOut, dt, fbytes)
+          : run_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, flags, st.at<float>(kOut), st.p[kWorkspace], wbytes, nullptr);
   if (rc != EDT_OK) return rc;
-  EDT_HIP_TRY(hipMemcpy(n_labels, tab + o_n, sizeof(int64_t), hipMemcpyDeviceToHost));
+  char *tab = st.at<char>(kAux);
+  rc = edt_hip_label_stats_device(st.p[kLabels], dtype, st.at<const float>(kOut), ndim, sx, sy, sz, cap, tab,
+                                  (int64_t *)(tab + o_counts), (float *)(tab + o_max), (int64_t *)(tab + o_argmax),
+                                  (int32_t *)(tab + o_bbox), (int64_t *)(tab + o_n), st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(n_labels, kAux, sizeof(int64_t), o_n)) != EDT_OK) return rc;
   if (*n_labels > cap) return EDT_OK;  // not an error: the caller retries with more room
   const size_t m = (size_t)*n_labels;
   if (m == 0) return EDT_OK;
-  EDT_HIP_TRY(hipMemcpy(keys, tab, m * ksz, hipMemcpyDeviceToHost));
-  EDT_HIP_TRY(hipMemcpy(counts, tab + o_counts, m * 8, hipMemcpyDeviceToHost));
-  EDT_HIP_TRY(hipMemcpy(argmax, tab + o_argmax, m * 8, hipMemcpyDeviceToHost));
-  EDT_HIP_TRY(hipMemcpy(max, tab + o_max, m * 4, hipMemcpyDeviceToHost));
-  EDT_HIP_TRY(hipMemcpy(bbox, tab + o_bbox, m * 24, hipMemcpyDeviceToHost));
-  return EDT_OK;
+  if ((rc = st.down(keys, kAux, m * ksz)) != EDT_OK || (rc = st.down(counts, kAux, m * 8, o_counts)) != EDT_OK ||
+      (rc = st.down(argmax, kAux, m * 8, o_argmax)) != EDT_OK || (rc = st.down(max, kAux, m * 4, o_max)) != EDT_OK)
+    return rc;
+  return st.down(bbox, kAux, m * 24, o_bbox);
 }
 
 }  // namespace edt_amd
@@ -502,14 +474,12 @@ int edt_hip_edt3dsq_multi(const void *labels, int dtype, int64_t sx, int64_t sy,
     return EDT_ERR_UNSUPPORTED;
   }
   if (n_devices == 1) {  // a list of one: that device does it
-    int prev = 0;
-    EDT_HIP_TRY(hipGetDevice(&prev));
-    EDT_HIP_TRY(hipSetDevice(devices[0]));
-    rc = run_host(labels, dtype, 3, sx, sy, sz, wx, wy, wz, flags | EDT_FLAG_SINGLE_DEVICE, output);
-    (void)hipSetDevice(prev);
-    return rc;
+    ListedDevice on_that_device(devices[0]);
+    if (on_that_device.rc != EDT_OK) return on_that_device.rc;
+    return run_on_current_device(labels, dtype, 3, sx, sy, sz, wx, wy, wz, flags, output);
   }
-  Prefault touch(output, (size_t)(sx * sy * sz) * sizeof(float));
+  Prefault touch;
+  touch.start(output, (size_t)(sx * sy * sz) * sizeof(float));
   touch.join();
   return run_multi(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devices, n_devices);
 }

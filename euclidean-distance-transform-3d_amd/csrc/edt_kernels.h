@@ -32,17 +32,41 @@ __device__ __forceinline__ float finish(float m, int epi) {
   return m;
 }
 
+// Pass X over a stack of sy * sz rows of sx voxels, whichever kernel serves it.  Every kernel writes `out`; the row kernels
+// (edt_rowwave.hip, edt_rows.hip) also emit the y-packed bit planes [z][y-band][x] of the column passes, and only the register
+// kernel of edt_rowwave.hip knows halo, codes and zero_label.
+struct RowPass {
+  int dtype = EDT_U8;
+  const void *labels = nullptr;
+  const void *halo = nullptr;  // the xy-slice below slice 0 (Z-sharded slabs, later slabs of a call); nullptr: slice 0 starts every z-run
+  int64_t sx = 1, sy = 1, sz = 1;
+  float w = 1.0f;              // voxel size along x
+  int bb = 0;
+  hipStream_t stream = nullptr;
+  float *out = nullptr;        // the fp32 field (not touched where codes is given)
+  uint32_t *nz_y = nullptr, *ys_y = nullptr, *zs_y = nullptr;  // foreground (nullptr: nobody reads one) / y-run starts / z-run starts (nullptr: no z pass)
+  uint16_t *codes = nullptr;   // index form: 16-bit distance indices go here INSTEAD of `out` (see XFuse) ...
+  int64_t codes_pitch = 0;     // ... their slices this many elements apart (0: sx * sy)
+  int zero_label = 0;          // label 0 is measured like every label (the signed transform; 2: nz_y keeps the true label != 0 bits)
+  // pass X is the call's LAST pass (a 1-D call): a row without a boundary keeps +inf, and the square root is taken here if asked
+  bool last = false, last_sqrt = false;
+  int64_t nrows() const { return sy * sz; }
+  int to_finite() const { return (bb || last) ? 0 : 1; }  // FLT_MAX, not +inf, where a row has no boundary: a column pass follows
+  int take_sqrt() const { return (last && last_sqrt) ? 1 : 0; }
+};
+inline RowPass row_pass(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, float w, int bb, hipStream_t stream) {
+  RowPass rp;
+  rp.dtype = dtype; rp.labels = labels; rp.sx = sx; rp.sy = sy; rp.sz = sz; rp.w = w; rp.bb = bb; rp.stream = stream;
+  return rp;
+}
 // ---- generic (any extent) kernels: edt_generic.hip ------------------------------------
-int launch_row_pass_serial(int dtype, const void *labels, float *out, int64_t sx, int64_t nrows,
-                           float w, int bb, int to_finite, int take_sqrt, hipStream_t stream);
+int launch_row_pass_serial(const RowPass &rp);  // a thread per row
 // ---- the 1-D transform as a parallel pipeline for lines of any length: edt_line.hip -----------------
 size_t line_workspace_bytes(int64_t n);
-int launch_line_pass(int dtype, const void *labels, float *out, int64_t n, float w, int bb, int take_sqrt,
-                     void *ws, hipStream_t stream);
-// pass 1 over rows of any length (sx > 2048): the line pipeline with a run start forced at every row's first voxel
+// pass 1 over rows of any length (sx > 2048), or the one line of a 1-D call: the line pipeline with a run start forced at
+// every row's first voxel
 size_t rows_line_workspace_bytes(int64_t sx, int64_t nrows);
-int launch_rows_line_pass(int dtype, const void *labels, float *out, int64_t sx, int64_t nrows, float w, int bb,
-                          int to_finite, void *ws, hipStream_t stream);
+int launch_rows_line_pass(const RowPass &rp, void *ws);
 size_t runs_workspace_bytes(int64_t n);
 int launch_extract_runs(int dtype, const void *labels, int64_t n, int64_t *starts, int64_t capacity, int64_t *total,
                         void *ws, hipStream_t stream);
@@ -94,9 +118,7 @@ int launch_column_pass_tiled(float *F, const uint32_t *nz, const uint32_t *rs, c
                              float w, int bb, int epi, hipStream_t stream);
 // ---- wave-per-row-group pass 1 + bit-plane transposer: edt_rows.hip ---------------------------
 bool row_pass_tiled_supported(int64_t sx);
-int launch_row_pass_tiled(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                          uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                          int to_finite, hipStream_t stream);
+int launch_row_pass_tiled(const RowPass &rp);
 // in_zstride: words between consecutive z of the y-packed planes (0 = dense, nby * sx)
 int launch_bits_transpose_yz(const uint32_t *nz_y, const uint32_t *zs_y, uint32_t *nz_z,
                              uint32_t *rs_z, int64_t sx, int64_t sy, int64_t sz, hipStream_t stream,
@@ -225,15 +247,18 @@ int run_column_pass(const ColumnPass &cp, const Quantum &Q, int axis, HandOver &
 namespace edt_amd {
 // ---- register-resident pass 1 (rows up to 512 voxels): edt_rowwave.hip -------------------------
 bool row_pass_wave_supported(int dtype, int64_t sx, int64_t sy, int64_t sz);
-// halo: the xy-slice below slice 0 (Z-sharded slabs), or nullptr = slice 0 starts every z-run
-// codes != nullptr: 16-bit distance indices are written there INSTEAD of `out` (see XFuse)
-int launch_row_pass_wave(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                         uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                         int to_finite, hipStream_t stream, const void *halo = nullptr, uint16_t *codes = nullptr,
-                         int zero_label = 0,  // zero_label: label 0 is measured like every label (the signed transform)
-                         int64_t codes_pitch = 0);  // elements between the slices of codes (0: sx * sy)
+int launch_row_pass_wave(const RowPass &rp);
 // k * w exact for every k of a row of sx voxels: the 16-bit index form (codes) is bit-identical
 bool row_codes_exact(float w, int64_t sx);
+// ---- the driver of pass X: edt_rowpass.hip ---------------------------------------------------
+// The one place that picks the pass-X kernel: the register kernel or the workgroup-phased one (debug bit kDbgTiledRows) where
+// rows are short enough and the call is not forced onto the generic kernels; else the line pipeline if the caller has scratch
+// for it (line_ws, rows_line_workspace_bytes), else a thread per row -- and then the y planes by launch_axis_bits, which the
+// row kernels emit themselves.  row_kernels: the answer of row_pass_on_row_kernels for this call, which the caller needs itself
+// (which planes exist, the index form) and therefore asks once and hands in; false for the one line of a 1-D call.
+// log: the pass log names x_pass (and y_bits).
+bool row_pass_on_row_kernels(int dtype, int64_t sx, int64_t sy, int64_t sz, bool force_generic);
+int run_row_pass(const RowPass &rp, bool row_kernels, void *line_ws, bool log = false);
 
 }  // namespace edt_amd
 

@@ -238,10 +238,9 @@ bool multiples_exact(float w, int64_t kmax) {
 
 template <typename T>
 int launch_line_t(const void *labels, float *out, int64_t n, float w, int bb, int take_sqrt, void *ws,
-                  hipStream_t stream, int64_t row = 0, int to_finite = 0) {
+                  hipStream_t stream, int64_t row, int to_finite) {
   const T *lab = static_cast<const T *>(labels);
-  if (row <= 0) row = n;                       // one line = one row
-  const int64_t rows = n / row;
+  const int64_t rows = n / row;                // (one line = one row)
   const int64_t bpr = ceil_div(row, kLineBlock);
   const int64_t nblk = rows * bpr;
   if (nblk > 0x7FFFFFFF) { set_error("line too long"); return EDT_ERR_UNSUPPORTED; }
@@ -349,17 +348,9 @@ size_t runs_workspace_bytes(int64_t n) { return align_up((size_t)ceil_div(n, kLi
 
 int launch_extract_runs(int dtype, const void *labels, int64_t n, int64_t *starts, int64_t capacity, int64_t *total,
                         void *ws, hipStream_t stream) {
-#define RUNS(T) return launch_runs_t<T>(labels, n, starts, capacity, total, ws, stream)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: RUNS(uint8_t);
-    case EDT_U16: RUNS(uint16_t);
-    case EDT_U32: RUNS(uint32_t);
-    case EDT_U64: RUNS(uint64_t);
-    case EDT_F32: RUNS(float);
-    case EDT_F64: RUNS(double);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef RUNS
+  return with_label_type(dtype, [&](auto t) {
+    return launch_runs_t<typename decltype(t)::type>(labels, n, starts, capacity, total, ws, stream);
+  });
 }
 
 size_t line_workspace_bytes(int64_t n) {
@@ -375,34 +366,12 @@ size_t rows_line_workspace_bytes(int64_t sx, int64_t nrows) {
   return align_up((size_t)(2 * nblk) * sizeof(int64_t), 256) + align_up((size_t)(sx + 2) * sizeof(float), 256) + 256;
 }
 
-int launch_rows_line_pass(int dtype, const void *labels, float *out, int64_t sx, int64_t nrows, float w, int bb,
-                          int to_finite, void *ws, hipStream_t stream) {
-#define ROWS(T) return launch_line_t<T>(labels, out, sx * nrows, w, bb, 0, ws, stream, sx, to_finite)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: ROWS(uint8_t);
-    case EDT_U16: ROWS(uint16_t);
-    case EDT_U32: ROWS(uint32_t);
-    case EDT_U64: ROWS(uint64_t);
-    case EDT_F32: ROWS(float);
-    case EDT_F64: ROWS(double);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef ROWS
-}
-
-int launch_line_pass(int dtype, const void *labels, float *out, int64_t n, float w, int bb, int take_sqrt,
-                     void *ws, hipStream_t stream) {
-#define LINE(T) return launch_line_t<T>(labels, out, n, w, bb, take_sqrt, ws, stream)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: LINE(uint8_t);
-    case EDT_U16: LINE(uint16_t);
-    case EDT_U32: LINE(uint32_t);
-    case EDT_U64: LINE(uint64_t);
-    case EDT_F32: LINE(float);
-    case EDT_F64: LINE(double);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef LINE
+// (a 1-D call is a stack of one row: rp.last keeps +inf and takes the square root here)
+int launch_rows_line_pass(const RowPass &rp, void *ws) {
+  return with_label_type(rp.dtype, [&](auto t) {
+    return launch_line_t<typename decltype(t)::type>(rp.labels, rp.out, rp.sx * rp.nrows(), rp.w, rp.bb, rp.take_sqrt(), ws,
+                                                     rp.stream, rp.sx, rp.to_finite());
+  });
 }
 
 }  // namespace edt_amd

@@ -187,14 +187,12 @@ k_row_pass_tiled(const T *__restrict__ labels, float *__restrict__ out,
 bool row_pass_tiled_supported(int64_t sx) { return sx >= 1 && sx <= (int64_t)kMaxChunks * 64; }
 
 template <typename T>
-static int launch_row_tiled_t(const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                              uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                              int to_finite, hipStream_t stream) {
-  const int NC = (int)ceil_div(sx, 64);
-  const int64_t nby = ceil_div(sy, kBandRows);
-  const int64_t ngroups = nby * sz;
+static int launch_row_tiled_t(const RowPass &rp) {
+  const int NC = (int)ceil_div(rp.sx, 64);
+  const int64_t nby = ceil_div(rp.sy, kBandRows);
+  const int64_t ngroups = nby * rp.sz;
   if (ngroups <= 0) return EDT_OK;
-  const size_t lds = (size_t)((sx + 2 + 3) & ~3) * sizeof(float) +
+  const size_t lds = (size_t)((rp.sx + 2 + 3) & ~3) * sizeof(float) +
                      (size_t)kWavesPerBlock * 32 * NC * 24;
   static std::atomic<uint64_t> attr_done{0};  // per instantiation, one bit per device
   EDT_HIP_TRY(EDT_LDS_ATTR_ONCE(attr_done, reinterpret_cast<const void *>(&k_row_pass_tiled<T, true>),
@@ -202,33 +200,15 @@ static int launch_row_tiled_t(const void *labels, float *out, uint32_t *nz_y, ui
   int64_t blocks = ceil_div(ngroups, kWavesPerBlock);
   const int64_t resident = 256 * 6;  // persistent grid: the T table is built once per block
   if (blocks > resident) blocks = resident;
-  if (zs_y != nullptr)
-    hipLaunchKernelGGL((k_row_pass_tiled<T, true>), dim3((unsigned)blocks), dim3(kWavesPerBlock * 64),
-                       lds, stream, (const T *)labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb,
-                       to_finite, NC, nby, ngroups);
-  else
-    hipLaunchKernelGGL((k_row_pass_tiled<T, false>), dim3((unsigned)blocks), dim3(kWavesPerBlock * 64),
-                       lds, stream, (const T *)labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb,
-                       to_finite, NC, nby, ngroups);
+  const auto kernel = rp.zs_y != nullptr ? k_row_pass_tiled<T, true> : k_row_pass_tiled<T, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kWavesPerBlock * 64), lds, rp.stream, (const T *)rp.labels, rp.out,
+                     rp.nz_y, rp.ys_y, rp.zs_y, rp.sx, rp.sy, rp.sz, rp.w, rp.bb, rp.to_finite(), NC, nby, ngroups);
   EDT_HIP_TRY(hipGetLastError());
   return EDT_OK;
 }
 
-int launch_row_pass_tiled(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                          uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                          int to_finite, hipStream_t stream) {
-#define ROW_TILED(T) \
-  return launch_row_tiled_t<T>(labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: ROW_TILED(uint8_t);
-    case EDT_U16: ROW_TILED(uint16_t);
-    case EDT_U32: ROW_TILED(uint32_t);
-    case EDT_U64: ROW_TILED(uint64_t);
-    case EDT_F32: ROW_TILED(float);
-    case EDT_F64: ROW_TILED(double);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef ROW_TILED
+int launch_row_pass_tiled(const RowPass &rp) {
+  return with_label_type(rp.dtype, [&](auto t) { return launch_row_tiled_t<typename decltype(t)::type>(rp); });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -375,11 +375,9 @@ bool row_pass_wave_supported(int dtype, int64_t sx, int64_t sy, int64_t sz) {
 }
 
 template <typename T, int NC, int H = 1>
-static int launch_row_wave_tn(const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                              uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                              int to_finite, hipStream_t stream, const void *halo, bool codes, int zero_label, int64_t opitch) {
-  const int64_t nby = ceil_div(sy, kBandRows);
-  const int64_t ngroups = nby * sz;
+static int launch_row_wave_tn(const RowPass &rp) {
+  const int64_t sx = rp.sx, nby = ceil_div(rp.sy, kBandRows);
+  const int64_t ngroups = nby * rp.sz;
   if (ngroups <= 0) return EDT_OK;
   constexpr int GW = H >= 2 ? 1 : kRowWaves;        // groups a workgroup works on at a time
   constexpr int WAVES = H >= 2 ? H : kRowWaves;     // its waves
@@ -387,66 +385,47 @@ static int launch_row_wave_tn(const void *labels, float *out, uint32_t *nz_y, ui
   int64_t blocks = ceil_div(ngroups, GW);
   const int64_t resident = 256 * 8 * (kRowWaves / WAVES > 0 ? kRowWaves / WAVES : 1);  // persistent grid: the T table is built once per workgroup
   if (blocks > resident) blocks = resident;
-  const int xcd_sched = row_xcd_schedule(nby, sz, &blocks, GW, resident / 8);
-#define LAUNCH(Z, F, C)                                                                                   \
-  hipLaunchKernelGGL((k_row_pass_wave<T, NC, Z, F, C, H>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream,  \
-                     (const T *)labels, out, nz_y, ys_y, zs_y, (int)sx, (int)sy, (int)sz, w, bb, to_finite, \
-                     (int)nby, (int)ngroups, xcd_sched, (const T *)halo, zero_label, opitch)
-#define LAUNCH_C(Z, F) do { if (codes) LAUNCH(Z, F, true); else LAUNCH(Z, F, false); } while (0)
+  const int xcd_sched = row_xcd_schedule(nby, rp.sz, &blocks, GW, resident / 8);
+  // codes != nullptr: the 16-bit distance indices go there and `out` is not touched; codes_pitch > 0: its slices lie that many
+  // elements apart (the padded pitch of the index buffer), else sx * sy like everything else
+  float *const out = rp.codes != nullptr ? reinterpret_cast<float *>(rp.codes) : rp.out;
+  const int64_t opitch = (rp.codes != nullptr && rp.codes_pitch > 0) ? rp.codes_pitch : sx * rp.sy;
   const bool full = sx == 64 * NC * H;
-  if (zs_y != nullptr) { if (full) LAUNCH_C(true, true); else LAUNCH_C(true, false); }
-  else { if (full) LAUNCH_C(false, true); else LAUNCH_C(false, false); }
-#undef LAUNCH_C
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVES * 64), lds, rp.stream, (const T *)rp.labels, out, rp.nz_y, rp.ys_y,
+                       rp.zs_y, (int)sx, (int)rp.sy, (int)rp.sz, rp.w, rp.bb, rp.to_finite(), (int)nby, (int)ngroups, xcd_sched,
+                       (const T *)rp.halo, rp.zero_label, opitch);
+  };
+#define LAUNCH(Z, F) do { if (rp.codes != nullptr) launch(k_row_pass_wave<T, NC, Z, F, true, H>); else launch(k_row_pass_wave<T, NC, Z, F, false, H>); } while (0)
+  if (rp.zs_y != nullptr) { if (full) LAUNCH(true, true); else LAUNCH(true, false); }
+  else { if (full) LAUNCH(false, true); else LAUNCH(false, false); }
 #undef LAUNCH
   EDT_HIP_TRY(hipGetLastError());
   return EDT_OK;
 }
 
 template <typename T>
-static int launch_row_wave_t(const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                             uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                             int to_finite, hipStream_t stream, const void *halo, bool codes, int zero_label, int64_t opitch) {
-  const int64_t nc = ceil_div(sx, 64);
-#define GO(N) return launch_row_wave_tn<T, N>(labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream, halo, codes, zero_label, opitch)
-  if (nc <= 1) GO(1);
-  if (nc <= 2) GO(2);
-  if (nc <= 4) GO(4);
-  if (nc <= 8) GO(8);
-  if (nc <= 16) GO(16);
-#undef GO
+static int launch_row_wave_t(const RowPass &rp) {
+  const int64_t nc = ceil_div(rp.sx, 64);
+#define GO(N, H) return launch_row_wave_tn<T, N, H>(rp)
+  if (nc <= 1) GO(1, 1);
+  if (nc <= 2) GO(2, 1);
+  if (nc <= 4) GO(4, 1);
+  if (nc <= 8) GO(8, 1);
+  if (nc <= 16) GO(16, 1);
   // rows of 1025..2048 voxels: two waves per row (H = 2), halves of 10, 12, 14 or 16 chunks
-#define GO2(N) return launch_row_wave_tn<T, N, 2>(labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream, halo, codes, zero_label, opitch)
-  if (nc <= 20) GO2(10);
-  if (nc <= 24) GO2(12);
-  if (nc <= 28) GO2(14);
-  if (nc <= 32) GO2(16);
-#undef GO2
+  if (nc <= 20) GO(10, 2);
+  if (nc <= 24) GO(12, 2);
+  if (nc <= 28) GO(14, 2);
+  if (nc <= 32) GO(16, 2);
   // rows of 2049..4096 voxels: four waves per row (H = 4), parts of 12 or 16 chunks
-#define GO4(N) return launch_row_wave_tn<T, N, 4>(labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream, halo, codes, zero_label, opitch)
-  if (nc <= 48) GO4(12);
-  GO4(16);
-#undef GO4
+  if (nc <= 48) GO(12, 4);
+  GO(16, 4);
+#undef GO
 }
 
-int launch_row_pass_wave(int dtype, const void *labels, float *out, uint32_t *nz_y, uint32_t *ys_y,
-                         uint32_t *zs_y, int64_t sx, int64_t sy, int64_t sz, float w, int bb,
-                         int to_finite, hipStream_t stream, const void *halo, uint16_t *codes, int zero_label, int64_t codes_pitch) {
-  // codes != nullptr: the 16-bit distance indices go there and `out` is not touched; codes_pitch > 0: its slices lie that many
-  // elements apart (the padded pitch of the index buffer), else sx * sy like everything else
-  const int64_t opitch = (codes != nullptr && codes_pitch > 0) ? codes_pitch : sx * sy;
-  if (codes != nullptr) out = reinterpret_cast<float *>(codes);
-#define ROW_WAVE(T) \
-  return launch_row_wave_t<T>(labels, out, nz_y, ys_y, zs_y, sx, sy, sz, w, bb, to_finite, stream, halo, codes != nullptr, zero_label, opitch)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: ROW_WAVE(uint8_t);
-    case EDT_U16: ROW_WAVE(uint16_t);
-    case EDT_U32: ROW_WAVE(uint32_t);
-    case EDT_U64: ROW_WAVE(uint64_t);
-    case EDT_F32: ROW_WAVE(float);
-    case EDT_F64: ROW_WAVE(double);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef ROW_WAVE
+int launch_row_pass_wave(const RowPass &rp) {
+  return with_label_type(rp.dtype, [&](auto t) { return launch_row_wave_t<typename decltype(t)::type>(rp); });
 }
 
 }  // namespace edt_amd

@@ -36,21 +36,13 @@ int launch_zflags(int dtype, const void *labels, const void *halo, uint8_t *flag
   int64_t blocks = ceil_div(sxy * szl, threads);
   if (blocks <= 0) return EDT_OK;
   if (blocks > 16384) blocks = 16384;
-#define LAUNCH_ZF(T)                                                                          \
-  hipLaunchKernelGGL(k_zflags<T>, dim3((unsigned)blocks), dim3(threads), 0, stream,           \
-                     (const T *)labels, (const T *)halo, flags, sxy, szl)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: LAUNCH_ZF(uint8_t); break;
-    case EDT_U16: LAUNCH_ZF(uint16_t); break;
-    case EDT_U32: LAUNCH_ZF(uint32_t); break;
-    case EDT_U64: LAUNCH_ZF(uint64_t); break;
-    case EDT_F32: LAUNCH_ZF(float); break;
-    case EDT_F64: LAUNCH_ZF(double); break;
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef LAUNCH_ZF
-  EDT_HIP_TRY(hipGetLastError());
-  return EDT_OK;
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(k_zflags<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, (const T *)halo, flags,
+                       sxy, szl);
+    EDT_HIP_TRY(hipGetLastError());
+    return EDT_OK;
+  });
 }
 
 // flags (one byte per voxel, volume addressing) -> nz / rs words of the given axis geometry

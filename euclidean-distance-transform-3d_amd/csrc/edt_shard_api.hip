@@ -141,24 +141,14 @@ int edt_hip_shard_xy_device(const void *d_labels, const void *d_halo, int dtype,
   const bool force_generic = (flags & EDT_FLAG_FORCE_GENERIC) != 0;
   AxisGeom gy = make_geom_y(sx, sy, sz_local);
   gy.fmin = edt_hip_field_floor(wx, wx);  // (pass Y reads the results of pass X: AxisGeom::fmin)
-  const bool tiled_x = !force_generic && (row_pass_tiled_supported(sx) || row_pass_wave_supported(dtype, sx, sy, sz_local));
   const bool tiled_y = !force_generic && column_inplace_supported(gy);
-  float *xout = tiled_y ? d_partial : p.bufB;  // the tiled y pass runs in place
-  if (tiled_x) {
-    rc = launch_row_bits(dtype, d_labels, xout, p.nz, p.rs, nullptr, sx, sy, sz_local, wx, bb, bb ? 0 : 1,
-                         stream);
-    if (rc != EDT_OK) return rc;
-  } else {
-    // rows of more than 2048 voxels: the line pipeline (a thread per voxel), its scratch borrowed from the hull
-    // stacks, which only the size-agnostic column pass uses -- later on this stream
-    if (!force_generic && rows_line_workspace_bytes(sx, sy * sz_local) <= (size_t)(sx * sy * sz_local) * sizeof(int32_t))
-      rc = launch_rows_line_pass(dtype, d_labels, xout, sx, sy * sz_local, wx, bb, bb ? 0 : 1, p.stack, stream);
-    else
-      rc = launch_row_pass_serial(dtype, d_labels, xout, sx, sy * sz_local, wx, bb, bb ? 0 : 1, 0, stream);
-    if (rc != EDT_OK) return rc;
-    rc = launch_axis_bits(dtype, d_labels, nullptr, p.nz, p.rs, gy, stream);
-    if (rc != EDT_OK) return rc;
-  }
+  RowPass rp = row_pass(dtype, d_labels, sx, sy, sz_local, wx, bb, stream);
+  rp.out = tiled_y ? d_partial : p.bufB;  // the tiled y pass runs in place
+  rp.nz_y = p.nz; rp.ys_y = p.rs;
+  // rows no row kernel takes: the line pipeline (a thread per voxel), its scratch borrowed from the hull stacks, which only
+  // the size-agnostic column pass uses -- later on this stream
+  const bool borrow = !force_generic && rows_line_workspace_bytes(sx, sy * sz_local) <= (size_t)(sx * sy * sz_local) * sizeof(int32_t);
+  if ((rc = run_row_pass(rp, row_pass_on_row_kernels(dtype, sx, sy, sz_local, force_generic), borrow ? p.stack : nullptr)) != EDT_OK) return rc;
   if (tiled_y) rc = launch_column_inplace(column_pass(d_partial, p.nz, p.rs, gy, wy, bb, 0, stream));
   else rc = launch_column_pass_serial(p.bufB, d_partial, p.nz, p.rs, p.stack, gy, wy, bb, 0, stream);
   if (rc != EDT_OK) return rc;
@@ -250,9 +240,9 @@ int edt_hip_shard_xy_records_device(const void *d_labels, const void *d_halo, in
   uint16_t *codes = index_form ? reinterpret_cast<uint16_t *>(p.F) : nullptr;
   {
     ScopedPass t("x_pass", stream);
-    rc = launch_row_pass_wave(dtype, d_labels, p.F, p.nz_y, p.ys_y, p.zs_y, sx, sy, sz_local, wx, bb,
-                              bb ? 0 : 1, stream, d_halo, codes);
-    if (rc != EDT_OK) return rc;
+    RowPass rp = row_pass(dtype, d_labels, sx, sy, sz_local, wx, bb, stream);
+    rp.halo = d_halo; rp.out = p.F; rp.nz_y = p.nz_y; rp.ys_y = p.ys_y; rp.zs_y = p.zs_y; rp.codes = codes;
+    if ((rc = launch_row_pass_wave(rp)) != EDT_OK) return rc;
   }
   {
     ScopedPass t("pack_bits", stream);
@@ -385,9 +375,9 @@ int edt_hip_shard_xy_records16_device(const void *d_labels, const void *d_halo, 
   uint16_t *codes = reinterpret_cast<uint16_t *>(p.F);
   {
     ScopedPass t("x_pass", stream);
-    rc = launch_row_pass_wave(dtype, d_labels, p.F, p.nz_y, p.ys_y, p.zs_y, sx, sy, sz_local, wx, bb, bb ? 0 : 1, stream,
-                              d_halo, codes);
-    if (rc != EDT_OK) return rc;
+    RowPass rp = row_pass(dtype, d_labels, sx, sy, sz_local, wx, bb, stream);
+    rp.halo = d_halo; rp.out = p.F; rp.nz_y = p.nz_y; rp.ys_y = p.ys_y; rp.zs_y = p.zs_y; rp.codes = codes;
+    if ((rc = launch_row_pass_wave(rp)) != EDT_OK) return rc;
   }
   {
     ScopedPass t("pack_bits", stream);

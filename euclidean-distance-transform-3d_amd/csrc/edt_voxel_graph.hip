@@ -67,21 +67,13 @@ int launch_vg_expand(int dtype, const void *labels, const uint8_t *graph, uint8_
   const int64_t total = sx * 2 * sy * (ndim == 3 ? 2 * sz : 1);
   int64_t blocks = ceil_div(total, threads);
   if (blocks > 16384) blocks = 16384;
-#define LAUNCH_VG(T)                                                                            \
-  hipLaunchKernelGGL(k_vg_expand<T>, dim3((unsigned)blocks), dim3(threads), 0, stream,          \
-                     (const T *)labels, graph, big, sx, sy, sz, ndim, bb)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: LAUNCH_VG(uint8_t); break;
-    case EDT_U16: LAUNCH_VG(uint16_t); break;
-    case EDT_U32: LAUNCH_VG(uint32_t); break;
-    case EDT_U64: LAUNCH_VG(uint64_t); break;
-    case EDT_F32: LAUNCH_VG(float); break;
-    case EDT_F64: LAUNCH_VG(double); break;
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef LAUNCH_VG
-  EDT_HIP_TRY(hipGetLastError());
-  return EDT_OK;
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(k_vg_expand<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, graph, big, sx, sy,
+                       sz, ndim, bb);
+    EDT_HIP_TRY(hipGetLastError());
+    return EDT_OK;
+  });
 }
 
 int launch_vg_gather(const float *big, float *out, int64_t sx, int64_t sy, int64_t sz, int ndim,
@@ -596,18 +588,9 @@ static int vg_native_t(const void *labels_, const uint8_t *graph, int ndim, int6
 
 int launch_vg_native(int dtype, const void *labels, const uint8_t *graph, int ndim, int64_t sx, int64_t sy, int64_t sz,
                      float wx, float wy, float wz, int bb, int want_sqrt, float *out, void *ws, hipStream_t stream) {
-#define VG_NATIVE(T) \
-  return vg_native_t<T>(labels, graph, ndim, sx, sy, sz, wx, wy, wz, bb, want_sqrt, out, ws, stream)
-  switch (dtype) {
-    case EDT_U8: case EDT_BOOL: VG_NATIVE(uint8_t);
-    case EDT_U16: VG_NATIVE(uint16_t);
-    case EDT_U32: VG_NATIVE(uint32_t);
-    case EDT_U64: VG_NATIVE(uint64_t);
-    case EDT_F32: VG_NATIVE(float);
-    case EDT_F64: VG_NATIVE(double);
-    default: set_error("unknown dtype"); return EDT_ERR_BAD_ARG;
-  }
-#undef VG_NATIVE
+  return with_label_type(dtype, [&](auto t) {
+    return vg_native_t<typename decltype(t)::type>(labels, graph, ndim, sx, sy, sz, wx, wy, wz, bb, want_sqrt, out, ws, stream);
+  });
 }
 
 }  // namespace edt_amd

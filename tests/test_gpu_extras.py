@@ -306,3 +306,95 @@ def test_device_entry_points_take_dlpack_and_cuda_array_interface(edt_gpu, oracl
         device.edtsq(np.zeros((4, 4), np.uint8))      # a host array: not this module's business
     with pytest.raises(TypeError):
         device.edtsq([[1, 2], [3, 4]])
+
+
+# ---- host-buffer staging: the pooled device buffers by role, their growth and reuse, allocate-per-call, a list of one ------
+def _staging_inputs():
+    rng = np.random.default_rng(2024)
+    small = np.asfortranarray(blocky_labels((40, 24, 33), nlabels=6, zero_frac=0.25, block=5, rng=rng).astype(np.uint32))
+    line = blocky_labels((5000,), nlabels=4, zero_frac=0.4, block=37, rng=rng).astype(np.uint16)
+    mid = blocky_labels((64, 80, 72), nlabels=7, zero_frac=0.2, block=9, rng=rng).astype(np.uint8)
+    graph = np.full(mid.shape, 0b00111111, dtype=np.uint8)
+    for bit in (0x01, 0x04, 0x10):
+        graph[rng.random(mid.shape) < 0.1] &= np.uint8(~bit & 0xFF)
+    large = blocky_labels((96, 280, 24), nlabels=5, zero_frac=0.2, block=11, rng=rng).astype(np.uint32)
+    return small, line, mid, graph, large
+
+
+@pytest.fixture(scope="module")
+def staging_case(oracle_port):
+    """inputs of the staging sequence and what the oracles say (oracle_port, tests/ft_oracle.py, tests/label_stats_oracle.py)"""
+    import ft_oracle
+    import label_stats_oracle
+    small, line, mid, graph, large = inputs = _staging_inputs()
+    feats, _ = ft_oracle.feature_transform(small, (1, 1, 1), False)            # (F order: x is axis 0, as the oracle indexes)
+    # expand_labels by its definition (include/edt_hip.h) from the oracle's features of the background mask
+    f, _ = ft_oracle.feature_transform((small == 0).astype(np.uint8), (1, 1, 1), False)
+    grids = np.stack(np.meshgrid(*[np.arange(s) for s in small.shape], indexing="ij"))
+    take = (small == 0) & ~np.all(f == -1, axis=0) & (((grids - f) ** 2).sum(axis=0) <= 3.0 * 3.0)
+    expanded = small.copy()
+    expanded[take] = small[tuple(np.where(take, f[k], 0) for k in range(3))][take]
+    want = [oracle_port.edtsq(small, (1.0, 2.0, 3.0), True), oracle_port.sdf(line, 2.0, False),
+            oracle_port.edtsq(mid, (1.0, 1.0, 2.0), False, voxel_graph=graph), feats.astype(np.int32), expanded,
+            label_stats_oracle.label_stats(mid, np.sqrt(oracle_port.edtsq(mid, (2.0, 1.0, 1.0), True))),
+            oracle_port.edtsq(large, (6.0, 6.0, 30.0), False)]
+    return inputs, want
+
+
+def _staging_sequence(edt, inputs, between):
+    """the host-buffer entry points one after another: every pooled slot first small, then grown, then reused by another
+    entry point for another role (the mask of sdf, the graph, the label-stats table share one)"""
+    small, line, mid, graph, large = inputs
+    steps = [lambda: edt.edtsq(small, anisotropy=(1.0, 2.0, 3.0), black_border=True),
+             lambda: edt.sdf(line, anisotropy=2.0, black_border=False),     # (1-D: two transforms, mask and second field)
+             lambda: edt.edtsq(mid, anisotropy=(1.0, 1.0, 2.0), black_border=False, voxel_graph=graph),
+             lambda: edt.feature_transform(small),
+             lambda: edt.expand_labels(small, distance=3.0),
+             lambda: edt.label_stats(mid, anisotropy=(2.0, 1.0, 1.0), black_border=True),
+             lambda: edt.edtsq(large, anisotropy=(6.0, 6.0, 30.0), black_border=False)]
+    got = []
+    for step in steps:
+        got.append(step())
+        between()
+    return got
+
+
+def _same_bytes(a, b):
+    if isinstance(a, tuple):
+        return len(a) == len(b) and all(_same_bytes(x, y) for x, y in zip(a, b))
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def test_host_staging_pool_growth_reuse_and_no_cache(edt_gpu, staging_case, monkeypatch):
+    import label_stats_oracle
+    from edt import _lib
+    lib = _lib.load()
+    inputs, want = staging_case
+    import torch
+    # a device list of one: that device runs the call, and the caller's current device is the same before and after.  Where the
+    # box has a second device it is made current first, so that the call has to switch to the listed one and back; on a box
+    # with one device the listed device IS the current one and only the no-switch path runs.
+    entered_on = torch.cuda.current_device()
+    torch.cuda.set_device(_lib.device_count() - 1)
+    try:
+        edt_gpu.set_devices([0])
+        before = torch.cuda.current_device()
+        listed = edt_gpu.edtsq(inputs[0], anisotropy=(1.0, 2.0, 3.0), black_border=True)
+        assert torch.cuda.current_device() == before
+    finally:
+        edt_gpu.set_devices(None)
+        torch.cuda.set_device(entered_on)
+    assert np.array_equal(listed, want[0])
+    lib.edt_hip_release_cache()                     # (every slot starts empty, whatever ran before in this process)
+    runs = {"pooled": _staging_sequence(edt_gpu, inputs, lambda: None),
+            "released between calls": _staging_sequence(edt_gpu, inputs, lambda: lib.edt_hip_release_cache())}
+    monkeypatch.setenv("EDT_HIP_NO_CACHE", "1")     # (read per call: private allocations, freed at return)
+    runs["allocate per call"] = _staging_sequence(edt_gpu, inputs, lambda: None)
+    monkeypatch.delenv("EDT_HIP_NO_CACHE")
+    for how, got in runs.items():
+        for i, (g, w) in enumerate(zip(got, want)):
+            if i == 5:
+                label_stats_oracle.assert_same(g, w, how)
+            else:
+                assert g.shape == w.shape and g.dtype == w.dtype and np.array_equal(g, w, equal_nan=True), (how, i)
+        assert all(_same_bytes(g, p) for g, p in zip(got, runs["pooled"])), how
