@@ -17,7 +17,7 @@ namespace edt_amd {
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
 // what a pooled buffer is for -- one slot each, so two roles never share memory within a call
-enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table */, kSecondField, kSlotCount };
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component count */, kSecondField, kSlotCount };
 struct DevicePool {
   static constexpr int kSlots = kSlotCount;
   void *p[kSlots] = {};
@@ -390,6 +390,32 @@ static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx,
   return st.down(bbox, kAux, m * 24, o_bbox);
 }
 
+// connected_components on host buffers (kernels: edt_components.hip): labels up once, the union-find on the device, the
+// numbers and their count down once.
+static int components_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
+                           int binary, uint32_t *out, int64_t *n) {
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !out, &empty, [&](After what) -> int {
+    if (what == After::shape) return components_check_args(dtype, ndim, sx, sy, sz, connectivity);
+    if (what == After::voxel_sizes && !n) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    return EDT_OK;
+  });
+  if (rc == EDT_OK && empty) *n = 0;
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), obytes = voxels * sizeof(uint32_t);
+  const size_t wbytes = edt_hip_components_workspace_bytes(dtype, ndim, sx, sy, sz);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}, {kAux, sizeof(int64_t)}})) != EDT_OK) return rc;
+  st.expect(out, obytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = edt_hip_connected_components_device(st.p[kLabels], dtype, ndim, sx, sy, sz, connectivity, binary, st.at<uint32_t>(kOut),
+                                           st.at<int64_t>(kAux), st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(out, kOut, obytes)) != EDT_OK) return rc;
+  return st.down(n, kAux, sizeof(int64_t));
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -539,6 +565,11 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
                         float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels) {
   return label_stats_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, black_border, dt, max_labels, keys, counts, max,
                           argmax, bbox, n_labels);
+}
+
+int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                                 int connectivity, int binary, uint32_t *out, int64_t *n) {
+  return components_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, out, n);
 }
 
 }  // extern "C"

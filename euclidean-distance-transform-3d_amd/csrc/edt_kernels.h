@@ -269,3 +269,13 @@ void multi_release();  // frees the per-slot pool (edt_hip_release_cache)
 int run_multi(const void *labels, int dtype, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
               int flags, float *output, const int *devices, int n_devices);
 }  // namespace edt_amd
+
+namespace edt_amd {
+// ---- connected components (run-based union-find, the output array is the parent array): edt_components.hip ----------
+size_t components_workspace_bytes(int64_t voxels);  // the per-chunk root counts of the numbering scan
+// shape, connectivity in 1..ndim, sx * sy * sz <= 2^31 - 1: what both entry points refuse before they look at a pointer
+int components_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity);
+// rows, merge, flatten, scan, number, final on `stream`; out: sx * sy * sz uint32 (not the labels), n: one int64, both on the device
+int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                      uint32_t *out, int64_t *n, void *ws, hipStream_t stream);
+}  // namespace edt_amd

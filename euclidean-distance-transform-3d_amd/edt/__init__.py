@@ -36,7 +36,7 @@ __all__ = [
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
-    "label_stats",
+    "label_stats", "connected_components",
 ]
 
 
@@ -316,6 +316,58 @@ def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, 
     if order == "C":                       # x is the LAST array axis
         lo, hi = lo[:, ::-1], hi[:, ::-1]
     return LabelStats(np.ascontiguousarray(keys), counts, mx, argmax, np.ascontiguousarray(lo), np.ascontiguousarray(hi))
+
+
+_NEIGHBOUR_COUNTS = {2: {4: 1, 8: 2}, 3: {6: 1, 18: 2, 26: 3}}   # cc3d's spelling of the connectivity
+
+
+def _connectivity(connectivity, ndim):
+    """The ABI's connectivity (1..ndim) of a call: None is full; 1..ndim as in skimage; cc3d's neighbour counts 4 / 8
+    (2-D) and 6 / 18 / 26 (3-D).  Anything else is a ValueError."""
+    if connectivity is None:
+        return ndim
+    if isinstance(connectivity, (int, np.integer)) and not isinstance(connectivity, (bool, np.bool_)):
+        c = int(connectivity)
+        if 1 <= c <= ndim:
+            return c
+        if c in _NEIGHBOUR_COUNTS.get(ndim, {}):
+            return _NEIGHBOUR_COUNTS[ndim][c]
+    raise ValueError(f"connected_components: connectivity of a {ndim}-D array is None, 1..{ndim}"
+                     + (f" or one of {sorted(_NEIGHBOUR_COUNTS[ndim])}" if ndim in _NEIGHBOUR_COUNTS else "")
+                     + f", got {connectivity!r}")
+
+
+def connected_components(data, connectivity=None, binary=False, return_N=False):
+    """Connected components of a 1-D to 3-D label array on the device (cc3d.connected_components /
+    skimage.measure.label / scipy.ndimage.label; contract: include/edt_hip.h, "connected components").  Two neighbouring
+    voxels belong to one component iff their labels are equal and non-zero; ``binary=True`` treats every non-zero voxel as
+    one class (``scipy.ndimage.label(data != 0)``; a bool array is always binary).  ``-0.0`` is background; a NaN voxel
+    is a component of its own, and joins its neighbours under ``binary``.
+
+    ``connectivity``: ``None`` is full (``data.ndim``); ``1..ndim`` is the number of axes along which neighbours may
+    differ (skimage); cc3d's neighbour counts ``4`` / ``8`` (2-D) and ``6`` / ``18`` / ``26`` (3-D) are accepted too.
+
+    Returns a ``uint32`` array of ``data``'s shape and memory order: 0 for background, else the component's number in
+    ``1..N``; with ``return_N=True`` the pair ``(out, N)``.  Components are numbered in the order in which a scan of the
+    array's MEMORY meets them: for a C-contiguous array and ``binary`` that is scipy's numbering, for an F-contiguous one
+    (also one that is C-contiguous as well, e.g. with unit axes, as in every entry point of this module) cc3d's.  At most
+    2^31 - 1 voxels."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"connected_components: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    nd = data.ndim
+    _label_code(data)
+    c = _connectivity(connectivity, nd)
+    if data.size == 0:
+        out = np.zeros(data.shape, dtype=np.uint32)
+        return (out, 0) if return_N else out
+    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    out = np.empty(data.shape, dtype=np.uint32, order=order)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().edt_hip_connected_components(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0,
+                                                        _ptr(out), ctypes.byref(n)))
+    return (out, int(n.value)) if return_N else out
 
 
 def set_devices(devices=None):

@@ -509,6 +509,53 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
     return LabelStats(keys, counts, mx, argmax, lo, hi)
 
 
+_cc_workspaces: dict = {}
+
+
+def _components_workspace(ext, code, nd, device) -> torch.Tensor:
+    # one scratch buffer per shape and stream (a workspace is only ever used on the stream it was allocated for); at most 9 are
+    # kept, and the one cached longest ago makes room for a new one
+    key = (tuple(ext), code, str(device), torch.cuda.current_stream(device).cuda_stream)
+    if key not in _cc_workspaces:
+        nbytes = _lib.load().edt_hip_components_workspace_bytes(code, nd, *ext)
+        if nbytes == 0:
+            raise ValueError(f"connected_components: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
+        if len(_cc_workspaces) > 8:
+            del _cc_workspaces[next(iter(_cc_workspaces))]
+        _cc_workspaces[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return _cc_workspaces[key]
+
+
+def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
+    """:func:`edt.connected_components` on a device array (semantics of a C-ordered array: the last tensor axis is
+    fastest, and components are numbered in the tensor's memory order; contract: include/edt_hip.h, "connected
+    components").  Returns ``(out, n)``: ``out`` an int32 tensor of the labels' shape -- 0 for background, else the
+    component's number in ``1..N`` (at most 2^31 - 1 voxels, so the numbers fit) -- and ``n`` a 0-dim int64 DEVICE tensor
+    holding ``N``: the call only enqueues kernels on the current stream, nothing is read back and nothing waits.  The
+    scratch (one word per 2048 voxels) is cached per shape and stream.
+
+    The result composes without leaving the device: ``label_stats(out, dt)`` is then a table per OBJECT,
+    ``each(out, dt)`` yields one image per object, and ``edt(out)`` is the transform of the instances."""
+    from . import _connectivity
+    labels = as_device_tensor(labels)
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"connected_components: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    nd = labels.dim()
+    code = dtype_code(labels.dtype)
+    c = _connectivity(connectivity, nd)
+    out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    if labels.numel() == 0:
+        return out, torch.zeros((), dtype=torch.int64, device=labels.device)
+    n = torch.empty((), dtype=torch.int64, device=labels.device)
+    labels = labels.contiguous()
+    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+    ws = _components_workspace(ext, code, nd, labels.device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    _lib.check(_lib.load().edt_hip_connected_components_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, vp(out),
+                                                               vp(n), vp(ws), ws.numel(), _stream_ptr()))
+    return out, n
+
+
 def pass_times():
     """Durations (ms) of the kernels of the last profiled call, as ``[(name, ms), ...]``."""
     lib = _lib.load()

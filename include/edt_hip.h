@@ -437,6 +437,40 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
                         float wz, int black_border, const float *dt, int64_t max_labels, void *keys, int64_t *counts,
                         float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels);
 
+/* ---- connected components: multi-label component labelling on the device ---------------------------------------------
+ * Conventions as above: x fastest, idx = x + sx * (y + sy * z), label 0 is background.
+ * Adjacency: connectivity = c, 1 <= c <= ndim.  Two voxels are neighbours if their coordinates differ by at most 1 along
+ *   every axis, and along at most c axes: 1-D 2 neighbours; 2-D 4 (c = 1) or 8 (c = 2); 3-D 6, 18 or 26.
+ * Connection: neighbours p, q are connected iff label(p) == label(q) and label(p) != 0 -- compared at full width with the
+ *   type's ==, as everywhere.  Floats: -0.0 is background; a NaN voxel is foreground and equals nothing, so it is a
+ *   component of its own.  EDT_BOOL: any non-zero byte is the one foreground label (bytes 1 and 2 join).  binary != 0:
+ *   every non-zero voxel is one class, for every dtype (scipy.ndimage.label of data != 0; NaN is non-zero).
+ * Output: one uint32 per voxel -- 0 where the label is background, otherwise the component's number in 1..N.  Components
+ *   are numbered in ascending order of the smallest idx among their voxels (raster order of first encounter along the
+ *   memory order).  *n receives N as int64.
+ * Determinism: the same call gives the same output, bit for bit.  Which thread wins an atomic may decide the shape of the
+ *   intermediate union-find forest, never the result: the root of a component is its smallest idx, and that is unique.
+ * Limits: sx * sy * sz <= 2^31 - 1 (parents and numbers are 32-bit; a root carries its number with the top bit set until
+ *   the last sweep strips it).  For a larger volume the workspace query returns 0 and the entry points return
+ *   EDT_ERR_UNSUPPORTED; the check is made in 64-bit arithmetic before any device work.  Byte offsets are 64-bit. */
+
+/* Scratch of edt_hip_connected_components_device: the output array itself serves as the parent array of the union-find,
+ * so nothing per voxel -- one uint32 for every 2048 voxels (the per-workgroup root counts of the numbering scan), rounded
+ * up to 256 bytes.  0 for a bad dtype or shape, or a volume past the limit. */
+size_t edt_hip_components_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
+/* Refused before any device work, in this order: bad dtype, ndim outside 1..3, unused extents not 1 (EDT_ERR_BAD_ARG);
+ * connectivity outside 1..ndim (EDT_ERR_BAD_ARG); a volume past the limit (EDT_ERR_UNSUPPORTED); NULL pointers, a missing
+ * or too small workspace (EDT_ERR_BAD_ARG).  Enqueue-only on `stream`: no allocation, no synchronisation; the workspace is
+ * initialised by the call itself (a reused one needs no memset).  d_out may not alias the labels.  d_n: one int64 on the
+ * device.  An empty volume only sets *d_n = 0. */
+int edt_hip_connected_components_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                                        int connectivity, int binary, uint32_t *d_out, int64_t *d_n,
+                                        void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, out and n down once.  An empty volume sets *n = 0. */
+int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                                 int connectivity, int binary, uint32_t *out, int64_t *n);
+
 #ifdef __cplusplus
 }
 #endif
