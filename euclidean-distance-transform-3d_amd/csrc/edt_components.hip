@@ -332,6 +332,36 @@ int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int
   return EDT_OK;
 }
 
+// The forest alone -- rows, merge, flatten, no numbering -- of a volume of 0/1 bytes: fill_holes (edt_fillholes.hip) runs it over
+// the mask labels == 0.  Afterwards P[i] is the smallest idx of i's component for every non-zero byte and kCcBg elsewhere.
+int launch_components_forest(const uint8_t *mask, int64_t sx, int64_t sy, int64_t sz, int connectivity, uint32_t *P, void *ws,
+                             hipStream_t stream) {
+  const int64_t voxels64 = sx * sy * sz;
+  if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error("components forest: volume out of range"); return EDT_ERR_UNSUPPORTED; }
+  const uint32_t voxels = (uint32_t)voxels64;
+  const int waves = kCcThreads / 64;
+  {
+    ScopedPass sp("fill_holes rows", stream);
+    const int64_t blocks = std::min<int64_t>(ceil_div(ceil_div(voxels64, kCcTile), waves), kCcBlocks);
+    hipLaunchKernelGGL(k_cc_rows<uint8_t>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, mask, P, voxels, (uint32_t)sx, 1);
+    EDT_HIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedPass sp("fill_holes merge", stream);
+    const int64_t blocks = std::min<int64_t>(ceil_div(voxels64, kCcThreads), kCcBlocks * 4);
+    hipLaunchKernelGGL(k_cc_merge<uint8_t>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, mask, P, voxels, (uint32_t)sx,
+                       (uint32_t)sy, connectivity, 1);
+    EDT_HIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedPass sp("fill_holes flatten", stream);
+    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, voxels,
+                       static_cast<uint32_t *>(ws));
+    EDT_HIP_TRY(hipGetLastError());
+  }
+  return EDT_OK;
+}
+
 // sx * sy * sz <= 2^31 - 1, in 64-bit arithmetic (extents are at most 2^31 - 1 each: check_shape)
 static bool cc_volume_fits(int64_t sx, int64_t sy, int64_t sz) {
   if (sx == 0 || sy == 0 || sz == 0) return true;
@@ -339,13 +369,14 @@ static bool cc_volume_fits(int64_t sx, int64_t sy, int64_t sz) {
   return sx * sy <= kCcMaxVoxels / sz;
 }
 
-// shape, then the call's own arguments: what both entry points refuse before they look at a pointer
-int components_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity) {
+// shape, then the call's own arguments: what both entry points refuse before they look at a pointer (who: the caller's name in
+// the message -- fill_holes refuses the same things in the same order)
+int components_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, const char *who) {
   const int rc = check_shape(dtype, ndim, sx, sy, sz);
   if (rc != EDT_OK) return rc;
-  if (connectivity < 1 || connectivity > ndim) { set_error("connected_components: connectivity must be in 1..ndim"); return EDT_ERR_BAD_ARG; }
+  if (connectivity < 1 || connectivity > ndim) { set_error(std::string(who) + ": connectivity must be in 1..ndim"); return EDT_ERR_BAD_ARG; }
   if (!cc_volume_fits(sx, sy, sz)) {
-    set_error("connected_components: more than 2^31 - 1 voxels (parents and numbers are 32-bit)");
+    set_error(std::string(who) + ": more than 2^31 - 1 voxels (parents and numbers are 32-bit)");
     return EDT_ERR_UNSUPPORTED;
   }
   return EDT_OK;

@@ -17,7 +17,7 @@ namespace edt_amd {
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
 // what a pooled buffer is for -- one slot each, so two roles never share memory within a call
-enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component count */, kSecondField, kSlotCount };
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count */, kSecondField, kSlotCount };
 struct DevicePool {
   static constexpr int kSlots = kSlotCount;
   void *p[kSlots] = {};
@@ -416,6 +416,33 @@ static int components_host(const void *labels, int dtype, int ndim, int64_t sx, 
   return st.down(n, kAux, sizeof(int64_t));
 }
 
+// fill_holes on host buffers (kernels: edt_fillholes.hip): labels up once, the background's forest and the fill on the device,
+// the filled labels and their count down once.
+static int fill_holes_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
+                           int binary, void *out, int64_t *n_filled) {
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !out, &empty, [&](After what) -> int {
+    if (what == After::shape) return components_check_args(dtype, ndim, sx, sy, sz, connectivity, "fill_holes");
+    if (what == After::voxel_sizes && !n_filled) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    if (what == After::pointers && labels == out) { set_error("fill_holes: the output may not alias the labels"); return EDT_ERR_BAD_ARG; }
+    return EDT_OK;
+  });
+  if (rc == EDT_OK && empty) *n_filled = 0;
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
+  const size_t wbytes = edt_hip_fill_holes_workspace_bytes(dtype, ndim, sx, sy, sz);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}, {kAux, sizeof(int64_t)}})) != EDT_OK) return rc;
+  st.expect(out, lbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = edt_hip_fill_holes_device(st.p[kLabels], dtype, ndim, sx, sy, sz, connectivity, binary, st.p[kOut], st.at<int64_t>(kAux),
+                                 st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(out, kOut, lbytes)) != EDT_OK) return rc;
+  return st.down(n_filled, kAux, sizeof(int64_t));
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -570,6 +597,11 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
 int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
                                  int connectivity, int binary, uint32_t *out, int64_t *n) {
   return components_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, out, n);
+}
+
+int edt_hip_fill_holes(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                       void *out, int64_t *n_filled) {
+  return fill_holes_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, out, n_filled);
 }
 
 }  // extern "C"

@@ -274,8 +274,13 @@ namespace edt_amd {
 // ---- connected components (run-based union-find, the output array is the parent array): edt_components.hip ----------
 size_t components_workspace_bytes(int64_t voxels);  // the per-chunk root counts of the numbering scan
 // shape, connectivity in 1..ndim, sx * sy * sz <= 2^31 - 1: what both entry points refuse before they look at a pointer
-int components_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity);
+int components_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
+                          const char *who = "connected_components");
 // rows, merge, flatten, scan, number, final on `stream`; out: sx * sy * sz uint32 (not the labels), n: one int64, both on the device
 int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                       uint32_t *out, int64_t *n, void *ws, hipStream_t stream);
+// rows, merge, flatten alone over a volume of 0/1 bytes: P[i] = the smallest idx of i's component (0xFFFFFFFF for a zero byte);
+// ws: components_workspace_bytes.  The background forest of fill_holes (edt_fillholes.hip)
+int launch_components_forest(const uint8_t *mask, int64_t sx, int64_t sy, int64_t sz, int connectivity, uint32_t *P, void *ws,
+                             hipStream_t stream);
 }  // namespace edt_amd

@@ -36,7 +36,7 @@ __all__ = [
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
-    "label_stats", "connected_components",
+    "label_stats", "connected_components", "fill_holes",
 ]
 
 
@@ -321,18 +321,18 @@ def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, 
 _NEIGHBOUR_COUNTS = {2: {4: 1, 8: 2}, 3: {6: 1, 18: 2, 26: 3}}   # cc3d's spelling of the connectivity
 
 
-def _connectivity(connectivity, ndim):
-    """The ABI's connectivity (1..ndim) of a call: None is full; 1..ndim as in skimage; cc3d's neighbour counts 4 / 8
-    (2-D) and 6 / 18 / 26 (3-D).  Anything else is a ValueError."""
+def _connectivity(connectivity, ndim, default=None, who="connected_components"):
+    """The ABI's connectivity (1..ndim) of a call: None is `default` (itself None: full); 1..ndim as in skimage; cc3d's
+    neighbour counts 4 / 8 (2-D) and 6 / 18 / 26 (3-D).  Anything else is a ValueError."""
     if connectivity is None:
-        return ndim
+        return ndim if default is None else default
     if isinstance(connectivity, (int, np.integer)) and not isinstance(connectivity, (bool, np.bool_)):
         c = int(connectivity)
         if 1 <= c <= ndim:
             return c
         if c in _NEIGHBOUR_COUNTS.get(ndim, {}):
             return _NEIGHBOUR_COUNTS[ndim][c]
-    raise ValueError(f"connected_components: connectivity of a {ndim}-D array is None, 1..{ndim}"
+    raise ValueError(f"{who}: connectivity of a {ndim}-D array is None, 1..{ndim}"
                      + (f" or one of {sorted(_NEIGHBOUR_COUNTS[ndim])}" if ndim in _NEIGHBOUR_COUNTS else "")
                      + f", got {connectivity!r}")
 
@@ -368,6 +368,38 @@ def connected_components(data, connectivity=None, binary=False, return_N=False):
     _lib.check(_lib.load().edt_hip_connected_components(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0,
                                                         _ptr(out), ctypes.byref(n)))
     return (out, int(n.value)) if return_N else out
+
+
+def fill_holes(data, connectivity=None, binary=False, return_fill_count=False):
+    """Fill the enclosed cavities of a 1-D to 3-D label array on the device (fill_voids.fill /
+    scipy.ndimage.binary_fill_holes, for every label at once; contract: include/edt_hip.h, "fill holes").  A cavity is a
+    connected component of zero voxels that does not touch the array's boundary; it takes the label of the voxels around
+    it if they all carry one label, and stays 0 if they carry several (or a NaN).  ``binary=True`` fills every cavity
+    with the label of its first wall voxel in memory order -- ``binary_fill_holes(data != 0)`` for a mask; a bool array
+    is always binary.  ``-0.0`` is background.  Enclosed foreground is never touched.
+
+    ``connectivity`` is the adjacency of the BACKGROUND: ``None`` means **1** (the background is 2 * ndim-connected:
+    scipy's default structure and fill_voids' rule) -- NOT the full connectivity that ``None`` means for
+    :func:`connected_components`.  ``1..ndim`` and cc3d's ``4`` / ``8``, ``6`` / ``18`` / ``26`` are accepted as there.
+
+    Returns an array of ``data``'s dtype, shape and memory order; with ``return_fill_count=True`` the pair
+    ``(out, n)``, ``n`` the number of voxels that were filled.  At most 2^31 - 1 voxels."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"fill_holes: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    nd = data.ndim
+    _label_code(data)
+    c = _connectivity(connectivity, nd, default=1, who="fill_holes")
+    if data.size == 0:
+        out = data.copy()
+        return (out, 0) if return_fill_count else out
+    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    out = np.empty(data.shape, dtype=data.dtype, order=order)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().edt_hip_fill_holes(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, _ptr(out),
+                                              ctypes.byref(n)))
+    return (out, int(n.value)) if return_fill_count else out
 
 
 def set_devices(devices=None):

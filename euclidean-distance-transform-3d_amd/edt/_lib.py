@@ -104,6 +104,9 @@ SIGNATURES = {
     "edt_hip_components_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
     "edt_hip_connected_components_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_connected_components": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
+    "edt_hip_fill_holes_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
+    "edt_hip_fill_holes_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "edt_hip_fill_holes": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
 }
 
 _lib = None

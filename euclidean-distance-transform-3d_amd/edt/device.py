@@ -556,6 +556,50 @@ def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
     return out, n
 
 
+_fh_workspaces: dict = {}
+
+
+def _fill_holes_workspace(ext, code, nd, device) -> torch.Tensor:
+    # as _components_workspace: one scratch buffer per shape and stream, at most 9 kept
+    key = (tuple(ext), code, str(device), torch.cuda.current_stream(device).cuda_stream)
+    if key not in _fh_workspaces:
+        nbytes = _lib.load().edt_hip_fill_holes_workspace_bytes(code, nd, *ext)
+        if nbytes == 0:
+            raise ValueError(f"fill_holes: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
+        if len(_fh_workspaces) > 8:
+            del _fh_workspaces[next(iter(_fh_workspaces))]
+        _fh_workspaces[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return _fh_workspaces[key]
+
+
+def fill_holes(labels: torch.Tensor, connectivity=None, binary=False):
+    """:func:`edt.fill_holes` on a device array (semantics of a C-ordered array: the last tensor axis is fastest;
+    contract: include/edt_hip.h, "fill holes").  ``connectivity=None`` means 1, the adjacency of the background.
+    Returns ``(out, n_filled)``: ``out`` a new tensor of the labels' dtype and shape, ``n_filled`` a 0-dim int64 DEVICE
+    tensor: the call only enqueues kernels on the current stream, nothing is read back and nothing waits.  The scratch
+    (4 bytes per voxel) is cached per shape and stream.
+
+    ``edt(fill_holes(x)[0])`` is then the transform of the filled segmentation without a trip to the host."""
+    from . import _connectivity
+    labels = as_device_tensor(labels)
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"fill_holes: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    nd = labels.dim()
+    code = dtype_code(labels.dtype)
+    c = _connectivity(connectivity, nd, default=1, who="fill_holes")
+    if labels.numel() == 0:
+        return labels.clone(), torch.zeros((), dtype=torch.int64, device=labels.device)
+    labels = labels.contiguous()
+    out = torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
+    n = torch.empty((), dtype=torch.int64, device=labels.device)
+    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+    ws = _fill_holes_workspace(ext, code, nd, labels.device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    _lib.check(_lib.load().edt_hip_fill_holes_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, vp(out), vp(n),
+                                                     vp(ws), ws.numel(), _stream_ptr()))
+    return out, n
+
+
 def pass_times():
     """Durations (ms) of the kernels of the last profiled call, as ``[(name, ms), ...]``."""
     lib = _lib.load()

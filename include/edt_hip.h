@@ -471,6 +471,49 @@ int edt_hip_connected_components_device(const void *d_labels, int dtype, int ndi
 int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
                                  int connectivity, int binary, uint32_t *out, int64_t *n);
 
+/* ---- fill holes: the enclosed cavities of a multi-label volume take the label of their wall ----------------------------
+ * Conventions as in the connected-components section: x fastest, idx = x + sx * (y + sy * z), labels compared at full width
+ * with the type's ==.
+ * Background: a voxel whose label == 0.  -0.0 is background, NaN is foreground; for EDT_BOOL a zero byte is background.
+ * Adjacency: connectivity = c, 1 <= c <= ndim, defined as in the connected-components section -- here it is the adjacency
+ *   of the BACKGROUND (c = 1: the background is 2 * ndim-connected, scipy.ndimage.binary_fill_holes' default structure and
+ *   fill_voids' rule).
+ * Cavity: a connected component of background voxels, under c, none of whose voxels lies on the array's boundary --
+ *   coordinate 0 or extent - 1 along any of the ndim axes.  A 3-D array with an axis of extent 1 therefore has no cavity.
+ *   The cavities are what scipy.ndimage.binary_fill_holes(data != 0, generate_binary_structure(ndim, c)) fills.
+ * Wall: the foreground voxels adjacent, under the same c, to a voxel of the cavity.  Never empty.
+ * Representative: the wall voxel of smallest idx.
+ * Fill: with binary != 0, or with EDT_BOOL, every cavity voxel takes the representative's label.  Otherwise a cavity is
+ *   filled with the representative's label iff every wall voxel's label == it; a cavity whose wall holds two different
+ *   labels is MIXED and stays 0, and so does one whose wall holds a NaN (which equals nothing).  Enclosed foreground is
+ *   never touched: an island of label B inside label A is left alone.
+ * Output: the labels' dtype, shape and memory order; foreground voxels and unfilled background are copied bit for bit.
+ *   *n_filled (int64) is the number of voxels that changed from background to a label (a filled -0.0 voxel counts).
+ * Determinism: the same call gives the same bytes.  Every reduction is an integer max or add; which thread wins an atomic
+ *   never shows.
+ * Limits: sx * sy * sz <= 2^31 - 1, as for connected components (32-bit parents, and the top bit of a root's word tags the
+ *   state of its component).  Byte offsets are 64-bit. */
+
+/* Scratch of edt_hip_fill_holes_device: 4 bytes per voxel (the parent plane of the background's union-find; a root's word
+ * carries its component's state) plus the scratch of edt_hip_components_workspace_bytes, each rounded up to 256 bytes.
+ * The mask labels == 0 is kept in the output array until the last sweep overwrites it.  0 for a bad dtype or shape, or a
+ * volume past the limit. */
+size_t edt_hip_fill_holes_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
+/* Refused before any device work, in the order of edt_hip_connected_components_device and with its codes: bad dtype, ndim
+ * outside 1..3, unused extents not 1 (EDT_ERR_BAD_ARG); connectivity outside 1..ndim (EDT_ERR_BAD_ARG); a volume past the
+ * limit (EDT_ERR_UNSUPPORTED); NULL pointers, d_out == d_labels, a missing or too small workspace (EDT_ERR_BAD_ARG).
+ * Enqueue-only on `stream`: no allocation, no synchronisation; the workspace is initialised by the call itself.  d_out: a
+ * volume of the labels' dtype that does not overlap them.  d_n_filled: one int64 on the device.  An empty volume only sets
+ * *d_n_filled = 0. */
+int edt_hip_fill_holes_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
+                              int binary, void *d_out, int64_t *d_n_filled, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, out and n_filled down once.  An empty volume sets
+ * *n_filled = 0. */
+int edt_hip_fill_holes(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                       void *out, int64_t *n_filled);
+
 #ifdef __cplusplus
 }
 #endif
