@@ -35,8 +35,7 @@
 namespace edt_amd {
 namespace {
 
-constexpr uint32_t kCcBg = 0xFFFFFFFFu;   // background in P (a tagged rank is at most kCcTag | (2^31 - 2))
-constexpr uint32_t kCcTag = 0x80000000u;
+// (kCcBg, background in P, and kCcTag: edt_kernels.h -- a tagged rank is at most kCcTag | (2^31 - 2))
 constexpr int kCcThreads = 256;
 constexpr int kCcGroups = 4;                      // 64-voxel groups per wave and step (256-byte loads of 4-byte labels)
 constexpr int kCcTile = 64 * kCcGroups;
@@ -278,6 +277,37 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_final(uint32_t *P, uint32_t v
   P[i] = (p & kCcTag) ? (p & ~kCcTag) + 1u : p;
 }
 
+// rows, merge, flatten: the forest of `labels` in P, the per-chunk root counts in `chunk`.  names: the three passes in the log
+struct ForestNames {
+  const char *rows, *merge, *flatten;
+};
+template <typename T>
+int launch_forest(const T *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int bin, uint32_t *P, uint32_t *chunk,
+                  const ForestNames &names, hipStream_t stream) {
+  const int64_t voxels64 = sx * sy * sz;
+  const uint32_t voxels = (uint32_t)voxels64;
+  const int waves = kCcThreads / 64;
+  {
+    ScopedPass sp(names.rows, stream);
+    const int64_t blocks = std::min<int64_t>(ceil_div(ceil_div(voxels64, kCcTile), waves), kCcBlocks);
+    hipLaunchKernelGGL(k_cc_rows<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, labels, P, voxels, (uint32_t)sx, bin);
+    EDT_HIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedPass sp(names.merge, stream);
+    const int64_t blocks = std::min<int64_t>(ceil_div(voxels64, kCcThreads), kCcBlocks * 4);
+    hipLaunchKernelGGL(k_cc_merge<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, labels, P, voxels, (uint32_t)sx,
+                       (uint32_t)sy, connectivity, bin);
+    EDT_HIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedPass sp(names.flatten, stream);
+    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, voxels, chunk);
+    EDT_HIP_TRY(hipGetLastError());
+  }
+  return EDT_OK;
+}
+
 }  // namespace
 
 size_t components_workspace_bytes(int64_t voxels) {
@@ -291,32 +321,13 @@ int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int
   const uint32_t voxels = (uint32_t)voxels64;
   uint32_t *chunk = static_cast<uint32_t *>(ws);
   const uint32_t nchunks = (uint32_t)ceil_div(voxels64, kCcChunk);
-  const int waves = kCcThreads / 64;
   const int bin = (binary || dtype == EDT_BOOL) ? 1 : 0;
   const int rc = with_label_type(dtype, [&](auto t) -> int {
     using T = typename decltype(t)::type;
-    {
-      ScopedPass sp("components rows", stream);
-      const int64_t blocks = std::min<int64_t>(ceil_div(ceil_div(voxels64, kCcTile), waves), kCcBlocks);
-      hipLaunchKernelGGL(k_cc_rows<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, (const T *)labels, out, voxels,
-                         (uint32_t)sx, bin);
-      EDT_HIP_TRY(hipGetLastError());
-    }
-    {
-      ScopedPass sp("components merge", stream);
-      const int64_t blocks = std::min<int64_t>(ceil_div(voxels64, kCcThreads), kCcBlocks * 4);
-      hipLaunchKernelGGL(k_cc_merge<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, (const T *)labels, out, voxels,
-                         (uint32_t)sx, (uint32_t)sy, connectivity, bin);
-      EDT_HIP_TRY(hipGetLastError());
-    }
-    return EDT_OK;
+    return launch_forest((const T *)labels, sx, sy, sz, connectivity, bin, out, chunk,
+                         {"components rows", "components merge", "components flatten"}, stream);
   });
   if (rc != EDT_OK) return rc;
-  {
-    ScopedPass sp("components flatten", stream);
-    hipLaunchKernelGGL(k_cc_flatten, dim3(nchunks), dim3(kCcThreads), 0, stream, out, voxels, chunk);
-    EDT_HIP_TRY(hipGetLastError());
-  }
   {
     ScopedPass sp("components number", stream);
     hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kCcScan), 0, stream, chunk, nchunks, n);
@@ -338,28 +349,21 @@ int launch_components_forest(const uint8_t *mask, int64_t sx, int64_t sy, int64_
                              hipStream_t stream) {
   const int64_t voxels64 = sx * sy * sz;
   if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error("components forest: volume out of range"); return EDT_ERR_UNSUPPORTED; }
-  const uint32_t voxels = (uint32_t)voxels64;
-  const int waves = kCcThreads / 64;
-  {
-    ScopedPass sp("fill_holes rows", stream);
-    const int64_t blocks = std::min<int64_t>(ceil_div(ceil_div(voxels64, kCcTile), waves), kCcBlocks);
-    hipLaunchKernelGGL(k_cc_rows<uint8_t>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, mask, P, voxels, (uint32_t)sx, 1);
-    EDT_HIP_TRY(hipGetLastError());
-  }
-  {
-    ScopedPass sp("fill_holes merge", stream);
-    const int64_t blocks = std::min<int64_t>(ceil_div(voxels64, kCcThreads), kCcBlocks * 4);
-    hipLaunchKernelGGL(k_cc_merge<uint8_t>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, mask, P, voxels, (uint32_t)sx,
-                       (uint32_t)sy, connectivity, 1);
-    EDT_HIP_TRY(hipGetLastError());
-  }
-  {
-    ScopedPass sp("fill_holes flatten", stream);
-    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, voxels,
-                       static_cast<uint32_t *>(ws));
-    EDT_HIP_TRY(hipGetLastError());
-  }
-  return EDT_OK;
+  return launch_forest(mask, sx, sy, sz, connectivity, 1, P, static_cast<uint32_t *>(ws),
+                       {"fill_holes rows", "fill_holes merge", "fill_holes flatten"}, stream);
+}
+
+// ... and of labels of any dtype: dust (edt_dust.hip) sizes and filters the components themselves
+int launch_labels_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                         uint32_t *P, void *ws, hipStream_t stream) {
+  const int64_t voxels64 = sx * sy * sz;
+  if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error("labels forest: volume out of range"); return EDT_ERR_UNSUPPORTED; }
+  const int bin = (binary || dtype == EDT_BOOL) ? 1 : 0;
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    return launch_forest((const T *)labels, sx, sy, sz, connectivity, bin, P, static_cast<uint32_t *>(ws),
+                         {"dust rows", "dust merge", "dust flatten"}, stream);
+  });
 }
 
 // sx * sy * sz <= 2^31 - 1, in 64-bit arithmetic (extents are at most 2^31 - 1 each: check_shape)

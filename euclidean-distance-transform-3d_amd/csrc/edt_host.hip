@@ -443,6 +443,32 @@ static int fill_holes_host(const void *labels, int dtype, int ndim, int64_t sx, 
   return st.down(n_filled, kAux, sizeof(int64_t));
 }
 
+// dust on host buffers (kernels: edt_dust.hip): labels up once, the forest, the sizes and the filter on the device, the
+// filtered labels and the three counts down once.
+static int dust_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                     int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts) {
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !out, &empty, [&](After what) -> int {
+    if (what == After::shape) return dust_check_args(dtype, ndim, sx, sy, sz, connectivity, min_voxels, max_voxels);
+    if (what == After::voxel_sizes && !counts) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    return EDT_OK;
+  });
+  if (rc == EDT_OK && empty) counts[0] = counts[1] = counts[2] = 0;
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
+  const size_t wbytes = edt_hip_dust_workspace_bytes(dtype, ndim, sx, sy, sz);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}, {kAux, 3 * sizeof(int64_t)}})) != EDT_OK) return rc;
+  if (out != labels) st.expect(out, lbytes);  // (in place: the pages are the labels', and being read)
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = edt_hip_dust_device(st.p[kLabels], dtype, ndim, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, st.p[kOut],
+                           st.at<int64_t>(kAux), st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(out, kOut, lbytes)) != EDT_OK) return rc;
+  return st.down(counts, kAux, 3 * sizeof(int64_t));
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -602,6 +628,11 @@ int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_
 int edt_hip_fill_holes(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                        void *out, int64_t *n_filled) {
   return fill_holes_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, out, n_filled);
+}
+
+int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                 int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts) {
+  return dust_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, out, counts);
 }
 
 }  // extern "C"

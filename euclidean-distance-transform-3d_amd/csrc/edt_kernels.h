@@ -283,4 +283,15 @@ int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int
 // ws: components_workspace_bytes.  The background forest of fill_holes (edt_fillholes.hip)
 int launch_components_forest(const uint8_t *mask, int64_t sx, int64_t sy, int64_t sz, int connectivity, uint32_t *P, void *ws,
                              hipStream_t stream);
+// the same forest over labels of any dtype (binary as in launch_components): P[i] = the smallest idx of i's component for a
+// foreground voxel, kCcBg for background.  The forest of dust (edt_dust.hip); passes "dust rows / merge / flatten"
+int launch_labels_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                         uint32_t *P, void *ws, hipStream_t stream);
+// words of a parent plane: background, and the top bit that marks a root's word once it carries something else than itself
+constexpr uint32_t kCcBg = 0xFFFFFFFFu;
+constexpr uint32_t kCcTag = 0x80000000u;
+// ---- dust (components kept or removed by size; sizes in the roots' own words of the parent plane): edt_dust.hip ----------
+// what components_check_args refuses, then min_voxels < 0 and max_voxels < min_voxels
+int dust_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int64_t min_voxels,
+                    int64_t max_voxels);
 }  // namespace edt_amd

@@ -36,7 +36,7 @@ __all__ = [
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
-    "label_stats", "connected_components", "fill_holes",
+    "label_stats", "connected_components", "fill_holes", "dust", "DustCounts",
 ]
 
 
@@ -400,6 +400,59 @@ def fill_holes(data, connectivity=None, binary=False, return_fill_count=False):
     _lib.check(_lib.load().edt_hip_fill_holes(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, _ptr(out),
                                               ctypes.byref(n)))
     return (out, int(n.value)) if return_fill_count else out
+
+
+DustCounts = collections.namedtuple("DustCounts", ["components", "kept", "removed_voxels"])
+_NO_UPPER_BOUND = (1 << 63) - 1          # INT64_MAX: the ABI's "no upper bound"
+
+
+def _dust_bounds(threshold):
+    """(min_voxels, max_voxels) of the ABI from `threshold`: an integer t (sizes below t are removed) or a pair (lo, hi)
+    (lo <= size < hi is kept).  Anything else, a negative value or hi < lo is a ValueError."""
+    def integer(v):
+        return (isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+                and 0 <= int(v) <= _NO_UPPER_BOUND)
+
+    if integer(threshold):
+        return int(threshold), _NO_UPPER_BOUND
+    if (isinstance(threshold, (tuple, list)) and len(threshold) == 2 and integer(threshold[0]) and integer(threshold[1])
+            and int(threshold[0]) <= int(threshold[1])):
+        return int(threshold[0]), int(threshold[1])
+    raise ValueError(f"dust: threshold is a non-negative integer or a pair (lo, hi) of them with lo <= hi, got {threshold!r}")
+
+
+def dust(data, threshold, connectivity=None, binary=False, invert=False, return_counts=False):
+    """Remove the connected components of a 1-D to 3-D label array by their voxel count, on the device (cc3d.dust /
+    skimage.morphology.remove_small_objects; contract: include/edt_hip.h, "dust").  Neither cc3d nor skimage is on the
+    build machine: what is tested is the header's contract, not their behaviour.  A component is exactly a component of
+    :func:`connected_components` with the same ``connectivity`` and ``binary``: ``-0.0`` is background, a NaN voxel is a
+    component of its own (and joins its neighbours under ``binary``), a bool array is always binary.
+
+    ``threshold``: an integer ``t`` removes the components of fewer than ``t`` voxels; a pair ``(lo, hi)`` keeps those
+    with ``lo <= size < hi``.  ``invert=True`` removes what would be kept and keeps what would be removed.
+    ``connectivity`` as in :func:`connected_components`: ``None`` is full, ``1..ndim``, or cc3d's ``4`` / ``8``,
+    ``6`` / ``18`` / ``26``.
+
+    Returns an array of ``data``'s dtype, shape and memory order: the voxels of kept components and the background bit for
+    bit, the voxels of removed components zero.  With ``return_counts=True`` the pair
+    ``(out, DustCounts(components, kept, removed_voxels))`` of Python ints.  At most 2^31 - 1 voxels."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"dust: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    nd = data.ndim
+    _label_code(data)
+    lo, hi = _dust_bounds(threshold)
+    c = _connectivity(connectivity, nd, who="dust")
+    if data.size == 0:
+        out = data.copy()
+        return (out, DustCounts(0, 0, 0)) if return_counts else out
+    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    out = np.empty(data.shape, dtype=data.dtype, order=order)
+    counts = np.zeros(3, dtype=np.int64)
+    _lib.check(_lib.load().edt_hip_dust(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, lo, hi,
+                                        1 if invert else 0, _ptr(out), _ptr(counts)))
+    return (out, DustCounts(*(int(v) for v in counts))) if return_counts else out
 
 
 def set_devices(devices=None):

@@ -107,6 +107,9 @@ SIGNATURES = {
     "edt_hip_fill_holes_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
     "edt_hip_fill_holes_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_fill_holes": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
+    "edt_hip_dust_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
+    "edt_hip_dust_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "edt_hip_dust": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp]),
 }
 
 _lib = None

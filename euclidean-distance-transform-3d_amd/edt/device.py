@@ -559,13 +559,13 @@ def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
 _fh_workspaces: dict = {}
 
 
-def _fill_holes_workspace(ext, code, nd, device) -> torch.Tensor:
-    # as _components_workspace: one scratch buffer per shape and stream, at most 9 kept
+def _fill_holes_workspace(ext, code, nd, device, who="fill_holes") -> torch.Tensor:
+    # as _components_workspace: one scratch buffer per shape and stream, at most 9 kept (dust needs the same bytes and shares them)
     key = (tuple(ext), code, str(device), torch.cuda.current_stream(device).cuda_stream)
     if key not in _fh_workspaces:
         nbytes = _lib.load().edt_hip_fill_holes_workspace_bytes(code, nd, *ext)
         if nbytes == 0:
-            raise ValueError(f"fill_holes: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
+            raise ValueError(f"{who}: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
         if len(_fh_workspaces) > 8:
             del _fh_workspaces[next(iter(_fh_workspaces))]
         _fh_workspaces[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
@@ -598,6 +598,39 @@ def fill_holes(labels: torch.Tensor, connectivity=None, binary=False):
     _lib.check(_lib.load().edt_hip_fill_holes_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, vp(out), vp(n),
                                                      vp(ws), ws.numel(), _stream_ptr()))
     return out, n
+
+
+def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, invert=False, in_place=False):
+    """:func:`edt.dust` on a device array (semantics of a C-ordered array: the last tensor axis is fastest; contract:
+    include/edt_hip.h, "dust").  Neither cc3d nor skimage is on the build machine: what is tested is the header's contract,
+    not their behaviour.  Returns ``(out, counts)``: ``out`` a new tensor of the labels' dtype and shape -- under
+    ``in_place=True`` the (contiguous) input tensor itself, filtered where it lies -- and ``counts`` an int64[3] DEVICE
+    tensor (components found, components kept, voxels removed): the call only enqueues kernels on the current stream,
+    nothing is read back and nothing waits.  The scratch (4 bytes per voxel, the size of fill_holes') is cached per shape
+    and stream, together with fill_holes'.
+
+    ``edt(fill_holes(dust(x, t)[0])[0])`` is then the transform of the cleaned segmentation without a trip to the host."""
+    from . import _connectivity, _dust_bounds
+    labels = as_device_tensor(labels)
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"dust: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    nd = labels.dim()
+    code = dtype_code(labels.dtype)
+    lo, hi = _dust_bounds(threshold)
+    c = _connectivity(connectivity, nd, who="dust")
+    if in_place and not labels.is_contiguous():
+        raise ValueError("dust: in_place needs a contiguous tensor")
+    if labels.numel() == 0:
+        return (labels if in_place else labels.clone()), torch.zeros(3, dtype=torch.int64, device=labels.device)
+    labels = labels.contiguous()
+    out = labels if in_place else torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
+    counts = torch.empty(3, dtype=torch.int64, device=labels.device)
+    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+    ws = _fill_holes_workspace(ext, code, nd, labels.device, who="dust")   # (the same bytes: edt_hip_dust_workspace_bytes)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    _lib.check(_lib.load().edt_hip_dust_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, lo, hi, 1 if invert else 0,
+                                               vp(out), vp(counts), vp(ws), ws.numel(), _stream_ptr()))
+    return out, counts
 
 
 def pass_times():

@@ -514,6 +514,48 @@ int edt_hip_fill_holes_device(const void *d_labels, int dtype, int ndim, int64_t
 int edt_hip_fill_holes(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                        void *out, int64_t *n_filled);
 
+/* ---- dust: connected components are kept or removed by their voxel count ------------------------------------------------
+ * Conventions as in the connected-components section: x fastest, idx = x + sx * (y + sy * z), labels compared at full width
+ * with the type's ==; -0.0 is background; a NaN voxel is a component of its own, and joins its neighbours under binary;
+ * EDT_BOOL is always binary.
+ * Component: exactly a component of edt_hip_connected_components with the same connectivity and binary.  Its size is its
+ *   voxel count.
+ * Kept: a component is kept iff min_voxels <= size < max_voxels; with invert != 0 iff that does NOT hold.  max_voxels =
+ *   INT64_MAX means "no upper bound" (min_voxels = t, max_voxels = INT64_MAX is cc3d.dust(threshold = t) and
+ *   skimage.morphology.remove_small_objects(min_size = t)).
+ * Output: the labels' dtype, shape and memory order.  A voxel of a kept component keeps its label bit for bit (a NaN its
+ *   payload); a voxel of a removed component becomes all-zero bits; a background voxel is copied as it is (-0.0 keeps its
+ *   sign).
+ * Counts: three int64, in this order: components found, components kept, voxels removed.
+ * Determinism: the same call gives the same bytes and counts.  Every reduction is an integer add; which thread wins an
+ *   atomic never shows.
+ * Limits: sx * sy * sz <= 2^31 - 1, as for connected components (32-bit parents; a root's word carries its component's size
+ *   under the top bit).  Byte offsets are 64-bit. */
+
+/* Voxels a wave of the size-counting kernel walks.  The wave sums what it meets of a component before it adds to the root's
+ * word: a component costs it about one atomic add per span, however it is cut up (csrc/edt_dust.hip). */
+#define EDT_HIP_DUST_COUNT_SPAN 8192
+
+/* Scratch of edt_hip_dust_device: 4 bytes per voxel (the parent plane of the union-find; a root's own word carries its
+ * component's size, there is no second plane) plus the scratch of edt_hip_components_workspace_bytes, each rounded up to 256
+ * bytes -- what edt_hip_fill_holes_workspace_bytes gives.  0 for a bad dtype or shape, or a volume past the limit. */
+size_t edt_hip_dust_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
+/* Refused before any device work, in the order of edt_hip_connected_components_device and with its codes: bad dtype, ndim
+ * outside 1..3, unused extents not 1 (EDT_ERR_BAD_ARG); connectivity outside 1..ndim (EDT_ERR_BAD_ARG); a volume past the
+ * limit (EDT_ERR_UNSUPPORTED); then min_voxels < 0, max_voxels < min_voxels (EDT_ERR_BAD_ARG); NULL pointers, a missing or
+ * too small workspace (EDT_ERR_BAD_ARG).  Enqueue-only on `stream`: no allocation, no synchronisation; the workspace is
+ * initialised by the call itself.  d_out: a volume of the labels' dtype; d_out == d_labels is allowed (in place: the forest
+ * is finished before the filter writes, and the filter's thread i reads and writes voxel i only); any other overlap is the
+ * caller's error.  d_counts: three int64 on the device, zeroed on the stream by the call.  An empty volume only zeroes them. */
+int edt_hip_dust_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
+                        int binary, int64_t min_voxels, int64_t max_voxels, int invert, void *d_out, int64_t *d_counts,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, out and the three counts down once.  out == labels is
+ * allowed.  An empty volume zeroes counts[0..2]. */
+int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                 int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts);
+
 #ifdef __cplusplus
 }
 #endif
