@@ -259,6 +259,12 @@ int check_column_voxel_size(float &w) {
   return EDT_OK;
 }
 
+int check_workspace_alignment(const void *d_workspace) {
+  if (reinterpret_cast<uintptr_t>(d_workspace) % kWorkspaceAlign == 0) return EDT_OK;
+  set_error("d_workspace must be 256-byte aligned (the alignment of hipMalloc; include/edt_hip.h)");
+  return EDT_ERR_BAD_ARG;
+}
+
 int require_device() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -537,6 +543,7 @@ size_t edt_hip_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int6
 int edt_hip_edtsq_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy,
                          int64_t sz, float wx, float wy, float wz, int flags, float *d_output,
                          void *d_workspace, size_t workspace_bytes, void *stream) {
+  if (check_workspace_alignment(d_workspace) != EDT_OK) return EDT_ERR_BAD_ARG;
   return run_device(d_labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, d_output, d_workspace,
                     workspace_bytes, (hipStream_t)stream);
 }
@@ -636,6 +643,7 @@ int edt_hip_edtsq_voxel_graph_device(const void *d_labels, int dtype, const uint
     set_error("workspace too small: need " + std::to_string(need) + " bytes");
     return EDT_ERR_BAD_ARG;
   }
+  if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
   const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
   if (vg_use_native(ndim, sx, sy, sz)) {
     ScopedPass t("voxel_graph", stream);
@@ -677,6 +685,7 @@ int edt_hip_extract_runs_device(const void *d_labels, int dtype, int64_t count, 
     set_error("null pointer or workspace too small (edt_hip_runs_workspace_bytes)");
     return EDT_ERR_BAD_ARG;
   }
+  if (check_workspace_alignment(d_workspace) != EDT_OK) return EDT_ERR_BAD_ARG;
   return launch_extract_runs(dtype, d_labels, count, d_starts, capacity, d_count, d_workspace, (hipStream_t)stream);
 }
 

@@ -30,6 +30,11 @@ struct Carver {
   }
 };
 
+// The workspace contract of the public *_device entry points (include/edt_hip.h): the carver's granule.  Checked in the
+// extern "C" wrappers only -- run_device and the launchers take carved parts of pooled buffers from internal callers.
+constexpr size_t kWorkspaceAlign = 256;
+int check_workspace_alignment(const void *d_workspace);
+
 AxisGeom make_geom_y(int64_t sx, int64_t sy, int64_t sz);
 AxisGeom make_geom_z(int64_t sx, int64_t sy, int64_t sz);
 bool env_force_generic();  // EDT_HIP_FORCE_GENERIC=1: every call takes the fallback kernels (test hook)

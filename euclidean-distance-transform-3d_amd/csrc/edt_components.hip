@@ -413,6 +413,7 @@ int edt_hip_connected_components_device(const void *d_labels, int dtype, int ndi
       set_error("connected_components: workspace missing or smaller than edt_hip_components_workspace_bytes()");
       return EDT_ERR_BAD_ARG;
     }
+    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {

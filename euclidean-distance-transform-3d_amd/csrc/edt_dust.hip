@@ -271,6 +271,7 @@ int edt_hip_dust_device(const void *d_labels, int dtype, int ndim, int64_t sx, i
       set_error("dust: workspace missing or smaller than edt_hip_dust_workspace_bytes()");
       return EDT_ERR_BAD_ARG;
     }
+    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {

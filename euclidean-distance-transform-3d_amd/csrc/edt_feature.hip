@@ -455,6 +455,7 @@ int edt_hip_feature_transform_device(const void *d_labels, int dtype, int ndim, 
     set_error("feature transform: workspace missing or smaller than edt_hip_feature_workspace_bytes()");
     return EDT_ERR_BAD_ARG;
   }
+  if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
   const FtCall c = {ndim, sx, sy, sz, {wx, wy, wz}, (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0};
   if (g_log.enabled.load(std::memory_order_relaxed)) {
     std::lock_guard<std::mutex> lock(g_log_mutex);
@@ -484,6 +485,7 @@ int edt_hip_expand_labels_device(const void *d_labels, int dtype, int ndim, int6
     set_error("expand_labels: workspace missing or smaller than edt_hip_expand_labels_workspace_bytes()");
     return EDT_ERR_BAD_ARG;
   }
+  if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
   const FtCall c = {ndim, sx, sy, sz, {wx, wy, wz}, 0};
   hipStream_t s = (hipStream_t)stream;
   if (g_log.enabled.load(std::memory_order_relaxed)) {

@@ -17,6 +17,8 @@
 // The lower envelope is built as the lower convex hull of the points (j, F[j] + w2*j^2)
 // with a division-free orientation test; only the value of the minimum reaches the
 // output, evaluated with the reference's own expression (src/edt.hpp:230, :307).
+#include <algorithm>
+
 #include "edt_common.h"
 #include "edt_kernels.h"
 
@@ -336,34 +338,37 @@ int launch_subtract(const float *a, const float *b, float *out, int64_t count, h
 
 // The sign of the SIGNED transform (sdf / sdfsq, src/edt.pyx:121-202: edt(x) - edt(x == 0); edt_api.hip, EDT_FLAG_SIGNED):
 // the field of the transform that measured label 0 like every label, negated where the label is 0.  Four voxels per
-// thread (the volume's tail one by one).
+// thread from the first 16-byte boundary of f on (`head` voxels before it, 0..3, and the volume's tail one by one): the
+// output needs the alignment of a float and nothing more.
 template <typename T>
-__global__ void k_negate_background(const T *__restrict__ labels, float *__restrict__ f, int64_t count) {
+__global__ void k_negate_background(const T *__restrict__ labels, float *__restrict__ f, int64_t head, int64_t count) {
   typedef float v4f __attribute__((ext_vector_type(4)));
-  const int64_t quads = count >> 2;
+  const int64_t quads = (count - head) >> 2;
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  if (i < head) f[i] = labels[i] == T(0) ? -f[i] : f[i];
   for (int64_t q = i; q < quads; q += step) {
     T l[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) l[k] = labels[4 * q + k];
-    v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(f) + q);
+    for (int k = 0; k < 4; ++k) l[k] = labels[head + 4 * q + k];
+    v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(f + head) + q);
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = l[k] == T(0) ? -v[k] : v[k];
-    __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(f) + q);
+    __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(f + head) + q);
   }
-  for (int64_t j = 4 * quads + i; j < count; j += step) f[j] = labels[j] == T(0) ? -f[j] : f[j];
+  for (int64_t j = head + 4 * quads + i; j < count; j += step) f[j] = labels[j] == T(0) ? -f[j] : f[j];
 }
 
 int launch_negate_background(int dtype, const void *labels, float *f, int64_t count, hipStream_t stream) {
   if (count <= 0) return EDT_OK;
-  if (reinterpret_cast<uintptr_t>(f) % 16 != 0) { set_error("output must be 16-byte aligned"); return EDT_ERR_BAD_ARG; }
+  // (f is float-aligned: 0..3 voxels lie before its first 16-byte boundary)
+  const int64_t head = std::min<int64_t>(count, (int64_t)((16 - reinterpret_cast<uintptr_t>(f) % 16) % 16 / sizeof(float)));
   const int threads = 256;
   int64_t blocks = ceil_div(ceil_div(count, 4), threads);
   if (blocks > 16384) blocks = 16384;
   return with_label_type(dtype, [&](auto t) -> int {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(k_negate_background<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, f, count);
+    hipLaunchKernelGGL(k_negate_background<T>, dim3((unsigned)blocks), dim3(threads), 0, stream, (const T *)labels, f, head, count);
     EDT_HIP_TRY(hipGetLastError());
     return EDT_OK;
   });

@@ -579,6 +579,7 @@ int edt_hip_label_stats_device(const void *d_labels, int dtype, const float *d_d
       set_error("label_stats: workspace missing or smaller than edt_hip_label_stats_workspace_bytes()");
       return EDT_ERR_BAD_ARG;
     }
+    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {

@@ -15,7 +15,7 @@ struct ShardPlan {
 };
 
 static int check_shard_workspace(const void *ws, size_t have, size_t need) {
-  if (ws && have >= need) return EDT_OK;
+  if (ws && have >= need) return check_workspace_alignment(ws);
   set_error("shard workspace too small: need " + std::to_string(need) + " bytes");
   return EDT_ERR_BAD_ARG;
 }
@@ -409,10 +409,13 @@ int edt_hip_shard_z_records16_device(const void *d_records, float *d_out, int64_
   const Quantum Q = q16_quantum(w3, 3);
   AxisGeom gz = make_geom_z(sx, sy_local, sz);  // the dense output: z-columns one (sy_local, sx) slice apart
   gz.fmin = edt_hip_field_floor(wx, wy);
-  if (!records16_z_ok(sx, sy_local, sz, wx, wy, wz) || !Q.ok ||
-      ((reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_out)) % 16) != 0) {
+  if (!records16_z_ok(sx, sy_local, sz, wx, wy, wz) || !Q.ok) {
     set_error("16-bit slab records do not apply to these extents / voxel sizes (edt_hip_shard_records16_supported)");
     return EDT_ERR_UNSUPPORTED;
+  }
+  if (((reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_out)) % 16) != 0) {
+    set_error("the gathered records and d_out must be 16-byte aligned");
+    return EDT_ERR_BAD_ARG;
   }
   RecordPlan p = make_record_plan(sx, sy_local, sz, d_workspace);
   if ((rc = check_shard_workspace(d_workspace, workspace_bytes, p.bytes)) != EDT_OK) return rc;

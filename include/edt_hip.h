@@ -177,6 +177,16 @@ int edt_hip_release_cache(void);
  * All pointers are DEVICE pointers on the current HIP device; `stream` is a hipStream_t
  * (NULL = the null stream).  Calls only enqueue work (no host synchronisation, no
  * allocation), so they can be timed with events and captured into a hipGraph.
+ *
+ * Alignment.  Label, field and output pointers (d_labels, d_output, d_dt, d_features, d_out, d_partial, d_graph, masks ...)
+ * need the alignment of their element type and nothing more: a view at any element offset into a larger buffer is served,
+ * with the same results bit for bit (the kernels choose their vector forms by the address and fall back element by
+ * element).  Count and table outputs (d_n, d_counts, d_keys ...) likewise need their element's alignment.  The slab-record
+ * forms state their own 8- and 16-byte requirements below.
+ * d_workspace is the one exception: every *_device entry point that takes one requires it 256-BYTE ALIGNED and refuses
+ * any other pointer with EDT_ERR_BAD_ARG before any device work.  256 bytes is the granule the scratch is carved at -- the
+ * bit planes, parent words and tables carved from it are targets of 32- and 64-bit atomics and of 16-byte loads, all relative
+ * to the base -- and it is what hipMalloc (and torch's allocator) deliver; every caller in this tree passes such a base.
  */
 
 /* bytes of scratch edt_hip_edtsq_device needs for a volume of this shape: the four bit planes of the column

@@ -2,7 +2,7 @@
 
 All generators return arrays whose shape is (sx, sy, sz) in Fortran order when asked for
 `order="F"`, i.e. x is the fastest axis, matching the reference's native layout
-(reference: src/edt.hpp:434, src/edt.pyx:659-664).  Only numpy is used so that the same
+(reference: src/edt.hpp:434, src/edt.pyx:659-664).  The generators use only numpy so that the same
 inputs can be rebuilt on the GPU box.
 """
 from __future__ import annotations
@@ -293,3 +293,84 @@ def box_edtsq_closed_form(shape, anisotropy):
         d2 = d2.reshape(shp)
         out = d2 if out is None else np.minimum(out, d2)
     return np.asfortranarray(np.broadcast_to(out, shape))
+
+
+# ---- device buffers at an element offset (tests/test_gpu_offset_pointers.py, tools/fuzz_ops.py) -------------------------------
+OFFSET_HEAD = 16   # elements of the buffer before a view of offset 0
+OFFSET_PAD = 64    # elements of the buffer beyond the view's own
+
+_TORCH_NAME = {"bool": "bool", "uint8": "uint8", "int8": "int8", "uint16": "int16", "int16": "int16", "uint32": "int32",
+               "int32": "int32", "uint64": "int64", "int64": "int64", "float32": "float32", "float64": "float64"}
+
+
+def aligned_host_bytes(nbytes, align=256):
+    """A zeroed host array of ``nbytes`` uint8 whose address is a multiple of ``align``: the stand-in for a device workspace in
+    the argument-validation tests of the CPU tier (include/edt_hip.h: d_workspace is 256-byte aligned)."""
+    raw = np.zeros(int(nbytes) + align, dtype=np.uint8)
+    lo = (-raw.ctypes.data) % align
+    return raw[lo:lo + int(nbytes)]
+
+
+def _signed_bits(bits, size):
+    """The `size`-byte bit pattern `bits` as the signed integer torch's intN holds it as."""
+    bits = int(bits) % (1 << (8 * size))
+    return bits - (1 << (8 * size)) if bits >= 1 << (8 * size - 1) else bits
+
+
+def element_bits(value):
+    """The bit pattern of a numpy scalar as a Python integer (what `sentinel` of :func:`offset_view` takes)."""
+    a = np.asarray(value).reshape(1)
+    return int(a.view(f"u{a.dtype.itemsize}")[0])
+
+
+def offset_view(array, k, sentinel=None):
+    """``(buf, view)``: ONE device buffer of ``array.size + 64`` elements and the contiguous view ``buf[16 + k : 16 + k + n]`` of
+    it, of the array's shape and holding its data (C order) -- a tensor whose address is the allocator's aligned base plus
+    ``16 + k`` elements: element-aligned and, for k = 1, 2, 3 on 1-, 2- and 4-byte types, off every wider boundary.
+
+    ``buf`` is the whole buffer as the signed integer type of the element's width (bit patterns compare as integers, NaN
+    payloads included); ``view`` has the torch dtype of the array (unsigned 16/32/64-bit labels as the signed type of their
+    width, which is how they reach torch everywhere in this project).  The elements outside the view hold ``sentinel`` (a bit
+    pattern).  ``sentinel=None`` is for INPUTS: the head holds the array's first element and the tail its last -- a non-zero
+    label each (bit pattern 1 where that element is all-zero bits), so that a kernel that reads past either end and uses what
+    it read lengthens a run or joins a component."""
+    import torch
+    a = np.ascontiguousarray(array)
+    size, n = a.dtype.itemsize, a.size
+    itype = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[size]
+    raw = a.reshape(-1).view(f"i{size}")
+    lo, hi = OFFSET_HEAD + k, OFFSET_HEAD + k + n
+    if sentinel is None:
+        head, tail = (int(raw[0]) or 1, int(raw[-1]) or 1) if n else (1, 1)
+    else:
+        head = tail = _signed_bits(sentinel, size)
+    buf = torch.empty(n + OFFSET_PAD, dtype=itype, device="cuda")
+    assert buf.data_ptr() % 256 == 0
+    buf[:lo] = head
+    buf[hi:] = tail
+    buf[lo:hi] = torch.from_numpy(raw.copy())
+    view = buf[lo:hi].view(getattr(torch, _TORCH_NAME[a.dtype.name])).view(a.shape)
+    assert view.data_ptr() == buf.data_ptr() + lo * size and view.is_contiguous()
+    return buf, view
+
+
+def offset_out(shape, dtype, k, sentinel):
+    """:func:`offset_view` for an OUTPUT: the view itself holds the sentinel too, so an element the call leaves unwritten shows."""
+    dt = np.dtype(dtype)
+    fill = np.array([int(sentinel) % (1 << (8 * dt.itemsize))], dtype=f"u{dt.itemsize}").view(dt)[0]
+    return offset_view(np.full(shape, fill, dtype=dt), k, sentinel)
+
+
+def outside_intact(buf, k, n, sentinel):
+    """Every element of ``buf`` outside the view of :func:`offset_view` still holds the sentinel's bits."""
+    s = _signed_bits(sentinel, buf.element_size())
+    lo, hi = OFFSET_HEAD + k, OFFSET_HEAD + k + n
+    return bool((buf[:lo] == s).all()) and bool((buf[hi:] == s).all())
+
+
+def bits_of(t):
+    """A device tensor's elements as a numpy array of unsigned integers of their width (bit-for-bit comparisons)."""
+    import torch
+    itype = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]
+    a = t.contiguous().view(itype).cpu().numpy()
+    return a.view(f"u{t.element_size()}")

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import dust_oracle as oracle
+from synth import aligned_host_bytes
 
 BAD_ARG, UNSUPPORTED = -2, -4
 U8, U16, U32, U64, F32, F64, BOOL = range(7)
@@ -131,7 +132,7 @@ class _Args:
         self.labels = np.ones(24, dtype=np.uint32)
         self.out = np.zeros(24, dtype=np.uint32)
         self.counts = np.zeros(3, dtype=np.int64)
-        self.ws = np.zeros(lib.edt_hip_dust_workspace_bytes(U32, 3, 4, 3, 2), dtype=np.uint8)
+        self.ws = aligned_host_bytes(lib.edt_hip_dust_workspace_bytes(U32, 3, 4, 3, 2))   # (256-byte aligned, as the ABI requires of d_workspace)
 
     @staticmethod
     def p(a):

@@ -1,0 +1,334 @@
+#!/usr/bin/env python3
+"""Seeded randomised runs of the label operations against their numpy oracles, bit for bit, in the manner of tools/fuzz_gpu.py:
+connected_components, fill_holes, dust, label_stats, feature_transform and expand_labels, round-robin.
+
+usage: python tools/fuzz_ops.py [ncases] [seed]
+
+One MISMATCH line per failing case, one line of per-operation counts, a last line `N cases, M mismatches`; the exit status is
+non-zero on any mismatch.  ``cases(seed, n)`` is the generator on its own (numpy only): the CPU tier draws the same inputs and
+holds the oracles against a second opinion (tests/test_fuzz_ops_cpu.py).
+
+A case: 1 to 3 dimensions in C or F order; an x extent from the lengths where 64-voxel groups, 256-voxel cuts and row kernels
+change (or 1..90), the other extents 1..40, the last ones clipped to the case's cap; blocks, noise near the percolation
+threshold, a solid with pin-holes, per-voxel labels, a serpentine or a comb; each of the eleven label dtypes in turn, every
+fifth case with the full-width palette (extreme keys, NaN, -0.0); a connectivity 1..ndim, binary or not.  The call goes through
+edt.device.* on device buffers at a random element offset (tests/synth.py: offset_view; the buffers, surroundings included, must
+come back unchanged), every fifth case through the host module edt.* as well, and the two must agree."""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "euclidean-distance-transform-3d_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+from synth import blocky_labels, palette  # noqa: E402
+
+OPS = ("connected_components", "fill_holes", "dust", "label_stats", "feature_transform", "expand_labels")
+COMPONENT_FAMILY = OPS[:3]
+X_EXTENTS = (1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1030)
+STRUCTURES = ("blocky", "noise", "pinholes", "per_voxel", "chain")
+CAP = {op: 60000 for op in OPS}
+CAP["feature_transform"] = CAP["expand_labels"] = 16000     # (their oracle is the slow one)
+
+
+def _tables():
+    from test_gpu_feature_transform import DTYPES, QUANTUM
+    return DTYPES, QUANTUM
+
+
+def _shape(rng, op, nd, at_least, turn):
+    """x-fastest extents: x first -- entry `turn` of X_EXTENTS, or (turn < 0) uniform in 1..90.  The extents behind x are
+    clipped so that the case stays within its cap (never skipped); at_least > 0: grown -- the other extents first, up to 40,
+    then x -- until the volume exceeds that many voxels."""
+    cap = CAP[op]
+    ext = [X_EXTENTS[turn % len(X_EXTENTS)] if turn >= 0 else int(rng.integers(1, 91))]
+    ext += [int(rng.integers(1, 41)) for _ in range(nd - 1)]
+    while at_least and int(np.prod(ext)) <= at_least:
+        grow = [k for k in range(1, nd) if ext[k] < 40]
+        if grow:
+            ext[grow[0]] = min(40, ext[grow[0]] * 2 + 1)
+        else:
+            ext[0] = ext[0] * 2 + 1
+    ext[0] = min(ext[0], cap)
+    for k in range(1, nd):
+        ext[k] = max(1, min(ext[k], cap // int(np.prod(ext[:k]))))
+    return tuple(ext)
+
+
+def _chain(ext, rng):
+    """a serpentine or a comb along x and y (tests/test_gpu_components.py), repeated in every other slice: one long component"""
+    nd = len(ext)
+    sx, sy = ext[0], ext[1] if nd > 1 else 1
+    img = np.zeros((sx, sy), dtype=np.int64)
+    if rng.random() < 0.5:
+        img[:, 0::2] = 4
+        for k, y in enumerate(range(1, sy, 2)):
+            img[sx - 1 if k % 2 == 0 else 0, y] = 4
+    else:
+        img[0::2, :] = 2
+        img[:, sy - 1] = 2
+    if nd == 1:
+        return img[:, 0]
+    if nd == 2:
+        return img
+    vol = np.zeros(ext, dtype=np.int64)
+    vol[:, :, 0::2] = img[:, :, None]
+    return vol
+
+
+def _ids(rng, ext, structure):
+    """small non-negative integers of shape `ext` (x first); 0 is background"""
+    if structure == "blocky":
+        return blocky_labels(ext, nlabels=int(rng.integers(1, 6)), zero_frac=float(rng.random() * 0.4), block=int(rng.integers(1, 7)),
+                             rng=rng)
+    if structure == "noise":      # near the percolation thresholds: few large, winding components
+        return (rng.random(ext) < rng.choice([0.3, 0.5, 0.7])) * int(rng.choice([1, 2]))
+    if structure == "pinholes":
+        ids = np.full(ext, int(rng.integers(1, 4)), dtype=np.int64)
+        ids[rng.random(ext) < 0.05] = 0
+        return ids
+    if structure == "per_voxel":
+        return rng.integers(0, 3, size=ext)
+    return _chain(ext, rng)
+
+
+def _typed(ids, dtype, full_width):
+    dt = np.dtype(dtype)
+    if dt == np.bool_:
+        return ids != 0
+    if not full_width:
+        return ids.astype(dt)
+    pal = palette(dt)                                   # extreme keys, NaN payloads, -0.0 (which is background)
+    table = np.concatenate([np.zeros(1, dtype=pal.dtype), pal])
+    stride = next(s for s in (3, 5, 7) if len(pal) % s)       # (the few small ids spread over the whole palette)
+    return table[np.where(ids == 0, 0, 1 + (ids - 1) * stride % len(pal))]
+
+
+def cases(seed, n):
+    """The `n` cases of `seed`, as dicts: op, data (numpy, C or F order; axis 0 is x in F order, the last axis in C order),
+    connectivity, binary, k (element offset of the device buffers), host (also through the host module), and the operation's
+    own parameters in the order of the array's axes."""
+    DTYPES, QUANTUM = _tables()
+    rng = np.random.default_rng(seed)
+    for i in range(n):
+        op = OPS[i % len(OPS)]
+        j = i // len(OPS)                               # the operation's own case number
+        # Stratified, so that a few short slices cover what a long run would: the dimensions and the connectivity go round with
+        # the operation's case number, every second case takes the next entry of X_EXTENTS (consecutive seeds continue where
+        # the last one stopped), and among the others every second one of the component family is grown past 2048 or 4096
+        # voxels, so that chunk and span boundaries fall inside the volume.
+        nd = 1 + (j + seed) % 3
+        connectivity = 1 + (j // 3 + seed) % nd
+        turn = (j // 2 + 5 * seed + 3 * OPS.index(op)) if j % 2 == 0 else -1
+        at_least = 0
+        if op in COMPONENT_FAMILY and j % 4 == 1:
+            at_least = 4096 if j % 8 == 1 else 2048
+        ext = _shape(rng, op, nd, at_least, turn)
+        order = "F" if rng.random() < 0.5 or ext[0] == 1 else "C"        # (a C-ordered array whose last extent is 1 is F-ordered too)
+        structure = STRUCTURES[(j + i % len(OPS)) % len(STRUCTURES)]
+        dtype = DTYPES[i % len(DTYPES)]
+        xyz = _typed(np.asarray(_ids(rng, ext, structure)), dtype, full_width=i % 5 == 4)     # indexed [x, y, z]
+        data = np.asfortranarray(xyz) if order == "F" else np.ascontiguousarray(xyz.T)
+        # (an array that is contiguous both ways -- 1-D, extents of 1 -- is taken in F order by every entry point and oracle)
+        order = "F" if data.flags.f_contiguous else "C"
+        case = dict(index=i, op=op, data=data, order=order, structure=structure, connectivity=connectivity,
+                    binary=bool(rng.integers(0, 2)), k=int(rng.integers(0, 4)), host=i % 5 == 2)
+        if op == "dust":
+            lo = int(rng.integers(1, 12))
+            case["threshold"] = lo if rng.random() < 0.5 else (lo, lo + int(rng.integers(1, 40)))
+            case["invert"] = bool(rng.integers(0, 2))
+        elif op == "label_stats":
+            field = rng.standard_normal(data.shape).astype(np.float32) * np.float32(3)
+            ties = rng.random(data.shape) < 0.1
+            field[ties] = np.round(field[ties] * 4) / 4                 # (two fractional bits: ties)
+            case["dt"] = np.asfortranarray(field) if order == "F" else field
+        elif op == "feature_transform":
+            w = list(QUANTUM)[int(rng.integers(0, len(QUANTUM)))]
+            case["w_xyz"], case["a_xyz"] = w[:nd], QUANTUM[w][:nd]
+            case["black_border"] = bool(rng.integers(0, 2))
+        elif op == "expand_labels":
+            case["distance"] = float(rng.choice([0.0, 1.0, 2.5, np.inf]))
+            case["w_xyz"] = tuple(float(v) for v in rng.integers(1, 4, size=nd))
+        yield case
+
+
+def describe(case):
+    d = case["data"]
+    extra = {k: v for k, v in case.items() if k in ("threshold", "invert", "w_xyz", "black_border", "distance")}
+    return (f"#{case['index']} {case['op']} {d.shape} {case['order']} {d.dtype.name} {case['structure']} c={case['connectivity']} "
+            f"binary={case['binary']} k={case['k']} host={case['host']} {extra}")
+
+
+# ---- expectations -----------------------------------------------------------------------------------------------------------
+def axis_order(case, xyz):
+    """a per-axis tuple given in ABI order (x first) in the order of the array's axes"""
+    return tuple(xyz) if case["order"] == "F" else tuple(xyz)[::-1]
+
+
+def expand_want(data, distance, a_xyz):
+    """expand_reference of tests/test_gpu_feature_transform.py (the definition of include/edt_hip.h) with the inner feature
+    transform from the numpy oracle, not from the library; a_xyz: the squared voxel sizes (integers), x first"""
+    from test_gpu_feature_transform import expected
+    nd = data.ndim
+    order = "F" if data.flags.f_contiguous else "C"
+    with np.errstate(invalid="ignore"):
+        mask = np.array(data == 0, order=order).astype(np.uint8, order=order)
+    f = expected(mask, False, a_xyz)                                    # component k: the coordinate along array axis k
+    grids = np.stack(np.meshgrid(*[np.arange(s) for s in data.shape], indexing="ij")) if nd > 1 else np.arange(data.shape[0])[None]
+    a_axis = tuple(a_xyz) if order == "F" else tuple(a_xyz)[::-1]
+    D = np.zeros(data.shape)
+    for k in (range(nd) if order == "F" else range(nd - 1, -1, -1)):    # terms added in ABI order x, y, z
+        D = D + np.float64(a_axis[k]) * ((grids[k] - f[k]).astype(np.int64) ** 2).astype(np.float64)
+    has = ~np.all(f == -1, axis=0)
+    out = data.copy(order=order)
+    with np.errstate(invalid="ignore"):
+        take = np.asarray(data == 0) & has & (D <= np.float64(distance) * np.float64(distance))
+    src = tuple(np.where(take, f[k], 0) for k in range(nd))
+    out[take] = data[src][take]
+    return out
+
+
+def want_of(case):
+    import components_oracle
+    import dust_oracle
+    import fill_holes_oracle
+    import label_stats_oracle
+    from test_gpu_feature_transform import expected
+    op, data, c, binary = case["op"], case["data"], case["connectivity"], case["binary"]
+    if op == "connected_components":
+        return components_oracle.connected_components(data, c, binary=binary, return_N=True)
+    if op == "fill_holes":
+        w = fill_holes_oracle.fill_holes(data, c, binary=binary)
+        return w.out, w.n_filled
+    if op == "dust":
+        w = dust_oracle.dust(data, case["threshold"], c, binary=binary, invert=case["invert"])
+        return w.out, (w.components, w.kept, w.removed_voxels)
+    if op == "label_stats":
+        return label_stats_oracle.label_stats(data, case["dt"])
+    if op == "feature_transform":
+        return expected(data, case["black_border"], case["a_xyz"])
+    return expand_want(data, case["distance"], tuple(int(v * v) for v in case["w_xyz"]))
+
+
+# ---- the library ------------------------------------------------------------------------------------------------------------
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype.itemsize == b.dtype.itemsize and np.array_equal(
+        np.ascontiguousarray(a).view(f"u{a.dtype.itemsize}"), np.ascontiguousarray(b).view(f"u{b.dtype.itemsize}"))
+
+
+def _back(case, t):
+    """a device result of the tensor's shape as a numpy array of the data's shape and dtype"""
+    from synth import bits_of
+    a = bits_of(t).view(case["data"].dtype if t.element_size() == case["data"].dtype.itemsize else f"u{t.element_size()}")
+    return a.T if case["order"] == "F" else a
+
+
+def run_device(case):
+    """the case through edt.device.* on buffers at element offset k; what want_of returns, plus whether the input buffers came
+    back unchanged"""
+    import torch
+    import label_stats_oracle
+    from edt import device
+    from synth import offset_view
+    op, data, c, binary, k = case["op"], case["data"], case["connectivity"], case["binary"], case["k"]
+    tdata = data.T if case["order"] == "F" else data                     # C-contiguous: the same memory
+    buf, t = offset_view(tdata, k)
+    held = [(buf, buf.clone())]
+    nd = data.ndim
+    if op == "connected_components":
+        out, n = device.connected_components(t, connectivity=c, binary=binary)
+        got = (_back(case, out).view(np.uint32), int(n))
+    elif op == "fill_holes":
+        out, n = device.fill_holes(t, connectivity=c, binary=binary)
+        got = (_back(case, out), int(n))
+    elif op == "dust":
+        out, counts = device.dust(t, case["threshold"], connectivity=c, binary=binary, invert=case["invert"])
+        got = (_back(case, out), tuple(counts.tolist()))
+    elif op == "label_stats":
+        field = case["dt"].T if case["order"] == "F" else case["dt"]
+        fbuf, ft = offset_view(field, k, 0x7FC0BEEF)
+        held.append((fbuf, fbuf.clone()))
+        s = [x.cpu().numpy() for x in device.label_stats(t, ft)]
+        keys = s[0].view(data.dtype) if s[0].dtype.itemsize == data.dtype.itemsize else s[0]
+        rows = np.argsort(keys, kind="stable") if data.dtype.kind == "u" else np.arange(len(keys))   # (unsigned labels travel as signed tensors)
+        flip = (lambda a: a[:, ::-1]) if case["order"] == "F" else (lambda a: a)
+        got = label_stats_oracle.LabelStats(keys[rows], s[1][rows], s[2][rows], np.ascontiguousarray(flip(s[3][rows])),
+                                            np.ascontiguousarray(flip(s[4][rows])), np.ascontiguousarray(flip(s[5][rows])))
+    elif op == "feature_transform":
+        f = device.feature_transform(t, anisotropy=tuple(case["w_xyz"])[::-1], black_border=case["black_border"]).cpu().numpy()
+        got = np.stack([f[nd - 1 - j].T for j in range(nd)]) if case["order"] == "F" else f
+    else:
+        out = device.expand_labels(t, distance=case["distance"], anisotropy=tuple(case["w_xyz"])[::-1])
+        got = _back(case, out)
+    torch.cuda.synchronize()
+    return got, all(torch.equal(b, before) for b, before in held)
+
+
+def run_host(case):
+    """the case through the host module edt.*"""
+    import edt
+    import label_stats_oracle
+    op, data, c, binary = case["op"], case["data"], case["connectivity"], case["binary"]
+    if op == "connected_components":
+        return edt.connected_components(data, connectivity=c, binary=binary, return_N=True)
+    if op == "fill_holes":
+        return edt.fill_holes(data, connectivity=c, binary=binary, return_fill_count=True)
+    if op == "dust":
+        out, counts = edt.dust(data, case["threshold"], connectivity=c, binary=binary, invert=case["invert"], return_counts=True)
+        return out, tuple(counts)
+    if op == "label_stats":
+        return label_stats_oracle.LabelStats(*edt.label_stats(data, case["dt"]))
+    if op == "feature_transform":
+        return edt.feature_transform(data, anisotropy=axis_order(case, case["w_xyz"]), black_border=case["black_border"])
+    return edt.expand_labels(data, distance=case["distance"], anisotropy=axis_order(case, case["w_xyz"]))
+
+
+def agrees(case, got, want):
+    """'' if `got` equals `want` bit for bit, else what differs"""
+    import label_stats_oracle
+    op = case["op"]
+    if op == "label_stats":
+        try:
+            label_stats_oracle.assert_same(got, want)
+        except AssertionError as e:
+            return f"table differs: {str(e)[:200]}"
+        return ""
+    if op in ("feature_transform", "expand_labels"):
+        return "" if same_bits(got, want) else f"{int(np.count_nonzero(np.asarray(got) != np.asarray(want)))} elements differ"
+    if not same_bits(got[0], want[0]):
+        return "the volume differs"
+    if tuple(np.atleast_1d(got[1]).tolist()) != tuple(np.atleast_1d(want[1]).tolist()):
+        return f"counts {got[1]} != {want[1]}"
+    return ""
+
+
+def main(argv):
+    ncases = int(argv[1]) if len(argv) > 1 else 60
+    seed = int(argv[2]) if len(argv) > 2 else 1
+    bad, t0 = 0, time.time()
+    ran = dict.fromkeys(OPS, 0)
+    for case in cases(seed, ncases):
+        want = want_of(case)
+        got, inputs_intact = run_device(case)
+        why = agrees(case, got, want)
+        if not why and not inputs_intact:
+            why = "the input buffers changed"
+        if not why and case["host"]:
+            why = agrees(case, run_host(case), want)
+            why = why and "host module: " + why
+        ran[case["op"]] += 1
+        if why:
+            bad += 1
+            print("MISMATCH", describe(case), "--", why, flush=True)
+    print("ops:", " ".join(f"{op}={ran[op]}" for op in OPS))
+    print(f"{ncases} cases, {bad} mismatches, {time.time() - t0:.1f} s")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
