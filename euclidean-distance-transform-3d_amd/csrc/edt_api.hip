@@ -191,7 +191,9 @@ static Plan make_plan(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, v
     // (pass Y runs over all sz slices at once whenever the index form is not taken at run time: sized for that)
     p.q16_map_words = (int)ceil_div(sz, 32);
     p.q16.slots = kQ16Slots;
-    p.q16.counts = c.take<uint32_t>(kQ16Slots + (size_t)(ceil_div(sx, 32) * p.q16_map_words));  // (zeroed together)
+    // (one region, two rules: the counters are zeroed on the stream before the first launch that may hand a tile over,
+    // HandOver::zero; the map behind them never is -- every tile of a pass that writes the plane sets or clears its own bit)
+    p.q16.counts = c.take<uint32_t>(kQ16Slots + (size_t)(ceil_div(sx, 32) * p.q16_map_words));
     p.q16_map = p.q16.counts ? p.q16.counts + kQ16Slots : nullptr;
     p.q16.capacity = std::max(HandOver::ids_of(sx, sz), HandOver::ids_of(sx, sy));
     p.q16.ids = c.take<uint32_t>((size_t)p.q16.capacity);
@@ -680,7 +682,7 @@ int edt_hip_extract_runs_device(const void *d_labels, int dtype, int64_t count, 
                                 int64_t *d_count, void *d_workspace, size_t workspace_bytes, void *stream) {
   if (count < 0 || capacity < 0 || dtype_size(dtype) == 0) { set_error("bad argument"); return EDT_ERR_BAD_ARG; }
   if (!d_count) { set_error("null pointer"); return EDT_ERR_BAD_ARG; }
-  if (count == 0) { EDT_HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int64_t), (hipStream_t)stream)); return EDT_OK; }
+  if (count == 0) return launch_fill_words(d_count, 0u, sizeof(int64_t) / sizeof(uint32_t), (hipStream_t)stream);
   if (!d_labels || !d_workspace || workspace_bytes < runs_workspace_bytes(count)) {
     set_error("null pointer or workspace too small (edt_hip_runs_workspace_bytes)");
     return EDT_ERR_BAD_ARG;

@@ -23,8 +23,24 @@ int launch_column_inplace(const ColumnPass &cp, const TileList &list) {
   return launch_column_pass_tiled(cp.F, cp.nz, cp.rs, g, cp.w, cp.bb, cp.epi, cp.stream);
 }
 
+namespace {
+__global__ void k_fill_words(uint32_t *__restrict__ p, uint32_t value, size_t count) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < count) p[i] = value;
+}
+}  // namespace
+
+int launch_fill_words(void *p, uint32_t value, size_t count, hipStream_t stream) {
+  if (count == 0) return EDT_OK;
+  hipLaunchKernelGGL(k_fill_words, dim3((unsigned)ceil_div((int64_t)count, 256)), dim3(256), 0, stream, static_cast<uint32_t *>(p), value,
+                     count);
+  EDT_HIP_TRY(hipGetLastError());
+  return EDT_OK;
+}
+
 int HandOver::zero(hipStream_t stream) {
-  EDT_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)slots * sizeof(uint32_t), stream));
+  const int rc = launch_fill_words(counts, 0u, (size_t)slots, stream);
+  if (rc != EDT_OK) return rc;
   zeroed = true;
   return EDT_OK;
 }

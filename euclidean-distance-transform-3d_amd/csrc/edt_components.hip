@@ -417,8 +417,7 @@ int edt_hip_connected_components_device(const void *d_labels, int dtype, int ndi
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {
-    EDT_HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(int64_t), stream));
-    return EDT_OK;
+    return launch_fill_words(d_n, 0u, sizeof(int64_t) / sizeof(uint32_t), stream);
   }
   if (g_log.enabled.load(std::memory_order_relaxed)) {
     std::lock_guard<std::mutex> lock(g_log_mutex);

@@ -217,7 +217,7 @@ int launch_dust(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t s
   if ((rc = launch_labels_forest(dtype, labels, sx, sy, sz, connectivity, binary, P, chunks, stream)) != EDT_OK) return rc;
   {
     ScopedPass sp("dust count", stream);
-    EDT_HIP_TRY(hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), stream));
+    if ((rc = launch_fill_words(counts, 0u, 3 * sizeof(int64_t) / sizeof(uint32_t), stream)) != EDT_OK) return rc;
     const int64_t spans = ceil_div(voxels, kDustSpan);
     hipLaunchKernelGGL(k_dust_count, dim3((unsigned)ceil_div(spans, kDustThreads / 64)), dim3(kDustThreads), 0, stream, P,
                        (uint32_t)voxels);
@@ -275,8 +275,7 @@ int edt_hip_dust_device(const void *d_labels, int dtype, int ndim, int64_t sx, i
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {
-    EDT_HIP_TRY(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), stream));
-    return EDT_OK;
+    return launch_fill_words(d_counts, 0u, 3 * sizeof(int64_t) / sizeof(uint32_t), stream);
   }
   if (g_log.enabled.load(std::memory_order_relaxed)) {
     std::lock_guard<std::mutex> lock(g_log_mutex);

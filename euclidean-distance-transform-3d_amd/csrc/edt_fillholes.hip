@@ -194,7 +194,7 @@ int launch_fill_holes(int dtype, const void *labels, int ndim, int64_t sx, int64
   int rc;
   {
     ScopedPass sp("fill_holes mask", stream);
-    EDT_HIP_TRY(hipMemsetAsync(n_filled, 0, sizeof(int64_t), stream));
+    if ((rc = launch_fill_words(n_filled, 0u, sizeof(int64_t) / sizeof(uint32_t), stream)) != EDT_OK) return rc;
     if ((rc = launch_is_background(dtype, labels, bg, voxels, stream)) != EDT_OK) return rc;
   }
   if ((rc = launch_components_forest(bg, sx, sy, sz, connectivity, P, chunks, stream)) != EDT_OK) return rc;
@@ -251,8 +251,7 @@ int edt_hip_fill_holes_device(const void *d_labels, int dtype, int ndim, int64_t
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {
-    EDT_HIP_TRY(hipMemsetAsync(d_n_filled, 0, sizeof(int64_t), stream));
-    return EDT_OK;
+    return launch_fill_words(d_n_filled, 0u, sizeof(int64_t) / sizeof(uint32_t), stream);
   }
   if (g_log.enabled.load(std::memory_order_relaxed)) {
     std::lock_guard<std::mutex> lock(g_log_mutex);

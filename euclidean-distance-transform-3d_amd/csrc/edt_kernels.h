@@ -213,6 +213,9 @@ inline bool column_pass_q16_aligned(const float *F, const uint16_t *codes, const
   return (reinterpret_cast<uintptr_t>(F) % 16) == 0 && (reinterpret_cast<uintptr_t>(codes) % 8) == 0 &&
          (reinterpret_cast<uintptr_t>(plane) % 8) == 0 && (reinterpret_cast<uintptr_t>(compact) % 8) == 0;
 }
+// `count` 32-bit words at p = value, by a KERNEL on the stream.  Every word an enqueue-only entry point sets on its stream is
+// set this way and not with hipMemsetAsync: see DESIGN.md 13.3 (a captured call must replay like the call itself).
+int launch_fill_words(void *p, uint32_t value, size_t count, hipStream_t stream);
 // The hand-over from the integer kernel to the fp32 kernel: counters (one per launch: `slot` is the next free one) and one
 // array of tile ids in the fp32 kernel's geometry (launches are stream-ordered: the array is reused).
 struct HandOver {

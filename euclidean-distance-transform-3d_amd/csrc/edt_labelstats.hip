@@ -583,8 +583,7 @@ int edt_hip_label_stats_device(const void *d_labels, int dtype, const float *d_d
   }
   if ((rc = require_device()) != EDT_OK) return rc;
   if (voxels == 0) {
-    EDT_HIP_TRY(hipMemsetAsync(d_n_labels, 0, sizeof(int64_t), stream));
-    return EDT_OK;
+    return launch_fill_words(d_n_labels, 0u, sizeof(int64_t) / sizeof(uint32_t), stream);
   }
   const LsTable t = carve_ls(d_workspace, dtype, ls_cap(voxels, max_labels));
   const LsOut o = {d_keys, d_counts, d_max, d_argmax, d_bbox, d_n_labels, dtype_size(dtype),

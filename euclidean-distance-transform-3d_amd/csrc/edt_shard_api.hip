@@ -438,7 +438,7 @@ int edt_hip_shard_z_records16_device(const void *d_records, float *d_out, int64_
   cp.map_words = (int)ceil_div(sz, 32);
   cp.plane_stride = 2 * rec;
   cp.plane_outer = sx;
-  EDT_HIP_TRY(hipMemsetAsync(p.ones_map, 0xFF, (size_t)(ceil_div(sx, 32) * cp.map_words) * sizeof(uint32_t), stream));
+  if ((rc = launch_fill_words(p.ones_map, ~0u, (size_t)(ceil_div(sx, 32) * cp.map_words), stream)) != EDT_OK) return rc;
   TileList served;
   rc = run_column_pass(cp, Q, 2, p.q16, Fp32Leg::wave, false, &served);
   if (rc == EDT_OK && served.count == nullptr) { set_error("internal: the Z phase of 16-bit records left the integer kernel"); return EDT_ERR_HIP; }

@@ -187,6 +187,12 @@ int edt_hip_release_cache(void);
  * any other pointer with EDT_ERR_BAD_ARG before any device work.  256 bytes is the granule the scratch is carved at -- the
  * bit planes, parent words and tables carved from it are targets of 32- and 64-bit atomics and of 16-byte loads, all relative
  * to the base -- and it is what hipMalloc (and torch's allocator) deliver; every caller in this tree passes such a base.
+ *
+ * Workspace.  The workspace of every *_device entry point is initialised by the call itself; a reused one needs no memset.
+ * A call reads nothing of its scratch that it has not written on `stream` before: what an earlier call -- of another shape,
+ * of other flags, another entry point's -- or the caller left there never shows in a result.  Nothing is kept in a workspace
+ * between calls either.  Every word a call sets it sets with kernels on `stream`, so a captured call replays like the call
+ * itself, on whatever the workspace holds by then.  (tests/test_gpu_workspace_contract.py; DESIGN.md 13 lists the regions.)
  */
 
 /* bytes of scratch edt_hip_edtsq_device needs for a volume of this shape: the four bit planes of the column
@@ -194,7 +200,9 @@ int edt_hip_release_cache(void);
  * passes X and Y (2 bytes per voxel, never more than 256 MiB: larger volumes run those passes slab by slab).
  * Only a call that has to use the size-agnostic column kernels (an axis longer than 32735 voxels, or
  * EDT_FLAG_FORCE_GENERIC) needs a second fp32 volume and the hull stacks as well (+ 8 bytes per voxel): ask
- * with the flags of the call. */
+ * with the flags of the call.  A call carves its regions from the base of whatever it is given, by its own flags: one buffer
+ * of the largest size -- the maximum of edt_hip_workspace_bytes_flags over the flag sets in use -- serves calls of every
+ * flag set, in any order, without being cleared in between. */
 size_t edt_hip_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
 size_t edt_hip_workspace_bytes_flags(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags);
 
@@ -209,7 +217,8 @@ int edt_hip_edt2dsq_batch(const void *labels, int dtype, int64_t sx, int64_t sy,
  * d_labels.  Implements _edt3dsq / _edt2dsq / squared_edt_1d_multi_seg (+ optional sqrt).
  * ndim = 1: with edt_hip_workspace_bytes() of scratch the line runs through the parallel pipeline (a thread per
  * voxel); with d_workspace = NULL (or too small) it is served by one thread walking the line -- correct, and slow
- * for long lines. */
+ * for long lines.
+ * Enqueue-only on `stream`; the workspace is initialised by the call itself; a reused one needs no memset. */
 int edt_hip_edtsq_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy,
                          int64_t sz, float wx, float wy, float wz, int flags, float *d_output,
                          void *d_workspace, size_t workspace_bytes, void *stream);
@@ -248,6 +257,8 @@ const char *edt_hip_get_pass_name(int index);
  * all-to-all (RCCL over xGMI) and phase 2 runs the Z pass on whole z-columns.
  *   d_halo: the last xy-slice of the previous rank's labels (NULL on the first rank) --
  *           the one-slab halo that decides run continuity across the cut.
+ * Both phases, in every form below: enqueue-only on `stream`; the workspace is initialised by the call itself; a reused one
+ * needs no memset (one buffer may serve the XY phase and the Z phase in turn).
  */
 size_t edt_hip_shard_workspace_bytes(int dtype, int64_t sx, int64_t sy, int64_t sz);
 int edt_hip_shard_xy_device(const void *d_labels, const void *d_halo, int dtype, int64_t sx,
@@ -313,7 +324,8 @@ int edt_hip_shard_z_records_device_w(float *d_records, int64_t sx, int64_t sy_lo
  * reads -- and leaves their rows unspecified; a caller that finds it non-zero repeats the step with the fp32 records
  * (edt/distributed.py: the ranks agree on it with one all-reduce of the counter, off the critical path).  The Z phase reads
  * the gathered records (sz x record16 words) and writes the dense (sz, sy_local, sx) fp32 result to d_out; the same bits as
- * every other route.  No counterpart in the reference (src/edt.hpp:448-475 is what both phases replace). */
+ * every other route.  No counterpart in the reference (src/edt.hpp:448-475 is what both phases replace).
+ * (*d_refused is the caller's word, not scratch: the XY phase only adds to it.) */
 int edt_hip_shard_records16_supported(int dtype, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz);
 size_t edt_hip_shard_record16_words(int64_t sx, int64_t y_rows);
 int edt_hip_shard_xy_records16_device(const void *d_labels, const void *d_halo, int dtype, int64_t sx, int64_t sy,
@@ -330,7 +342,8 @@ int edt_hip_subtract_device(const float *d_a, const float *d_b, float *d_out, in
 /* pyedt::extract_runs (src/edt_voxel_graph.hpp:238-268) on device-resident labels: the START offsets of the
  * maximal constant runs of the flattened array, ascending (run k = [starts[k], starts[k+1]) resp. up to count for
  * the last one; its label is labels[starts[k]]).  *d_count receives the number of runs; at most `capacity` starts are
- * written (capacity = 0, d_starts = NULL: count only).  Enqueue-only; scratch: edt_hip_runs_workspace_bytes. */
+ * written (capacity = 0, d_starts = NULL: count only).  Enqueue-only; scratch: edt_hip_runs_workspace_bytes -- initialised
+ * by the call itself; a reused one needs no memset. */
 size_t edt_hip_runs_workspace_bytes(int64_t count);
 int edt_hip_extract_runs_device(const void *d_labels, int dtype, int64_t count, int64_t *d_starts, int64_t capacity,
                                 int64_t *d_count, void *d_workspace, size_t workspace_bytes, void *stream);
@@ -344,7 +357,7 @@ int edt_hip_is_background_device(const void *d_labels, int dtype, uint8_t *d_mas
  * output live in HBM; enqueue-only on `stream`.  Scratch: edt_hip_voxel_graph_workspace_bytes (native form: the
  * even-x cells of the doubled grid as fp32, 4 x voxels floats, and the bit planes of its two column passes; the
  * up-sampled fallback for doubled axes beyond 2048 rows: the 2x uint8 volume, its fp32 transform and the
- * ordinary workspace of that volume). */
+ * ordinary workspace of that volume).  The workspace is initialised by the call itself; a reused one needs no memset. */
 size_t edt_hip_voxel_graph_workspace_bytes(int ndim, int64_t sx, int64_t sy, int64_t sz);
 int edt_hip_edtsq_voxel_graph_device(const void *d_labels, int dtype, const uint8_t *d_graph, int ndim,
                                      int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
@@ -384,7 +397,8 @@ size_t edt_hip_feature_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t 
  * flags: EDT_FLAG_BLACK_BORDER, EDT_FLAG_FORCE_GENERIC (accepted; every axis length runs on the size-agnostic column
  * kernel, so the features are the same); any other flag is EDT_ERR_UNSUPPORTED.  ndim 1..3, unused extents 1, voxel
  * sizes as for edt_hip_edtsq_device (EDT_ERR_BAD_ARG before any device work).  NULL pointers and a missing or too small
- * workspace are EDT_ERR_BAD_ARG.  Enqueue-only on `stream`: no allocation, no synchronisation. */
+ * workspace are EDT_ERR_BAD_ARG.  Enqueue-only on `stream`: no allocation, no synchronisation; the workspace is initialised
+ * by the call itself (a reused one needs no memset). */
 int edt_hip_feature_transform_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
                                      float wy, float wz, int flags, int32_t *d_features, void *d_workspace,
                                      size_t workspace_bytes, void *stream);
@@ -399,7 +413,8 @@ int edt_hip_feature_transform(const void *labels, int dtype, int ndim, int64_t s
  * in fp64 from the integer offsets and the fp32 voxel sizes widened to fp64 (no fma); otherwise out[p] keeps its own
  * (background) value.  No foreground at all: out is a copy of labels.  distance >= 0, +inf allowed; NaN or negative is
  * EDT_ERR_BAD_ARG.  The output has the labels' dtype and may not alias them.  Scratch: one byte per voxel for the mask
- * plus the feature transform's workspace of the mask. */
+ * plus the feature transform's workspace of the mask -- initialised by the call itself; a reused one needs no memset.
+ * Enqueue-only on `stream`. */
 size_t edt_hip_expand_labels_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
 int edt_hip_expand_labels_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx,
                                  float wy, float wz, double distance, void *d_out, void *d_workspace, size_t workspace_bytes,
