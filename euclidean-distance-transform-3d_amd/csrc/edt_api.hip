@@ -277,6 +277,34 @@ int require_device() {
   return EDT_OK;
 }
 
+bool label_op_begin(const char *who, int own_rc, void *d_result, size_t result_words, int64_t voxels, bool null_data,
+                    bool aliased, const void *d_workspace, size_t workspace_bytes, size_t needed, const char *query,
+                    hipStream_t stream, int *rc) {
+  const auto refuse = [&](const std::string &why) {
+    set_error(std::string(who) + ": " + why);
+    *rc = EDT_ERR_BAD_ARG;
+    return false;
+  };
+  if ((*rc = own_rc) != EDT_OK) return false;
+  if (!d_result) return refuse("null device pointer");
+  if (voxels > 0) {
+    if (null_data) return refuse("null device pointer");
+    if (aliased) return refuse("the output may not alias the labels");
+    if (!d_workspace || workspace_bytes < needed) return refuse(std::string("workspace missing or smaller than ") + query + "()");
+    if ((*rc = check_workspace_alignment(d_workspace)) != EDT_OK) return false;
+  }
+  if ((*rc = require_device()) != EDT_OK) return false;
+  if (voxels == 0) {
+    *rc = launch_fill_words(d_result, 0u, result_words * sizeof(int64_t) / sizeof(uint32_t), stream);
+    return false;
+  }
+  if (g_log.enabled.load(std::memory_order_relaxed)) {
+    std::lock_guard<std::mutex> lock(g_log_mutex);
+    log_begin_call();
+  }
+  return true;
+}
+
 // ---- the pass pipeline on device-resident data -----------------------------------------
 int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
                       float wx, float wy, float wz, int flags, float *d_out, void *d_ws,

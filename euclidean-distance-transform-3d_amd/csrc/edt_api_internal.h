@@ -43,6 +43,15 @@ int check_voxel_sizes(int naxes, float &wx, float &wy, float &wz);  // (drops th
 int check_column_voxel_size(float &w);
 bool signed_transform_supported(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags);  // EDT_FLAG_SIGNED
 int require_device();
+// What the device entry points of the label operations (connected_components, fill_holes, dust, label_stats) do before their
+// launch, in this order: the call's own argument check (own_rc: its result), the scalar result pointer (d_result: result_words
+// int64), then for a volume that is not empty the data pointers (null_data), aliasing (aliased: the output is the labels and the call
+// does not allow it), the workspace (`needed` bytes, what `query` returns) and its alignment; the device; an empty volume zeroes the
+// result words on `stream`; a new call in the pass log.  true: go on to the launch; false: return *rc -- a refusal, named
+// "<who>: ...", or what became of the empty volume.
+bool label_op_begin(const char *who, int own_rc, void *d_result, size_t result_words, int64_t voxels, bool null_data,
+                    bool aliased, const void *d_workspace, size_t workspace_bytes, size_t needed, const char *query,
+                    hipStream_t stream, int *rc);
 // the pass pipeline on device-resident data
 int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                int flags, float *d_out, void *d_ws, size_t ws_bytes, hipStream_t stream);

@@ -30,24 +30,18 @@
 //                 this is why a volume has at most 2^31 - 1 voxels.
 #include <type_traits>
 
-#include "edt_api_internal.h"
+#include "edt_forest.h"
 
 namespace edt_amd {
 namespace {
 
-// (kCcBg, background in P, and kCcTag: edt_kernels.h -- a tagged rank is at most kCcTag | (2^31 - 2))
+// (kCcBg, kCcTag, kCcMaxVoxels, label_fg, label_conn, parent_peek, wave_sum: edt_forest.h)
 constexpr int kCcThreads = 256;
 constexpr int kCcGroups = 4;                      // 64-voxel groups per wave and step (256-byte loads of 4-byte labels)
 constexpr int kCcTile = 64 * kCcGroups;
 constexpr int kCcBlocks = 256 * 8;                // grid of the striding sweeps
 constexpr int kCcChunk = 2048;                    // voxels per workgroup of the numbering kernels
 constexpr int kCcScan = 1024;                     // chunks per round of the scan
-constexpr int64_t kCcMaxVoxels = 0x7FFFFFFF;
-
-template <typename T> __device__ __forceinline__ bool cc_fg(T v) { return v != (T)0; }  // (-0.0 is background, NaN is not)
-template <typename T> __device__ __forceinline__ bool cc_conn(T a, T b, int binary) {
-  return binary ? (cc_fg(a) && cc_fg(b)) : (a == b && cc_fg(a));
-}
 
 // the label of lane `src` / of the lane below, at any width
 template <typename T> __device__ __forceinline__ T cc_shfl(T v, int src) {
@@ -67,16 +61,12 @@ template <typename T> __device__ __forceinline__ T cc_shfl_up1(T v) {
   return v;
 }
 
-__device__ __forceinline__ uint32_t cc_peek(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // the root above i: strictly downhill (P[j] <= j), so at most i steps
 __device__ __forceinline__ uint32_t cc_find(uint32_t *P, uint32_t i) {
   const uint32_t from = i;
   int steps = 0;
   for (;;) {
-    const uint32_t p = cc_peek(&P[i]);
+    const uint32_t p = parent_peek(&P[i]);
     if (p >= i) break;  // a root (p == i); p > i cannot be (background is never walked)
     i = p;
     ++steps;
@@ -124,11 +114,11 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_rows(const T *__restrict__ la
         const T last = cc_shfl(v[j - 1], 63);
         if (lane == 0) pv = last;
       }
-      const bool cont = x != 0 && !(j == 0 && lane == 0) && cc_conn(pv, v[j], binary);
+      const bool cont = x != 0 && !(j == 0 && lane == 0) && label_conn(pv, v[j], binary);
       const uint64_t m = __ballot(!cont);
       const uint64_t below = m & ((2ull << lane) - 1ull);
       const uint32_t par = below ? base + j * 64 + (uint32_t)(63 - __builtin_clzll(below)) : carry;
-      if (idx < voxels) P[idx] = cc_fg(v[j]) ? par : kCcBg;
+      if (idx < voxels) P[idx] = label_fg(v[j]) ? par : kCcBg;
       carry = __shfl(par, 63);
     }
   }
@@ -139,12 +129,12 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_rows(const T *__restrict__ la
 template <typename T>
 __device__ __forceinline__ void cc_visit(const T *__restrict__ labels, uint32_t *P, T v, uint32_t p, uint32_t q0, uint32_t x,
                                          uint32_t sx, bool L, bool dilate, int binary) {
-  const bool mc = cc_conn(v, labels[q0], binary);
+  const bool mc = label_conn(v, labels[q0], binary);
   if (!dilate) {
-    if (mc && !(L && cc_conn(v, labels[q0 - 1], binary))) cc_union(P, p, q0);  // (L: x > 0)
+    if (mc && !(L && label_conn(v, labels[q0 - 1], binary))) cc_union(P, p, q0);  // (L: x > 0)
     return;
   }
-  const bool mr = x + 1 < sx && cc_conn(v, labels[q0 + 1], binary);
+  const bool mr = x + 1 < sx && label_conn(v, labels[q0 + 1], binary);
   if (L) {
     if (mr && !mc) cc_union(P, p, q0 + 1);
     return;
@@ -153,7 +143,7 @@ __device__ __forceinline__ void cc_visit(const T *__restrict__ labels, uint32_t 
     cc_union(P, p, q0);
     return;
   }
-  if (x > 0 && cc_conn(v, labels[q0 - 1], binary)) cc_union(P, p, q0 - 1);
+  if (x > 0 && label_conn(v, labels[q0 - 1], binary)) cc_union(P, p, q0 - 1);
   if (mr) cc_union(P, p, q0 + 1);
 }
 
@@ -165,10 +155,10 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_merge(const T *__restrict__ l
   const uint32_t stride = gridDim.x * kCcThreads;
   for (uint32_t p = blockIdx.x * kCcThreads + threadIdx.x; p < voxels; p += stride) {  // (voxels + stride < 2^32)
     const T v = labels[p];
-    if (!cc_fg(v)) continue;
+    if (!label_fg(v)) continue;
     const uint32_t row = p / sx, x = p - row * sx;
     const uint32_t z = row / sy, y = row - z * sy;
-    const bool L = x > 0 && cc_conn(labels[p - 1], v, binary);
+    const bool L = x > 0 && label_conn(labels[p - 1], v, binary);
     if (L && (p % kCcTile) == 0) cc_union(P, p, p - 1);  // the cut of k_cc_rows
     if (y > 0) cc_visit(labels, P, v, p, p - sx, x, sx, L, near_dilate, binary);
     if (z > 0) {
@@ -189,12 +179,12 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_flatten(uint32_t *P, uint32_t
   for (int k = 0; k < kCcChunk / kCcThreads; ++k) {
     const uint32_t i = base + k * kCcThreads + threadIdx.x;
     if (i >= voxels) continue;
-    const uint32_t p = cc_peek(&P[i]);
+    const uint32_t p = parent_peek(&P[i]);
     if (p == kCcBg) continue;
     uint32_t r = p;
     if (p != i)
       for (;;) {  // strictly downhill
-        const uint32_t n = cc_peek(&P[r]);
+        const uint32_t n = parent_peek(&P[r]);
         if (n >= r) break;
         r = n;
       }
@@ -202,7 +192,7 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_flatten(uint32_t *P, uint32_t
     roots += r == i;
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) roots += __shfl_xor(roots, off);
+  for (int off = 32; off > 0; off >>= 1) roots += __shfl_xor(roots, off);  // (not wave_sum: the kernel's code would change)
   if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = roots;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -273,39 +263,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_final(uint32_t *P, uint32_t v
     P[i] = 0u;
     return;
   }
-  if (!(p & kCcTag)) p = cc_peek(&P[p]);  // the root's word: tagged rank, or (its own thread was here) already its number
+  if (!(p & kCcTag)) p = parent_peek(&P[p]);  // the root's word: tagged rank, or (its own thread was here) already its number
   P[i] = (p & kCcTag) ? (p & ~kCcTag) + 1u : p;
-}
-
-// rows, merge, flatten: the forest of `labels` in P, the per-chunk root counts in `chunk`.  names: the three passes in the log
-struct ForestNames {
-  const char *rows, *merge, *flatten;
-};
-template <typename T>
-int launch_forest(const T *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int bin, uint32_t *P, uint32_t *chunk,
-                  const ForestNames &names, hipStream_t stream) {
-  const int64_t voxels64 = sx * sy * sz;
-  const uint32_t voxels = (uint32_t)voxels64;
-  const int waves = kCcThreads / 64;
-  {
-    ScopedPass sp(names.rows, stream);
-    const int64_t blocks = std::min<int64_t>(ceil_div(ceil_div(voxels64, kCcTile), waves), kCcBlocks);
-    hipLaunchKernelGGL(k_cc_rows<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, labels, P, voxels, (uint32_t)sx, bin);
-    EDT_HIP_TRY(hipGetLastError());
-  }
-  {
-    ScopedPass sp(names.merge, stream);
-    const int64_t blocks = std::min<int64_t>(ceil_div(voxels64, kCcThreads), kCcBlocks * 4);
-    hipLaunchKernelGGL(k_cc_merge<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, labels, P, voxels, (uint32_t)sx,
-                       (uint32_t)sy, connectivity, bin);
-    EDT_HIP_TRY(hipGetLastError());
-  }
-  {
-    ScopedPass sp(names.flatten, stream);
-    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, voxels, chunk);
-    EDT_HIP_TRY(hipGetLastError());
-  }
-  return EDT_OK;
 }
 
 }  // namespace
@@ -314,20 +273,50 @@ size_t components_workspace_bytes(int64_t voxels) {
   return align_up((size_t)ceil_div(std::max<int64_t>(voxels, 1), kCcChunk) * sizeof(uint32_t), 256);
 }
 
+// (contract: edt_forest.h)
+int launch_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary, uint32_t *P,
+                  void *chunks, const char *who, hipStream_t stream) {
+  const int64_t voxels64 = sx * sy * sz;
+  if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error(std::string(who) + ": volume out of range"); return EDT_ERR_UNSUPPORTED; }
+  const uint32_t voxels = (uint32_t)voxels64;
+  const int bin = (binary || dtype == EDT_BOOL) ? 1 : 0;
+  char rows[40], merge[40], flatten[40];  // (on the stack: the pass log copies the names it keeps)
+  snprintf(rows, sizeof rows, "%s rows", who);
+  snprintf(merge, sizeof merge, "%s merge", who);
+  snprintf(flatten, sizeof flatten, "%s flatten", who);
+  return with_label_type(dtype, [&](auto t) -> int {
+    using T = typename decltype(t)::type;
+    const int waves = kCcThreads / 64;
+    {
+      ScopedPass sp(rows, stream);
+      const int64_t blocks = std::min<int64_t>(ceil_div(ceil_div(voxels64, kCcTile), waves), kCcBlocks);
+      hipLaunchKernelGGL(k_cc_rows<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, (const T *)labels, P, voxels,
+                         (uint32_t)sx, bin);
+      EDT_HIP_TRY(hipGetLastError());
+    }
+    {
+      ScopedPass sp(merge, stream);
+      const int64_t blocks = std::min<int64_t>(ceil_div(voxels64, kCcThreads), kCcBlocks * 4);
+      hipLaunchKernelGGL(k_cc_merge<T>, dim3((unsigned)blocks), dim3(kCcThreads), 0, stream, (const T *)labels, P, voxels,
+                         (uint32_t)sx, (uint32_t)sy, connectivity, bin);
+      EDT_HIP_TRY(hipGetLastError());
+    }
+    ScopedPass sp(flatten, stream);
+    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, voxels,
+                       static_cast<uint32_t *>(chunks));
+    EDT_HIP_TRY(hipGetLastError());
+    return EDT_OK;
+  });
+}
+
 int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                       uint32_t *out, int64_t *n, void *ws, hipStream_t stream) {
+  const int rc = launch_forest(dtype, labels, sx, sy, sz, connectivity, binary, out, ws, "components", stream);
+  if (rc != EDT_OK) return rc;
   const int64_t voxels64 = sx * sy * sz;
-  if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error("connected_components: volume out of range"); return EDT_ERR_UNSUPPORTED; }
   const uint32_t voxels = (uint32_t)voxels64;
   uint32_t *chunk = static_cast<uint32_t *>(ws);
   const uint32_t nchunks = (uint32_t)ceil_div(voxels64, kCcChunk);
-  const int bin = (binary || dtype == EDT_BOOL) ? 1 : 0;
-  const int rc = with_label_type(dtype, [&](auto t) -> int {
-    using T = typename decltype(t)::type;
-    return launch_forest((const T *)labels, sx, sy, sz, connectivity, bin, out, chunk,
-                         {"components rows", "components merge", "components flatten"}, stream);
-  });
-  if (rc != EDT_OK) return rc;
   {
     ScopedPass sp("components number", stream);
     hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kCcScan), 0, stream, chunk, nchunks, n);
@@ -341,29 +330,6 @@ int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int
     EDT_HIP_TRY(hipGetLastError());
   }
   return EDT_OK;
-}
-
-// The forest alone -- rows, merge, flatten, no numbering -- of a volume of 0/1 bytes: fill_holes (edt_fillholes.hip) runs it over
-// the mask labels == 0.  Afterwards P[i] is the smallest idx of i's component for every non-zero byte and kCcBg elsewhere.
-int launch_components_forest(const uint8_t *mask, int64_t sx, int64_t sy, int64_t sz, int connectivity, uint32_t *P, void *ws,
-                             hipStream_t stream) {
-  const int64_t voxels64 = sx * sy * sz;
-  if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error("components forest: volume out of range"); return EDT_ERR_UNSUPPORTED; }
-  return launch_forest(mask, sx, sy, sz, connectivity, 1, P, static_cast<uint32_t *>(ws),
-                       {"fill_holes rows", "fill_holes merge", "fill_holes flatten"}, stream);
-}
-
-// ... and of labels of any dtype: dust (edt_dust.hip) sizes and filters the components themselves
-int launch_labels_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
-                         uint32_t *P, void *ws, hipStream_t stream) {
-  const int64_t voxels64 = sx * sy * sz;
-  if (voxels64 < 1 || voxels64 > kCcMaxVoxels) { set_error("labels forest: volume out of range"); return EDT_ERR_UNSUPPORTED; }
-  const int bin = (binary || dtype == EDT_BOOL) ? 1 : 0;
-  return with_label_type(dtype, [&](auto t) -> int {
-    using T = typename decltype(t)::type;
-    return launch_forest((const T *)labels, sx, sy, sz, connectivity, bin, P, static_cast<uint32_t *>(ws),
-                         {"dust rows", "dust merge", "dust flatten"}, stream);
-  });
 }
 
 // sx * sy * sz <= 2^31 - 1, in 64-bit arithmetic (extents are at most 2^31 - 1 each: check_shape)
@@ -403,27 +369,29 @@ int edt_hip_connected_components_device(const void *d_labels, int dtype, int ndi
                                         int connectivity, int binary, uint32_t *d_out, int64_t *d_n, void *d_workspace,
                                         size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = components_check_args(dtype, ndim, sx, sy, sz, connectivity);
-  if (rc != EDT_OK) return rc;
-  if (!d_n) { set_error("connected_components: null device pointer"); return EDT_ERR_BAD_ARG; }
-  const int64_t voxels = sx * sy * sz;
-  if (voxels > 0) {
-    if (!d_labels || !d_out) { set_error("connected_components: null device pointer"); return EDT_ERR_BAD_ARG; }
-    if (!d_workspace || workspace_bytes < components_workspace_bytes(voxels)) {
-      set_error("connected_components: workspace missing or smaller than edt_hip_components_workspace_bytes()");
-      return EDT_ERR_BAD_ARG;
-    }
-    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
-  }
-  if ((rc = require_device()) != EDT_OK) return rc;
-  if (voxels == 0) {
-    return launch_fill_words(d_n, 0u, sizeof(int64_t) / sizeof(uint32_t), stream);
-  }
-  if (g_log.enabled.load(std::memory_order_relaxed)) {
-    std::lock_guard<std::mutex> lock(g_log_mutex);
-    log_begin_call();
-  }
+  const int own = components_check_args(dtype, ndim, sx, sy, sz, connectivity);
+  const int64_t voxels = own == EDT_OK ? sx * sy * sz : 0;
+  int rc;
+  if (!label_op_begin("connected_components", own, d_n, 1, voxels, !d_labels || !d_out, false, d_workspace, workspace_bytes,
+                      components_workspace_bytes(voxels), "edt_hip_components_workspace_bytes", stream, &rc))
+    return rc;
   return launch_components(dtype, d_labels, sx, sy, sz, connectivity, binary, d_out, d_n, d_workspace, stream);
 }
 
 }  // extern "C"
+
+// The label types in the order in which their kernels stand in the code object -- one-byte labels last, as measured in
+// DESIGN 10-12.  Left to the order of first use they would come first and every other instantiation sit two kernels further on,
+// and a kernel that moves is timed anew although no instruction of it changed.  Nothing but this list holds the order: a first
+// use of k_cc_rows<T> or k_cc_merge<T> above it reorders them again.  To re-check after a change to this unit, compile it with
+// the Makefile's flags plus  -S --cuda-device-only  at this commit and at the previous one and diff the two files: only the
+// __hip_cuid lines may differ.
+namespace edt_amd {
+namespace {
+#define EDT_CC_KERNELS(T)                                                                \
+  template __global__ void k_cc_rows<T>(const T *, uint32_t *, uint32_t, uint32_t, int); \
+  template __global__ void k_cc_merge<T>(const T *, uint32_t *, uint32_t, uint32_t, uint32_t, int, int);
+EDT_CC_KERNELS(uint16_t) EDT_CC_KERNELS(uint32_t) EDT_CC_KERNELS(uint64_t) EDT_CC_KERNELS(float) EDT_CC_KERNELS(double) EDT_CC_KERNELS(uint8_t)
+#undef EDT_CC_KERNELS
+}  // namespace
+}  // namespace edt_amd

@@ -1,7 +1,7 @@
 // edt_dust.hip -- dust: connected components are kept or removed by their voxel count (include/edt_hip.h, "dust", states the
 // contract).
 //
-// The components come from the union-find of edt_components.hip, run over the labels themselves (launch_labels_forest:
+// The components come from the union-find of edt_components.hip, run over the labels themselves (launch_forest:
 // k_cc_rows / k_cc_merge / k_cc_flatten, no numbering).  After it every foreground voxel i holds its component's root in P[i] --
 // the component's smallest idx -- a root holds itself, and background holds kCcBg.
 //
@@ -11,7 +11,8 @@
 // the component's smallest idx, so r - 1 is never of r's component and r always begins a stretch -- adds  kCcTag - r  on top.  The
 // sum is the same in every order: r + (kCcTag - r) + size.  While the adds are in flight the word of root r is r + (part of the
 // size) with or without the tag, in any case >= r and below 2^32; every other foreground word is a root's idx < i and never
-// changes.  So the count kernel tells a root by P[i] >= i, whatever has been added already, and reads nothing but P[i] itself.
+// changes.  So the count kernel tells a root by P[i] >= i (the root rule of edt_forest.h), whatever has been added already, and
+// reads nothing but P[i] itself.
 //
 //   rows, merge, flatten   the forest of the labels in P                                      (edt_components.hip)
 //   k_dust_count   a wave walks EDT_HIP_DUST_COUNT_SPAN consecutive voxels, 64 at a time.  A stretch is a maximal range of
@@ -30,7 +31,7 @@
 //                  atomics per workgroup.
 // Phases are separate launches; no thread waits for another, every loop is bounded by its inputs, and every reduction is an
 // integer add, so the result does not depend on which thread won an atomic.
-#include "edt_api_internal.h"
+#include "edt_forest.h"
 
 namespace edt_amd {
 namespace {
@@ -44,19 +45,9 @@ constexpr int kDustAdopt = 2;                           // slots a 64-voxel grou
 constexpr uint32_t kDustNone = 0xFFFFFFFEu;             // "no voxel before this one": neither a root (< 2^31) nor kCcBg
 static_assert(kDustSpan % (64 * kDustBatch) == 0, "a span is whole batches of groups");
 
-template <typename T> __device__ __forceinline__ bool dust_fg(T v) { return v != (T)0; }  // (-0.0 is background, NaN is not)
-__device__ __forceinline__ uint32_t dust_peek(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // what the stretch [first, first + len) of root r adds to the root's word
 __device__ __forceinline__ uint32_t dust_amount(uint32_t r, uint32_t first, uint32_t len) {
   return r == first ? len + (kCcTag - r) : len;
-}
-__device__ __forceinline__ uint32_t dust_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 // The adds a wave has not sent yet: kDustSlots roots (wave-uniform) and what their stretches came to so far.
@@ -75,7 +66,7 @@ __device__ __forceinline__ void dust_combine(uint32_t *P, DustSlots &s, bool pen
   for (int k = 0; k < kDustSlots; ++k) {
     const bool match = pending && r == s.root[k];  // (an empty slot holds kDustNone, which is nobody's root)
     if (__ballot(match)) {
-      s.sum[k] += (uint32_t)__builtin_amdgcn_readfirstlane((int)dust_wave_sum(match ? amount : 0u));
+      s.sum[k] += (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum(match ? amount : 0u));
       pending = pending && !match;
     }
   }
@@ -83,7 +74,7 @@ __device__ __forceinline__ void dust_combine(uint32_t *P, DustSlots &s, bool pen
   for (int j = 0; j < kDustAdopt && left; ++j) {
     const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)__shfl(r, __ffsll((unsigned long long)left) - 1));
     const bool match = pending && r == c;
-    const uint32_t sum = (uint32_t)__builtin_amdgcn_readfirstlane((int)dust_wave_sum(match ? amount : 0u));
+    const uint32_t sum = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum(match ? amount : 0u));
     int victim = 0;
     uint32_t least = s.sum[0];
 #pragma unroll
@@ -127,8 +118,8 @@ __global__ __launch_bounds__(kDustThreads) void k_dust_count(uint32_t *P, uint32
       const uint32_t i = bbase + j * 64 + lane;
       uint32_t r = kCcBg;  // (past the end: background)
       if (i < voxels) {
-        const uint32_t p = dust_peek(&P[i]);
-        r = p == kCcBg ? kCcBg : (p >= i ? i : p);  // a root's word: itself plus what has been added so far
+        const uint32_t p = parent_peek(&P[i]);
+        r = p == kCcBg ? kCcBg : (is_root(i, p) ? i : p);  // a root's word: itself plus what has been added so far
       }
       root[j] = r;
     }
@@ -172,13 +163,15 @@ __global__ __launch_bounds__(kDustThreads) void k_dust_filter(const T *labels, c
   uint32_t found = 0, kept = 0, removed = 0;  // (a thread sees fewer than 2^31 voxels)
   for (uint32_t i = blockIdx.x * kDustThreads + threadIdx.x; i < voxels; i += stride) {  // (voxels + stride < 2^32)
     T v = labels[i];
-    if (dust_fg(v)) {
+    if (label_fg(v)) {
       const uint32_t p = P[i];
-      const bool is_root = (p & kCcTag) != 0;        // (a foreground word is a root's idx < 2^31, or a root's tagged size)
-      const int64_t size = (int64_t)((is_root ? p : P[p]) & ~kCcTag);
+      // (a foreground word is a root's idx < 2^31, or a root's tagged size: here the tag says what the root rule of edt_forest.h
+      // says, and the kernel keeps the test it was compiled with)
+      const bool tagged = (p & kCcTag) != 0;
+      const int64_t size = (int64_t)((tagged ? p : P[p]) & ~kCcTag);
       const bool keep = (size >= min_voxels && size < max_voxels) != (invert != 0);
-      found += is_root;
-      kept += is_root && keep;
+      found += tagged;
+      kept += tagged && keep;
       if (!keep) {
         ++removed;
         __builtin_memset(&v, 0, sizeof(T));
@@ -187,7 +180,7 @@ __global__ __launch_bounds__(kDustThreads) void k_dust_filter(const T *labels, c
     out[i] = v;
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
+  for (int off = 32; off > 0; off >>= 1) {  // (three sums in step, not wave_sum: the kernel's code would change)
     found += __shfl_xor(found, off);
     kept += __shfl_xor(kept, off);
     removed += __shfl_xor(removed, off);
@@ -205,16 +198,13 @@ __global__ __launch_bounds__(kDustThreads) void k_dust_filter(const T *labels, c
   }
 }
 
-size_t dust_parent_bytes(int64_t voxels) { return align_up((size_t)std::max<int64_t>(voxels, 1) * sizeof(uint32_t), 256); }
-
 int launch_dust(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary, int64_t min_voxels,
                 int64_t max_voxels, int invert, void *out, int64_t *counts, void *ws, hipStream_t stream) {
   const int64_t voxels = sx * sy * sz;
-  Carver carve(ws);
-  uint32_t *P = carve.take<uint32_t>((size_t)voxels);
-  void *chunks = carve.take<char>(components_workspace_bytes(voxels));
+  const ForestWorkspace w(ws, voxels);
+  uint32_t *P = w.P;
   int rc;
-  if ((rc = launch_labels_forest(dtype, labels, sx, sy, sz, connectivity, binary, P, chunks, stream)) != EDT_OK) return rc;
+  if ((rc = launch_forest(dtype, labels, sx, sy, sz, connectivity, binary, P, w.chunks, "dust", stream)) != EDT_OK) return rc;
   {
     ScopedPass sp("dust count", stream);
     if ((rc = launch_fill_words(counts, 0u, 3 * sizeof(int64_t) / sizeof(uint32_t), stream)) != EDT_OK) return rc;
@@ -254,33 +244,19 @@ extern "C" {
 
 size_t edt_hip_dust_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz) {
   const size_t chunks = edt_hip_components_workspace_bytes(dtype, ndim, sx, sy, sz);  // (0: a bad dtype or shape, or past the limit)
-  return chunks == 0 ? 0 : dust_parent_bytes(sx * sy * sz) + chunks;
+  return chunks == 0 ? 0 : ForestWorkspace::bytes(sx * sy * sz);
 }
 
 int edt_hip_dust_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                         int64_t min_voxels, int64_t max_voxels, int invert, void *d_out, int64_t *d_counts, void *d_workspace,
                         size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = dust_check_args(dtype, ndim, sx, sy, sz, connectivity, min_voxels, max_voxels);
-  if (rc != EDT_OK) return rc;
-  if (!d_counts) { set_error("dust: null device pointer"); return EDT_ERR_BAD_ARG; }
-  const int64_t voxels = sx * sy * sz;
-  if (voxels > 0) {
-    if (!d_labels || !d_out) { set_error("dust: null device pointer"); return EDT_ERR_BAD_ARG; }
-    if (!d_workspace || workspace_bytes < dust_parent_bytes(voxels) + components_workspace_bytes(voxels)) {
-      set_error("dust: workspace missing or smaller than edt_hip_dust_workspace_bytes()");
-      return EDT_ERR_BAD_ARG;
-    }
-    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
-  }
-  if ((rc = require_device()) != EDT_OK) return rc;
-  if (voxels == 0) {
-    return launch_fill_words(d_counts, 0u, 3 * sizeof(int64_t) / sizeof(uint32_t), stream);
-  }
-  if (g_log.enabled.load(std::memory_order_relaxed)) {
-    std::lock_guard<std::mutex> lock(g_log_mutex);
-    log_begin_call();
-  }
+  const int own = dust_check_args(dtype, ndim, sx, sy, sz, connectivity, min_voxels, max_voxels);
+  const int64_t voxels = own == EDT_OK ? sx * sy * sz : 0;
+  int rc;
+  if (!label_op_begin("dust", own, d_counts, 3, voxels, !d_labels || !d_out, false, d_workspace, workspace_bytes,
+                      ForestWorkspace::bytes(voxels), "edt_hip_dust_workspace_bytes", stream, &rc))
+    return rc;
   return launch_dust(dtype, d_labels, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, d_out, d_counts,
                      d_workspace, stream);
 }

@@ -2,17 +2,17 @@
 // (include/edt_hip.h, "fill holes", states the contract).
 //
 // The background's components come from the union-find of edt_components.hip, run over the mask labels == 0
-// (launch_components_forest: k_cc_rows / k_cc_merge / k_cc_flatten of one-byte labels, no numbering).  After it every background
+// (launch_forest: k_cc_rows / k_cc_merge / k_cc_flatten of one-byte labels, no numbering).  After it every background
 // voxel i holds its component's root in P[i] -- the component's smallest idx -- and a root holds itself.
 //
 // Room for the state of a component: a root's own word.  It is only ever a self-pointer, and idx < 2^31, so the top bit of every
-// parent is clear.  A root's word becomes  kFhTag | (0x7FFFFFFF - s)  with the state s:
+// parent is clear.  A root's word becomes  kCcTag | (0x7FFFFFFF - s)  with the state s:
 //     s = 0        the component is open (touches the array's boundary) or mixed (its wall holds two labels): not filled
 //     s = q + 1    q is the smallest idx seen so far of a wall voxel
 // and every update is atomicMax of that word: an untagged self-pointer is below every tagged value (the first update replaces
 // it), a smaller s is a larger word (the minimum of s survives), and s = 0 is the largest word there is (open and mixed are
 // final).  The representative q lies below the root -- the root's x-1 neighbour exists in a cavity and is a wall voxel -- so
-// q + 1 <= 2^31 - 2.  A voxel i is a root iff P[i] >= i (itself, or tagged); every other voxel's word never changes.
+// q + 1 <= 2^31 - 2.  A voxel i is a root iff P[i] >= i (itself, or tagged: the root rule of edt_forest.h).
 //
 // The mask lives in the first sx*sy*sz bytes of the OUTPUT array, which nothing else uses until the last sweep writes it (by then
 // the mask is dead), so the workspace is the parent plane alone.
@@ -26,39 +26,23 @@
 //                  wave reduction and one 64-bit atomicAdd per workgroup
 // Phases are separate launches; no thread waits for another, every loop is bounded by its inputs, and every reduction is an
 // integer max or add, so the result does not depend on which thread won an atomic.
-#include "edt_api_internal.h"
+#include "edt_forest.h"
 
 namespace edt_amd {
 namespace {
 
-constexpr uint32_t kFhTag = 0x80000000u;
 constexpr uint32_t kFhDone = 0xFFFFFFFFu;  // s = 0: open or mixed
 constexpr uint32_t kFhNone = 0xFFFFFFFFu;  // "this lane has no update" (a root is at most 2^31 - 2)
 constexpr int kFhThreads = 256;
 constexpr int kFhBlocks = 256 * 8;         // grid of the striding sweeps
 
-template <typename T> __device__ __forceinline__ bool fh_fg(T v) { return v != (T)0; }  // (-0.0 is background, NaN is not)
-__device__ __forceinline__ uint32_t fh_word(uint32_t s) { return kFhTag | (0x7FFFFFFFu - s); }
+__device__ __forceinline__ uint32_t fh_word(uint32_t s) { return kCcTag | (0x7FFFFFFFu - s); }
 __device__ __forceinline__ uint32_t fh_state(uint32_t word) { return 0x7FFFFFFFu - (word & 0x7FFFFFFFu); }
-__device__ __forceinline__ uint32_t fh_peek(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 struct FhGeom {
   uint32_t voxels, sx, sy, sz;
   int ndim, c;
 };
-
-// the root of background voxel i and the root's word
-__device__ __forceinline__ uint32_t fh_root(const uint32_t *P, uint32_t i, uint32_t &word) {
-  const uint32_t p = fh_peek(&P[i]);
-  if (p >= i) {  // a root: itself, or its state
-    word = p;
-    return i;
-  }
-  word = fh_peek(&P[p]);
-  return p;
-}
 
 __device__ __forceinline__ bool fh_on_boundary(const FhGeom &g, uint32_t i) {
   const uint32_t row = i / g.sx, x = i - row * g.sx;
@@ -110,7 +94,7 @@ __global__ __launch_bounds__(kFhThreads) void k_fh_mark(const uint8_t *__restric
     uint32_t r = kFhNone, word = 0;
     if (i < g.voxels && bg[i]) {
       uint32_t cur;
-      const uint32_t root = fh_root(P, i, cur);
+      const uint32_t root = root_of(P, i, cur);
       if (cur != kFhDone) {
         if (fh_on_boundary(g, i)) {
           word = kFhDone;
@@ -138,8 +122,8 @@ __global__ __launch_bounds__(kFhThreads) void k_fh_check(const T *__restrict__ l
     uint32_t r = kFhNone;
     if (i < g.voxels && bg[i]) {
       uint32_t cur;
-      const uint32_t root = fh_root(P, i, cur);
-      if ((cur & kFhTag) && cur != kFhDone) {  // still closed, so i is interior: every neighbour exists
+      const uint32_t root = root_of(P, i, cur);
+      if ((cur & kCcTag) && cur != kFhDone) {  // still closed, so i is interior: every neighbour exists
         const T ref = labels[fh_state(cur) - 1];
         fh_neighbours(g, i, [&](uint32_t q) {
           if (bg[q] || labels[q] == ref) return false;
@@ -161,10 +145,10 @@ __global__ __launch_bounds__(kFhThreads) void k_fh_fill(const T *__restrict__ la
   uint32_t filled = 0;  // (a thread fills fewer than 2^31 voxels)
   for (uint32_t i = blockIdx.x * kFhThreads + threadIdx.x; i < voxels; i += stride) {
     T v = labels[i];
-    if (!fh_fg(v)) {
+    if (!label_fg(v)) {
       const uint32_t p = P[i];
-      const uint32_t word = p >= i ? p : P[p];
-      if ((word & kFhTag) && word != kFhDone) {
+      const uint32_t word = is_root(i, p) ? p : P[p];
+      if ((word & kCcTag) && word != kFhDone) {
         v = labels[fh_state(word) - 1];
         ++filled;
       }
@@ -172,7 +156,7 @@ __global__ __launch_bounds__(kFhThreads) void k_fh_fill(const T *__restrict__ la
     out[i] = v;
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) filled += __shfl_xor(filled, off);
+  for (int off = 32; off > 0; off >>= 1) filled += __shfl_xor(filled, off);  // (not wave_sum: the kernel's code would change)
   if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = filled;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -182,14 +166,11 @@ __global__ __launch_bounds__(kFhThreads) void k_fh_fill(const T *__restrict__ la
   }
 }
 
-size_t fh_parent_bytes(int64_t voxels) { return align_up((size_t)std::max<int64_t>(voxels, 1) * sizeof(uint32_t), 256); }
-
 int launch_fill_holes(int dtype, const void *labels, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                       void *out, int64_t *n_filled, void *ws, hipStream_t stream) {
   const int64_t voxels = sx * sy * sz;
-  Carver carve(ws);
-  uint32_t *P = carve.take<uint32_t>((size_t)voxels);
-  void *chunks = carve.take<char>(components_workspace_bytes(voxels));
+  const ForestWorkspace w(ws, voxels);
+  uint32_t *P = w.P;
   uint8_t *bg = static_cast<uint8_t *>(out);
   int rc;
   {
@@ -197,7 +178,7 @@ int launch_fill_holes(int dtype, const void *labels, int ndim, int64_t sx, int64
     if ((rc = launch_fill_words(n_filled, 0u, sizeof(int64_t) / sizeof(uint32_t), stream)) != EDT_OK) return rc;
     if ((rc = launch_is_background(dtype, labels, bg, voxels, stream)) != EDT_OK) return rc;
   }
-  if ((rc = launch_components_forest(bg, sx, sy, sz, connectivity, P, chunks, stream)) != EDT_OK) return rc;
+  if ((rc = launch_forest(EDT_U8, bg, sx, sy, sz, connectivity, 1, P, w.chunks, "fill_holes", stream)) != EDT_OK) return rc;
   const FhGeom g{(uint32_t)voxels, (uint32_t)sx, (uint32_t)sy, (uint32_t)sz, ndim, connectivity};
   const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(voxels, kFhThreads), kFhBlocks * 4);
   {
@@ -229,34 +210,20 @@ extern "C" {
 
 size_t edt_hip_fill_holes_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz) {
   const size_t chunks = edt_hip_components_workspace_bytes(dtype, ndim, sx, sy, sz);  // (0: a bad dtype or shape, or past the limit)
-  return chunks == 0 ? 0 : fh_parent_bytes(sx * sy * sz) + chunks;
+  return chunks == 0 ? 0 : ForestWorkspace::bytes(sx * sy * sz);
 }
 
 int edt_hip_fill_holes_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
                               int binary, void *d_out, int64_t *d_n_filled, void *d_workspace, size_t workspace_bytes,
                               void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = components_check_args(dtype, ndim, sx, sy, sz, connectivity, "fill_holes");
-  if (rc != EDT_OK) return rc;
-  if (!d_n_filled) { set_error("fill_holes: null device pointer"); return EDT_ERR_BAD_ARG; }
-  const int64_t voxels = sx * sy * sz;
-  if (voxels > 0) {
-    if (!d_labels || !d_out) { set_error("fill_holes: null device pointer"); return EDT_ERR_BAD_ARG; }
-    if (d_labels == d_out) { set_error("fill_holes: the output may not alias the labels"); return EDT_ERR_BAD_ARG; }
-    if (!d_workspace || workspace_bytes < fh_parent_bytes(voxels) + components_workspace_bytes(voxels)) {
-      set_error("fill_holes: workspace missing or smaller than edt_hip_fill_holes_workspace_bytes()");
-      return EDT_ERR_BAD_ARG;
-    }
-    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
-  }
-  if ((rc = require_device()) != EDT_OK) return rc;
-  if (voxels == 0) {
-    return launch_fill_words(d_n_filled, 0u, sizeof(int64_t) / sizeof(uint32_t), stream);
-  }
-  if (g_log.enabled.load(std::memory_order_relaxed)) {
-    std::lock_guard<std::mutex> lock(g_log_mutex);
-    log_begin_call();
-  }
+  const int own = components_check_args(dtype, ndim, sx, sy, sz, connectivity, "fill_holes");
+  const int64_t voxels = own == EDT_OK ? sx * sy * sz : 0;
+  int rc;
+  if (!label_op_begin("fill_holes", own, d_n_filled, 1, voxels, !d_labels || !d_out,
+                      d_labels == d_out, d_workspace, workspace_bytes,
+                      ForestWorkspace::bytes(voxels), "edt_hip_fill_holes_workspace_bytes", stream, &rc))
+    return rc;
   return launch_fill_holes(dtype, d_labels, ndim, sx, sy, sz, connectivity, binary, d_out, d_n_filled, d_workspace, stream);
 }
 

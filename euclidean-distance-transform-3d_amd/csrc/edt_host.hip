@@ -390,83 +390,44 @@ static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx,
   return st.down(bbox, kAux, m * 24, o_bbox);
 }
 
-// connected_components on host buffers (kernels: edt_components.hip): labels up once, the union-find on the device, the
-// numbers and their count down once.
-static int components_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
-                           int binary, uint32_t *out, int64_t *n) {
+// connected_components, fill_holes and dust on host buffers (kernels: edt_components.hip, edt_fillholes.hip, edt_dust.hip):
+// labels up once, the operation on the device, its output and its int64 results down once.  What tells the three apart:
+enum class Alias { ignored /* the output is of another type */, refused, in_place /* the result pages are the labels', and being read: no first touch */ };
+struct LabelOp {
+  const char *who;   // the call's name in its own refusals
+  size_t out_elem;   // bytes per voxel of the output
+  int words;         // int64 results
+  Alias alias;       // what out == labels means to it
+  size_t (*ws_query)(int, int, int64_t, int64_t, int64_t);  // its edt_hip_*_workspace_bytes
+};
+// own_check: what the call refuses after the shape (its *_check_args).  call(d_labels, d_out, d_result, d_ws, ws_bytes): its
+// device entry point.
+template <typename Check, typename Call>
+static int label_op_host(const LabelOp &op, const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, void *out,
+                         int64_t *result, Check own_check, Call call) {
   bool empty;
   int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !out, &empty, [&](After what) -> int {
-    if (what == After::shape) return components_check_args(dtype, ndim, sx, sy, sz, connectivity);
-    if (what == After::voxel_sizes && !n) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    if (what == After::shape) return own_check();
+    if (what == After::voxel_sizes && !result) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    if (what == After::pointers && op.alias == Alias::refused && labels == out) {
+      set_error(std::string(op.who) + ": the output may not alias the labels");
+      return EDT_ERR_BAD_ARG;
+    }
     return EDT_OK;
   });
-  if (rc == EDT_OK && empty) *n = 0;
+  if (rc == EDT_OK && empty) std::fill(result, result + op.words, int64_t(0));
   if (rc != EDT_OK || empty) return rc;
   ListedDevice on_listed_device;
   if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), obytes = voxels * sizeof(uint32_t);
-  const size_t wbytes = edt_hip_components_workspace_bytes(dtype, ndim, sx, sy, sz);
+  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), obytes = voxels * op.out_elem;
+  const size_t wbytes = op.ws_query(dtype, ndim, sx, sy, sz), rbytes = op.words * sizeof(int64_t);
   Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}, {kAux, sizeof(int64_t)}})) != EDT_OK) return rc;
-  st.expect(out, obytes);
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, obytes}, {kWorkspace, wbytes}, {kAux, rbytes}})) != EDT_OK) return rc;
+  if (!(op.alias == Alias::in_place && out == labels)) st.expect(out, obytes);
   if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  rc = edt_hip_connected_components_device(st.p[kLabels], dtype, ndim, sx, sy, sz, connectivity, binary, st.at<uint32_t>(kOut),
-                                           st.at<int64_t>(kAux), st.p[kWorkspace], wbytes, nullptr);
+  rc = call(st.p[kLabels], st.p[kOut], st.at<int64_t>(kAux), st.p[kWorkspace], wbytes);
   if (rc != EDT_OK || (rc = st.down(out, kOut, obytes)) != EDT_OK) return rc;
-  return st.down(n, kAux, sizeof(int64_t));
-}
-
-// fill_holes on host buffers (kernels: edt_fillholes.hip): labels up once, the background's forest and the fill on the device,
-// the filled labels and their count down once.
-static int fill_holes_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
-                           int binary, void *out, int64_t *n_filled) {
-  bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !out, &empty, [&](After what) -> int {
-    if (what == After::shape) return components_check_args(dtype, ndim, sx, sy, sz, connectivity, "fill_holes");
-    if (what == After::voxel_sizes && !n_filled) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-    if (what == After::pointers && labels == out) { set_error("fill_holes: the output may not alias the labels"); return EDT_ERR_BAD_ARG; }
-    return EDT_OK;
-  });
-  if (rc == EDT_OK && empty) *n_filled = 0;
-  if (rc != EDT_OK || empty) return rc;
-  ListedDevice on_listed_device;
-  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
-  const size_t wbytes = edt_hip_fill_holes_workspace_bytes(dtype, ndim, sx, sy, sz);
-  Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}, {kAux, sizeof(int64_t)}})) != EDT_OK) return rc;
-  st.expect(out, lbytes);
-  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  rc = edt_hip_fill_holes_device(st.p[kLabels], dtype, ndim, sx, sy, sz, connectivity, binary, st.p[kOut], st.at<int64_t>(kAux),
-                                 st.p[kWorkspace], wbytes, nullptr);
-  if (rc != EDT_OK || (rc = st.down(out, kOut, lbytes)) != EDT_OK) return rc;
-  return st.down(n_filled, kAux, sizeof(int64_t));
-}
-
-// dust on host buffers (kernels: edt_dust.hip): labels up once, the forest, the sizes and the filter on the device, the
-// filtered labels and the three counts down once.
-static int dust_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
-                     int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts) {
-  bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !out, &empty, [&](After what) -> int {
-    if (what == After::shape) return dust_check_args(dtype, ndim, sx, sy, sz, connectivity, min_voxels, max_voxels);
-    if (what == After::voxel_sizes && !counts) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-    return EDT_OK;
-  });
-  if (rc == EDT_OK && empty) counts[0] = counts[1] = counts[2] = 0;
-  if (rc != EDT_OK || empty) return rc;
-  ListedDevice on_listed_device;
-  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
-  const size_t wbytes = edt_hip_dust_workspace_bytes(dtype, ndim, sx, sy, sz);
-  Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}, {kAux, 3 * sizeof(int64_t)}})) != EDT_OK) return rc;
-  if (out != labels) st.expect(out, lbytes);  // (in place: the pages are the labels', and being read)
-  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  rc = edt_hip_dust_device(st.p[kLabels], dtype, ndim, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, st.p[kOut],
-                           st.at<int64_t>(kAux), st.p[kWorkspace], wbytes, nullptr);
-  if (rc != EDT_OK || (rc = st.down(out, kOut, lbytes)) != EDT_OK) return rc;
-  return st.down(counts, kAux, 3 * sizeof(int64_t));
+  return st.down(result, kAux, rbytes);
 }
 
 }  // namespace edt_amd
@@ -622,17 +583,34 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
 
 int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
                                  int connectivity, int binary, uint32_t *out, int64_t *n) {
-  return components_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, out, n);
+  return label_op_host(
+      {"connected_components", sizeof(uint32_t), 1, Alias::ignored, edt_hip_components_workspace_bytes}, labels, dtype, ndim, sx, sy,
+      sz, out, n, [&] { return components_check_args(dtype, ndim, sx, sy, sz, connectivity); },
+      [&](const void *d_labels, void *d_out, int64_t *d_n, void *d_ws, size_t ws_bytes) {
+        return edt_hip_connected_components_device(d_labels, dtype, ndim, sx, sy, sz, connectivity, binary, (uint32_t *)d_out, d_n,
+                                                   d_ws, ws_bytes, nullptr);
+      });
 }
 
 int edt_hip_fill_holes(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                        void *out, int64_t *n_filled) {
-  return fill_holes_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, out, n_filled);
+  return label_op_host(
+      {"fill_holes", (size_t)dtype_size(dtype), 1, Alias::refused, edt_hip_fill_holes_workspace_bytes}, labels, dtype, ndim, sx, sy, sz, out,
+      n_filled, [&] { return components_check_args(dtype, ndim, sx, sy, sz, connectivity, "fill_holes"); },
+      [&](const void *d_labels, void *d_out, int64_t *d_n, void *d_ws, size_t ws_bytes) {
+        return edt_hip_fill_holes_device(d_labels, dtype, ndim, sx, sy, sz, connectivity, binary, d_out, d_n, d_ws, ws_bytes, nullptr);
+      });
 }
 
 int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                  int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts) {
-  return dust_host(labels, dtype, ndim, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, out, counts);
+  return label_op_host(
+      {"dust", (size_t)dtype_size(dtype), 3, Alias::in_place, edt_hip_dust_workspace_bytes}, labels, dtype, ndim, sx, sy, sz, out, counts,
+      [&] { return dust_check_args(dtype, ndim, sx, sy, sz, connectivity, min_voxels, max_voxels); },
+      [&](const void *d_labels, void *d_out, int64_t *d_counts, void *d_ws, size_t ws_bytes) {
+        return edt_hip_dust_device(d_labels, dtype, ndim, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, d_out,
+                                   d_counts, d_ws, ws_bytes, nullptr);
+      });
 }
 
 }  // extern "C"

@@ -279,20 +279,9 @@ size_t components_workspace_bytes(int64_t voxels);  // the per-chunk root counts
 // shape, connectivity in 1..ndim, sx * sy * sz <= 2^31 - 1: what both entry points refuse before they look at a pointer
 int components_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity,
                           const char *who = "connected_components");
-// rows, merge, flatten, scan, number, final on `stream`; out: sx * sy * sz uint32 (not the labels), n: one int64, both on the device
+// the forest (launch_forest, edt_forest.h), then scan, number, final on `stream`; out: sx * sy * sz uint32 (not the labels), n: one int64, both on the device
 int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                       uint32_t *out, int64_t *n, void *ws, hipStream_t stream);
-// rows, merge, flatten alone over a volume of 0/1 bytes: P[i] = the smallest idx of i's component (0xFFFFFFFF for a zero byte);
-// ws: components_workspace_bytes.  The background forest of fill_holes (edt_fillholes.hip)
-int launch_components_forest(const uint8_t *mask, int64_t sx, int64_t sy, int64_t sz, int connectivity, uint32_t *P, void *ws,
-                             hipStream_t stream);
-// the same forest over labels of any dtype (binary as in launch_components): P[i] = the smallest idx of i's component for a
-// foreground voxel, kCcBg for background.  The forest of dust (edt_dust.hip); passes "dust rows / merge / flatten"
-int launch_labels_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
-                         uint32_t *P, void *ws, hipStream_t stream);
-// words of a parent plane: background, and the top bit that marks a root's word once it carries something else than itself
-constexpr uint32_t kCcBg = 0xFFFFFFFFu;
-constexpr uint32_t kCcTag = 0x80000000u;
 // ---- dust (components kept or removed by size; sizes in the roots' own words of the parent plane): edt_dust.hip ----------
 // what components_check_args refuses, then min_voxels < 0 and max_voxels < min_voxels
 int dust_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int64_t min_voxels,

@@ -566,32 +566,17 @@ int edt_hip_label_stats_device(const void *d_labels, int dtype, const float *d_d
                                int64_t *d_argmax, int32_t *d_bbox, int64_t *d_n_labels, void *d_workspace,
                                size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = ls_check_args(dtype, ndim, sx, sy, sz, max_labels);
-  if (rc != EDT_OK) return rc;
-  if (!d_n_labels) { set_error("label_stats: null device pointer"); return EDT_ERR_BAD_ARG; }
-  const int64_t voxels = sx * sy * sz;
-  if (voxels > 0) {
-    if (!d_labels || !d_dt || !d_keys || !d_counts || !d_max || !d_argmax || !d_bbox) {
-      set_error("label_stats: null device pointer");
-      return EDT_ERR_BAD_ARG;
-    }
-    if (!d_workspace || workspace_bytes < edt_hip_label_stats_workspace_bytes(dtype, voxels, max_labels)) {
-      set_error("label_stats: workspace missing or smaller than edt_hip_label_stats_workspace_bytes()");
-      return EDT_ERR_BAD_ARG;
-    }
-    if ((rc = check_workspace_alignment(d_workspace)) != EDT_OK) return rc;
-  }
-  if ((rc = require_device()) != EDT_OK) return rc;
-  if (voxels == 0) {
-    return launch_fill_words(d_n_labels, 0u, sizeof(int64_t) / sizeof(uint32_t), stream);
-  }
+  const int own = ls_check_args(dtype, ndim, sx, sy, sz, max_labels);
+  const int64_t voxels = own == EDT_OK ? sx * sy * sz : 0;
+  int rc;
+  if (!label_op_begin("label_stats", own, d_n_labels, 1, voxels,
+                      !d_labels || !d_dt || !d_keys || !d_counts || !d_max || !d_argmax || !d_bbox, false, d_workspace,
+                      workspace_bytes, edt_hip_label_stats_workspace_bytes(dtype, voxels, max_labels),
+                      "edt_hip_label_stats_workspace_bytes", stream, &rc))
+    return rc;
   const LsTable t = carve_ls(d_workspace, dtype, ls_cap(voxels, max_labels));
   const LsOut o = {d_keys, d_counts, d_max, d_argmax, d_bbox, d_n_labels, dtype_size(dtype),
                    dtype == EDT_F32 ? 1 : dtype == EDT_F64 ? 2 : 0};
-  if (g_log.enabled.load(std::memory_order_relaxed)) {
-    std::lock_guard<std::mutex> lock(g_log_mutex);
-    log_begin_call();
-  }
   switch (dtype) {
     case EDT_U8: return launch_ls_t<uint8_t, false>((const uint8_t *)d_labels, d_dt, voxels, sx, sy, t, o, stream);
     case EDT_BOOL: return launch_ls_t<uint8_t, true>((const uint8_t *)d_labels, d_dt, voxels, sx, sy, t, o, stream);

@@ -337,6 +337,23 @@ def _connectivity(connectivity, ndim, default=None, who="connected_components"):
                      + f", got {connectivity!r}")
 
 
+def _label_op_array(data, who):
+    """What every label operation asks of its input before anything else: an array of 1 to 3 dimensions and a label dtype."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"{who}: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    _label_code(data)
+    return data, data.ndim
+
+
+def _label_op_layout(data):
+    """... and once its own arguments and the empty case are through: ``(data, order, dtype code, label buffer, x-fastest
+    extents padded to three)``."""
+    nd = data.ndim
+    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+    return data, order, code, buf, tuple(int(v) for v in extents) + (1,) * (3 - nd)
+
+
 def connected_components(data, connectivity=None, binary=False, return_N=False):
     """Connected components of a 1-D to 3-D label array on the device (cc3d.connected_components /
     skimage.measure.label / scipy.ndimage.label; contract: include/edt_hip.h, "connected components").  Two neighbouring
@@ -352,17 +369,12 @@ def connected_components(data, connectivity=None, binary=False, return_N=False):
     array's MEMORY meets them: for a C-contiguous array and ``binary`` that is scipy's numbering, for an F-contiguous one
     (also one that is C-contiguous as well, e.g. with unit axes, as in every entry point of this module) cc3d's.  At most
     2^31 - 1 voxels."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"connected_components: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    nd = data.ndim
-    _label_code(data)
+    data, nd = _label_op_array(data, "connected_components")
     c = _connectivity(connectivity, nd)
     if data.size == 0:
         out = np.zeros(data.shape, dtype=np.uint32)
         return (out, 0) if return_N else out
-    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    data, order, code, buf, e = _label_op_layout(data)
     out = np.empty(data.shape, dtype=np.uint32, order=order)
     n = ctypes.c_int64(0)
     _lib.check(_lib.load().edt_hip_connected_components(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0,
@@ -384,17 +396,12 @@ def fill_holes(data, connectivity=None, binary=False, return_fill_count=False):
 
     Returns an array of ``data``'s dtype, shape and memory order; with ``return_fill_count=True`` the pair
     ``(out, n)``, ``n`` the number of voxels that were filled.  At most 2^31 - 1 voxels."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"fill_holes: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    nd = data.ndim
-    _label_code(data)
+    data, nd = _label_op_array(data, "fill_holes")
     c = _connectivity(connectivity, nd, default=1, who="fill_holes")
     if data.size == 0:
         out = data.copy()
         return (out, 0) if return_fill_count else out
-    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    data, order, code, buf, e = _label_op_layout(data)
     out = np.empty(data.shape, dtype=data.dtype, order=order)
     n = ctypes.c_int64(0)
     _lib.check(_lib.load().edt_hip_fill_holes(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, _ptr(out),
@@ -436,18 +443,13 @@ def dust(data, threshold, connectivity=None, binary=False, invert=False, return_
     Returns an array of ``data``'s dtype, shape and memory order: the voxels of kept components and the background bit for
     bit, the voxels of removed components zero.  With ``return_counts=True`` the pair
     ``(out, DustCounts(components, kept, removed_voxels))`` of Python ints.  At most 2^31 - 1 voxels."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"dust: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    nd = data.ndim
-    _label_code(data)
+    data, nd = _label_op_array(data, "dust")
     lo, hi = _dust_bounds(threshold)
     c = _connectivity(connectivity, nd, who="dust")
     if data.size == 0:
         out = data.copy()
         return (out, DustCounts(0, 0, 0)) if return_counts else out
-    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    data, order, code, buf, e = _label_op_layout(data)
     out = np.empty(data.shape, dtype=data.dtype, order=order)
     counts = np.zeros(3, dtype=np.int64)
     _lib.check(_lib.load().edt_hip_dust(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, lo, hi,

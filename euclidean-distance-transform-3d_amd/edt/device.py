@@ -455,9 +455,8 @@ def _label_stats_raw(labels, dt, nd, ext, cap):
     arg = torch.empty(cap, dtype=torch.int64, device=dev)
     bbox = torch.empty((cap, 6), dtype=torch.int32, device=dev)
     n = torch.empty(1, dtype=torch.int64, device=dev)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(lib.edt_hip_label_stats_device(vp(labels), code, vp(dt), nd, *ext, cap, vp(keys), vp(counts), vp(mx),
-                                              vp(arg), vp(bbox), vp(n), vp(ws), ws.numel(), _stream_ptr()))
+    _lib.check(lib.edt_hip_label_stats_device(_vp(labels), code, _vp(dt), nd, *ext, cap, _vp(keys), _vp(counts), _vp(mx),
+                                              _vp(arg), _vp(bbox), _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
     return int(n.item()), keys, counts, mx, arg, bbox
 
 
@@ -510,20 +509,34 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
 
 
 _cc_workspaces: dict = {}
+_fh_workspaces: dict = {}      # fill_holes and dust: the same bytes (edt_hip_dust_workspace_bytes), one cache
 
 
-def _components_workspace(ext, code, nd, device) -> torch.Tensor:
+def _label_op_workspace(cache, query, ext, code, nd, device, who) -> torch.Tensor:
     # one scratch buffer per shape and stream (a workspace is only ever used on the stream it was allocated for); at most 9 are
-    # kept, and the one cached longest ago makes room for a new one
+    # kept per cache, and the one cached longest ago makes room for a new one
     key = (tuple(ext), code, str(device), torch.cuda.current_stream(device).cuda_stream)
-    if key not in _cc_workspaces:
-        nbytes = _lib.load().edt_hip_components_workspace_bytes(code, nd, *ext)
+    if key not in cache:
+        nbytes = getattr(_lib.load(), query)(code, nd, *ext)
         if nbytes == 0:
-            raise ValueError(f"connected_components: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
-        if len(_cc_workspaces) > 8:
-            del _cc_workspaces[next(iter(_cc_workspaces))]
-        _cc_workspaces[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    return _cc_workspaces[key]
+            raise ValueError(f"{who}: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
+        if len(cache) > 8:
+            del cache[next(iter(cache))]
+        cache[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return cache[key]
+
+
+def _label_op_tensor(labels, who):
+    """What every label operation asks of its input: ``(labels, nd, dtype code, x-fastest extents padded to three)``."""
+    labels = as_device_tensor(labels)
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"{who}: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    nd = labels.dim()
+    return labels, nd, dtype_code(labels.dtype), tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
 
 
 def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
@@ -537,39 +550,18 @@ def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
     The result composes without leaving the device: ``label_stats(out, dt)`` is then a table per OBJECT,
     ``each(out, dt)`` yields one image per object, and ``edt(out)`` is the transform of the instances."""
     from . import _connectivity
-    labels = as_device_tensor(labels)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"connected_components: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
-    nd = labels.dim()
-    code = dtype_code(labels.dtype)
+    labels, nd, code, ext = _label_op_tensor(labels, "connected_components")
     c = _connectivity(connectivity, nd)
     out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
     if labels.numel() == 0:
         return out, torch.zeros((), dtype=torch.int64, device=labels.device)
     n = torch.empty((), dtype=torch.int64, device=labels.device)
     labels = labels.contiguous()
-    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-    ws = _components_workspace(ext, code, nd, labels.device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(_lib.load().edt_hip_connected_components_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, vp(out),
-                                                               vp(n), vp(ws), ws.numel(), _stream_ptr()))
+    ws = _label_op_workspace(_cc_workspaces, "edt_hip_components_workspace_bytes", ext, code, nd, labels.device,
+                             "connected_components")
+    _lib.check(_lib.load().edt_hip_connected_components_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, _vp(out),
+                                                               _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
-
-
-_fh_workspaces: dict = {}
-
-
-def _fill_holes_workspace(ext, code, nd, device, who="fill_holes") -> torch.Tensor:
-    # as _components_workspace: one scratch buffer per shape and stream, at most 9 kept (dust needs the same bytes and shares them)
-    key = (tuple(ext), code, str(device), torch.cuda.current_stream(device).cuda_stream)
-    if key not in _fh_workspaces:
-        nbytes = _lib.load().edt_hip_fill_holes_workspace_bytes(code, nd, *ext)
-        if nbytes == 0:
-            raise ValueError(f"{who}: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
-        if len(_fh_workspaces) > 8:
-            del _fh_workspaces[next(iter(_fh_workspaces))]
-        _fh_workspaces[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    return _fh_workspaces[key]
 
 
 def fill_holes(labels: torch.Tensor, connectivity=None, binary=False):
@@ -581,22 +573,16 @@ def fill_holes(labels: torch.Tensor, connectivity=None, binary=False):
 
     ``edt(fill_holes(x)[0])`` is then the transform of the filled segmentation without a trip to the host."""
     from . import _connectivity
-    labels = as_device_tensor(labels)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"fill_holes: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
-    nd = labels.dim()
-    code = dtype_code(labels.dtype)
+    labels, nd, code, ext = _label_op_tensor(labels, "fill_holes")
     c = _connectivity(connectivity, nd, default=1, who="fill_holes")
     if labels.numel() == 0:
         return labels.clone(), torch.zeros((), dtype=torch.int64, device=labels.device)
     labels = labels.contiguous()
     out = torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
     n = torch.empty((), dtype=torch.int64, device=labels.device)
-    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-    ws = _fill_holes_workspace(ext, code, nd, labels.device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(_lib.load().edt_hip_fill_holes_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, vp(out), vp(n),
-                                                     vp(ws), ws.numel(), _stream_ptr()))
+    ws = _label_op_workspace(_fh_workspaces, "edt_hip_fill_holes_workspace_bytes", ext, code, nd, labels.device, "fill_holes")
+    _lib.check(_lib.load().edt_hip_fill_holes_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, _vp(out), _vp(n),
+                                                     _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
 
 
@@ -611,11 +597,7 @@ def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, inver
 
     ``edt(fill_holes(dust(x, t)[0])[0])`` is then the transform of the cleaned segmentation without a trip to the host."""
     from . import _connectivity, _dust_bounds
-    labels = as_device_tensor(labels)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"dust: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
-    nd = labels.dim()
-    code = dtype_code(labels.dtype)
+    labels, nd, code, ext = _label_op_tensor(labels, "dust")
     lo, hi = _dust_bounds(threshold)
     c = _connectivity(connectivity, nd, who="dust")
     if in_place and not labels.is_contiguous():
@@ -625,11 +607,9 @@ def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, inver
     labels = labels.contiguous()
     out = labels if in_place else torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
     counts = torch.empty(3, dtype=torch.int64, device=labels.device)
-    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-    ws = _fill_holes_workspace(ext, code, nd, labels.device, who="dust")   # (the same bytes: edt_hip_dust_workspace_bytes)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(_lib.load().edt_hip_dust_device(vp(labels), code, nd, *ext, c, 1 if binary else 0, lo, hi, 1 if invert else 0,
-                                               vp(out), vp(counts), vp(ws), ws.numel(), _stream_ptr()))
+    ws = _label_op_workspace(_fh_workspaces, "edt_hip_fill_holes_workspace_bytes", ext, code, nd, labels.device, "dust")
+    _lib.check(_lib.load().edt_hip_dust_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, lo, hi, 1 if invert else 0,
+                                               _vp(out), _vp(counts), _vp(ws), ws.numel(), _stream_ptr()))
     return out, counts
 
 

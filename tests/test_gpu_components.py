@@ -306,6 +306,14 @@ def test_entry_points_agree(edt_gpu):
             assert int(rn) == wn and torch.equal(raw, out)
             _raw_device_call(lib, t, c, int(binary), raw, rn, ws)
             assert int(rn) == wn and torch.equal(raw, out)
+    device.set_profiling(True)
+    try:
+        device.connected_components(t, connectivity=2)
+        torch.cuda.synchronize()
+        names = [name for name, _ in device.pass_times()]
+    finally:
+        device.set_profiling(False)
+    assert names == ["components rows", "components merge", "components flatten", "components number", "components final"]
 
 
 def test_device_form_is_graph_capturable(edt_gpu):
