@@ -17,7 +17,7 @@ namespace edt_amd {
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
 // what a pooled buffer is for -- one slot each, so two roles never share memory within a call
-enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count */, kSecondField, kSlotCount };
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count, morphology's mask */, kSecondField, kSlotCount };
 struct DevicePool {
   static constexpr int kSlots = kSlotCount;
   void *p[kSlots] = {};
@@ -430,6 +430,84 @@ static int label_op_host(const LabelOp &op, const void *labels, int dtype, int n
   return st.down(result, kAux, rbytes);
 }
 
+// erode / dilate / opening / closing on host buffers (kernels: edt_morph.hip; contract: include/edt_hip.h, "morphology"): labels
+// up once, the transforms (run_device), the mask and select kernels and expand_labels on the device, the output down once.  The
+// composition owns its buffers: the fp32 field in kSecondField, the uint8 mask in kAux, one workspace that serves every step.
+static int morphology_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                           float wz, int op, double radius, int flags, void *output) {
+  const bool measures = op == EDT_MORPH_ERODE || op == EDT_MORPH_OPEN;  // the ops that take flags: their first step is a transform of the labels
+  double r2 = 0.0;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !output, &empty, [&](After what) -> int {
+    if (what == After::shape) {
+      if (op < EDT_MORPH_ERODE || op > EDT_MORPH_CLOSE) { set_error("morphology: op must be one of EDT_MORPH_*"); return EDT_ERR_BAD_ARG; }
+      if (flags & ~(measures ? (EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY) : 0)) {
+        set_error(measures ? "morphology: erode / opening take EDT_FLAG_BLACK_BORDER and EDT_FLAG_MORPH_BINARY only"
+                           : "morphology: dilate / closing take no flags");
+        return EDT_ERR_UNSUPPORTED;
+      }
+      return morph_radius_squared(radius, op == EDT_MORPH_DILATE, "morphology", &r2);
+    }
+    if (what == After::pointers) {
+      const size_t bytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
+      const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(output);
+      if (a < b + bytes && b < a + bytes) { set_error("morphology: the output may not overlap the labels"); return EDT_ERR_BAD_ARG; }
+    }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const int64_t voxels = sx * sy * sz;
+  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
+  const int generic = env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0;
+  const int bb = flags & EDT_FLAG_BLACK_BORDER;
+  const bool binary = (flags & EDT_FLAG_MORPH_BINARY) || dtype == EDT_BOOL;
+  size_t wbytes = edt_hip_workspace_bytes_flags(EDT_U8, ndim, sx, sy, sz, generic);
+  if (measures && !binary) wbytes = std::max(wbytes, edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, generic));
+  if (!measures) wbytes = std::max(wbytes, edt_hip_expand_labels_workspace_bytes(dtype, ndim, sx, sy, sz));
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}})) != EDT_OK) return rc;
+  if (op != EDT_MORPH_DILATE && (rc = st.alloc({{kAux, (size_t)voxels}, {kSecondField, fbytes}})) != EDT_OK) return rc;
+  void *const d_labels = st.p[kLabels], *const d_out = st.p[kOut], *const d_ws = st.p[kWorkspace];
+  float *const field = st.at<float>(kSecondField);
+  uint8_t *const mask = st.at<uint8_t>(kAux);
+  const auto transform = [&](const void *of, int of_dtype, int border) {
+    return run_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, border | generic, field, d_ws, wbytes, nullptr);
+  };
+  st.expect(output, lbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  if (measures) {
+    // S: the transform of the labels, or of the mask labels != 0
+    if (binary) {
+      if ((rc = launch_is_foreground(dtype, d_labels, mask, voxels, nullptr)) != EDT_OK) return rc;
+      rc = transform(mask, EDT_U8, bb);
+    } else {
+      rc = transform(d_labels, dtype, bb);
+    }
+    if (rc != EDT_OK) return rc;
+    if (op == EDT_MORPH_ERODE) {
+      rc = launch_morph_select(dtype, d_labels, nullptr, field, r2, EDT_MORPH_FARTHER, d_out, nullptr, voxels, nullptr);
+    } else {
+      // z = not eroded, B = its transform without a border, out = the labels within r of the eroded set
+      if ((rc = launch_morph_select(dtype, nullptr, nullptr, field, r2, EDT_MORPH_FARTHER, nullptr, mask, voxels, nullptr)) != EDT_OK ||
+          (rc = transform(mask, EDT_U8, 0)) != EDT_OK)
+        return rc;
+      rc = launch_morph_select(dtype, d_labels, nullptr, field, r2, EDT_MORPH_WITHIN, d_out, nullptr, voxels, nullptr);
+    }
+  } else {
+    rc = edt_hip_expand_labels_device(d_labels, dtype, ndim, sx, sy, sz, wx, wy, wz, radius, d_out, d_ws, wbytes, nullptr);
+    if (rc == EDT_OK && op == EDT_MORPH_CLOSE) {
+      // the dilation eroded again: D kept where the labels were, or farther than r from what the dilation left empty
+      if ((rc = launch_is_foreground(dtype, d_out, mask, voxels, nullptr)) != EDT_OK || (rc = transform(mask, EDT_U8, 0)) != EDT_OK)
+        return rc;
+      rc = launch_morph_select(dtype, d_out, d_labels, field, r2, EDT_MORPH_FARTHER, d_out, nullptr, voxels, nullptr);
+    }
+  }
+  return rc != EDT_OK ? rc : st.down(output, kOut, lbytes);
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -611,6 +689,11 @@ int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy
         return edt_hip_dust_device(d_labels, dtype, ndim, sx, sy, sz, connectivity, binary, min_voxels, max_voxels, invert, d_out,
                                    d_counts, d_ws, ws_bytes, nullptr);
       });
+}
+
+int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                       int op, double radius, int flags, void *output) {
+  return morphology_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, op, radius, flags, output);
 }
 
 }  // extern "C"

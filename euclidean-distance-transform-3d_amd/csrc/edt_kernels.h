@@ -83,6 +83,15 @@ int launch_is_background(int dtype, const void *labels, uint8_t *mask, int64_t c
 int launch_negate_background(int dtype, const void *labels, float *f, int64_t count, hipStream_t stream);  // f = labels == 0 ? -f : f
 int launch_select_label(int dtype, const void *labels, const float *dt, float *out, const void *key,
                         int64_t count, hipStream_t stream);
+// ---- the streaming kernels of the morphology operations: edt_morph.hip ------------------------------
+// mask[i] = labels[i] != 0 (the type's own comparison: -0.0 is zero, a NaN is not)
+int launch_is_foreground(int dtype, const void *labels, uint8_t *mask, int64_t count, hipStream_t stream);
+// pass(i) = field[i] > r2 (EDT_MORPH_FARTHER) or <= r2 (EDT_MORPH_WITHIN), in fp64, or guard[i] != 0 where a guard is given;
+// out[i] = pass ? values[i] : zero bits (out == values allowed), mask[i] = pass ? 0 : 1 -- either may be null, not both
+int launch_morph_select(int dtype, const void *values, const void *guard, const float *field, double r2, int rule, void *out,
+                        uint8_t *mask, int64_t count, hipStream_t stream);
+// *r2 = radius * radius in fp64; EDT_ERR_BAD_ARG, named "<who>: ...", unless radius >= 0 and *r2 is finite (inf_allowed: or radius is +inf)
+int morph_radius_squared(double radius, bool inf_allowed, const char *who, double *r2);
 
 }  // namespace edt_amd
 

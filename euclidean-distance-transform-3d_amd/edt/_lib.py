@@ -24,6 +24,11 @@ FLAG_BATCH_2D = 8
 FLAG_SMALL_WORKSPACE = 16
 FLAG_BINARY_YZ = 32
 FLAG_SIGNED = 64
+FLAG_MORPH_BINARY = 128
+
+# edt_hip_morphology's op and edt_hip_morph_select_device's rule
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = range(4)
+MORPH_FARTHER, MORPH_WITHIN = range(2)
 
 OK = 0
 ERR_NO_DEVICE = -1
@@ -110,6 +115,9 @@ SIGNATURES = {
     "edt_hip_dust_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
     "edt_hip_dust_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_dust": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp]),
+    "edt_hip_is_foreground_device": (_i, [_vp, _i, _vp, _i64, _vp]),
+    "edt_hip_morph_select_device": (_i, [_vp, _vp, _i, _vp, _d, _i, _vp, _vp, _i64, _vp]),
+    "edt_hip_morphology": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _i, _vp]),
 }
 
 _lib = None

@@ -613,6 +613,101 @@ def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, inver
     return out, counts
 
 
+_morph_buffers: dict = {}
+
+
+def _morph_scratch(labels) -> tuple:
+    """The fp32 field and the uint8 mask of a morphology call: one pair per shape and stream, as the plans' scratch (at most
+    9 pairs are kept; the one cached longest ago makes room for a new one)."""
+    key = (tuple(labels.shape), str(labels.device), torch.cuda.current_stream(labels.device).cuda_stream)
+    if key not in _morph_buffers:
+        if len(_morph_buffers) > 8:
+            del _morph_buffers[next(iter(_morph_buffers))]
+        _morph_buffers[key] = (torch.empty(labels.shape, dtype=torch.float32, device=labels.device),
+                               torch.empty(labels.shape, dtype=torch.uint8, device=labels.device))
+    return _morph_buffers[key]
+
+
+def _is_foreground(labels, mask):
+    _lib.check(_lib.load().edt_hip_is_foreground_device(_vp(labels), dtype_code(labels.dtype), _vp(mask), labels.numel(),
+                                                        _stream_ptr()))
+    return mask
+
+
+def _morph_select(code, values, field, radius, rule, out=None, mask=None, guard=None):
+    """edt_hip_morph_select_device over ``field.numel()`` voxels; ``code``: the dtype code of values / guard / out"""
+    _lib.check(_lib.load().edt_hip_morph_select_device(
+        None if values is None else _vp(values), None if guard is None else _vp(guard), code, _vp(field), radius, rule,
+        None if out is None else _vp(out), None if mask is None else _vp(mask), field.numel(), _stream_ptr()))
+
+
+def _eroded_field(labels, nd, ext, w, black_border, binary, field, mask):
+    """S of the contract: the squared transform of the labels, or of the mask labels != 0 (bool: always)"""
+    if binary or labels.dtype == torch.bool:
+        return _plan_for(ext[:nd], _lib.U8, labels.device).run(_is_foreground(labels, mask), w[:nd], black_border, out=field)
+    return _plan_for(ext[:nd], dtype_code(labels.dtype), labels.device).run(labels, w[:nd], black_border, out=field)
+
+
+def _morph_input(labels, radius, anisotropy, who, in_place=False, inf_allowed=False):
+    from . import _morph_radius
+    raw = as_device_tensor(labels)
+    r = _morph_radius(radius, who, inf_allowed)
+    if in_place and not raw.is_contiguous():
+        raise ValueError(f"{who}: in_place needs a contiguous tensor")
+    labels, nd, ext, w = _ft_tensor(raw, anisotropy, who)
+    dtype_code(labels.dtype)
+    return labels, nd, ext, w, r
+
+
+def erode(labels: torch.Tensor, radius=1.0, anisotropy=None, black_border=False, binary=False, in_place=False) -> torch.Tensor:
+    """:func:`edt.erode` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
+    include/edt_hip.h, "morphology"): one transform and one streaming select on the current stream, nothing read back.
+    ``in_place=True`` writes the result into the (contiguous) input tensor and returns it."""
+    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "erode", in_place)
+    if labels.numel() == 0:
+        return labels if in_place else labels.clone()
+    field, mask = _morph_scratch(labels)
+    _eroded_field(labels, nd, ext, w, black_border, binary, field, mask)
+    out = labels if in_place else torch.empty_like(labels)
+    _morph_select(dtype_code(labels.dtype), labels, field, r, _lib.MORPH_FARTHER, out=out)
+    return out
+
+
+def dilate(labels: torch.Tensor, radius=1.0, anisotropy=None) -> torch.Tensor:
+    """:func:`edt.dilate` on a device array: exactly :func:`expand_labels`."""
+    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "dilate", inf_allowed=True)
+    return expand_labels(labels, r, anisotropy)
+
+
+def opening(labels: torch.Tensor, radius=1.0, anisotropy=None, black_border=False, binary=False, in_place=False) -> torch.Tensor:
+    """:func:`edt.opening` on a device array: the transform of the labels, the mask of what the erosion removes, its
+    binary transform, and the select of the voxels within ``radius`` of what survived -- two transforms and two streaming
+    kernels on the current stream.  ``in_place=True`` writes the result into the (contiguous) input tensor and returns it."""
+    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "opening", in_place)
+    if labels.numel() == 0:
+        return labels if in_place else labels.clone()
+    field, mask = _morph_scratch(labels)
+    _eroded_field(labels, nd, ext, w, black_border, binary, field, mask)
+    _morph_select(_lib.U8, None, field, r, _lib.MORPH_FARTHER, mask=mask)
+    _plan_for(ext[:nd], _lib.U8, labels.device).run(mask, w[:nd], False, out=field)
+    out = labels if in_place else torch.empty_like(labels)
+    _morph_select(dtype_code(labels.dtype), labels, field, r, _lib.MORPH_WITHIN, out=out)
+    return out
+
+
+def closing(labels: torch.Tensor, radius=1.0, anisotropy=None) -> torch.Tensor:
+    """:func:`edt.closing` on a device array: :func:`expand_labels`, the binary transform of what it left empty, and the
+    select that keeps the input's voxels and the new voxels farther than ``radius`` from the emptiness."""
+    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "closing")
+    if labels.numel() == 0:
+        return labels.clone()
+    out = expand_labels(labels, r, anisotropy)
+    field, mask = _morph_scratch(labels)
+    _plan_for(ext[:nd], _lib.U8, labels.device).run(_is_foreground(out, mask), w[:nd], False, out=field)
+    _morph_select(dtype_code(labels.dtype), out, field, r, _lib.MORPH_FARTHER, out=out, guard=labels)
+    return out
+
+
 def pass_times():
     """Durations (ms) of the kernels of the last profiled call, as ``[(name, ms), ...]``."""
     lib = _lib.load()

@@ -581,6 +581,55 @@ int edt_hip_dust_device(const void *d_labels, int dtype, int ndim, int64_t sx, i
 int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                  int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts);
 
+/* ---- morphology: spherical erode / dilate / opening / closing of a label volume, through the distance transform ----------
+ * Conventions as elsewhere in this header: x fastest, idx = x + sx * (y + sy * z); label 0 is background, compared with the
+ * type's == (so -0.0 is background and a NaN is foreground); voxel sizes as for edt_hip_edtsq_device.  The structuring element is
+ * the ball of physical radius `radius`: R2 = radius * radius, evaluated in fp64.  radius must be >= 0 with R2 finite -- NaN,
+ * negative or overflowing values are EDT_ERR_BAD_ARG; only dilate accepts +inf, as expand_labels does.
+ * The fields named below are exactly what edt_hip_edtsq_device writes (fp32, bit-identical to the reference); every comparison
+ * is (double)field[p] > R2 or <= R2.  "Zero" means all-zero bits, "kept" means bit for bit.
+ *
+ * erode(labels, r, black_border, binary):  S = edtsq(labels, w, black_border) -- with binary, S = edtsq(m, w, black_border) for
+ *   the uint8 mask m[p] = (labels[p] != 0).  out[p] = labels[p] if S[p] > R2, else zero (a -0.0 background voxel comes out
+ *   +0.0).  r = 0 returns the labels otherwise unchanged.  EDT_BOOL is always the binary form.
+ * dilate(labels, r):  exactly expand_labels(labels, r).
+ * opening(labels, r, black_border, binary):  z[p] = 1 unless S[p] > R2, S as in erode, z uint8; B = edtsq(z, w, black border
+ *   off); out[p] = labels[p] if B[p] <= R2, else zero.  If nothing survives the erosion B is +inf everywhere and out is zero.
+ *   One binary transform serves every label at once: S[p] > R2 puts every voxel of another label farther than r from p, so
+ *   no eroded voxel of another label lies within r of a voxel of label l, and the voxels within r of the eroded set, under
+ *   their own labels, are the union over the labels of each label's opening.
+ * closing(labels, r):  D = expand_labels(labels, r); m[p] = (D[p] != 0) as uint8; C = edtsq(m, w, black border off);
+ *   out[p] = D[p] if labels[p] != 0 or C[p] > R2, else zero.  New voxels take the label expand_labels gives them, with its tie
+ *   rule.  The labels[p] != 0 term makes closing extensive by construction, also for voxel sizes without a quantum, where
+ *   expand_labels measures in fp64 and C is fp32.  Outside the volume counts as foreground for the erosion (border off). */
+enum { EDT_MORPH_ERODE = 0, EDT_MORPH_DILATE = 1, EDT_MORPH_OPEN = 2, EDT_MORPH_CLOSE = 3 };
+enum { EDT_MORPH_FARTHER = 0, EDT_MORPH_WITHIN = 1 };
+#define EDT_FLAG_MORPH_BINARY 128   /* erode / opening: measure the mask labels != 0 */
+
+/* The two streaming helpers the operations are composed from, on device-resident data.  Enqueue-only on `stream`: no
+ * allocation, no synchronisation, no scratch.  Pointers as in "Alignment" above: any element offset is served; the vector
+ * forms (four voxels per thread: 16 bytes of the field) are used where every pointer of the call has the alignment of four of
+ * its elements, 16 bytes at the most; element by element otherwise, with the same bits.  Offsets are 64-bit (count may pass 2^32).  All seven label dtypes; 8-byte and float labels move as bit patterns. */
+/* mask[i] = (labels[i] != 0) as one byte per voxel */
+int edt_hip_is_foreground_device(const void *d_labels, int dtype, uint8_t *d_mask, int64_t count, void *stream);
+/* pass(i) = rule == EDT_MORPH_FARTHER ? (double)field[i] > R2 : (double)field[i] <= R2   (EDT_MORPH_WITHIN);
+ * d_guard != NULL: pass(i) |= guard[i] != 0   (guard has the dtype of values)
+ * d_out   != NULL: out[i]  = pass ? values[i] : zero bits   (d_out == d_values allowed; d_values required)
+ * d_mask  != NULL: mask[i] = pass ? 0 : 1
+ * At least one of d_out / d_mask; a bad rule, a bad radius (+inf included), a bad dtype, count < 0 and missing pointers are
+ * EDT_ERR_BAD_ARG before any device work. */
+int edt_hip_morph_select_device(const void *d_values, const void *d_guard, int dtype, const float *d_field, double radius,
+                                int rule, void *d_out, uint8_t *d_mask, int64_t count, void *stream);
+
+/* The four operations on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, output down once, everything between on the device.
+ * op: EDT_MORPH_*.  ndim in {1,2,3}, unused extents 1.  `output` has the labels' dtype and may not overlap `labels`.
+ * flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY for erode / opening; 0 for dilate / closing.  Refused before any device
+ * work: a bad op, a bad radius (EDT_ERR_BAD_ARG); a flag the op does not take (EDT_ERR_UNSUPPORTED); bad voxel sizes; NULL
+ * pointers and overlapping buffers (EDT_ERR_BAD_ARG).  An empty volume is EDT_OK with nothing touched. */
+int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                       int op, double radius, int flags, void *output);
+
 #ifdef __cplusplus
 }
 #endif
