@@ -17,7 +17,7 @@ namespace edt_amd {
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
 // what a pooled buffer is for -- one slot each, so two roles never share memory within a call
-enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count, morphology's mask */, kSecondField, kSlotCount };
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count, morphology's mask, local thickness' mask and counters */, kSecondField, kThirdField /* local thickness: S, B and T are alive together */, kSlotCount };
 struct DevicePool {
   static constexpr int kSlots = kSlotCount;
   void *p[kSlots] = {};
@@ -508,6 +508,121 @@ static int morphology_host(const void *labels, int dtype, int ndim, int64_t sx, 
   return rc != EDT_OK ? rc : st.down(output, kOut, lbytes);
 }
 
+// local thickness on host buffers (kernel: k_thickness_step, edt_morph.hip; contract: include/edt_hip.h, "local thickness"):
+// labels up once, S by one transform, then per radius the binary transform of the mask the step before left and one step; T and
+// the sizes down once.  The buffers: S in kSecondField, B in kThirdField, T in kOut, the byte mask in kAux with the counters
+// (k sizes, then Smax's bits) behind it, one workspace that serves every transform.
+static int thickness_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                          int flags, const double *radii, int64_t n_radii, double step, float *thickness, int64_t *sizes,
+                          int64_t *n_used) {
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !thickness || !n_used || (n_radii > 0 && !sizes), &empty, [&](After what) -> int {
+    if (what == After::shape) {
+      if (flags & ~(EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY)) {
+        set_error("local_thickness takes EDT_FLAG_BLACK_BORDER and EDT_FLAG_MORPH_BINARY only");
+        return EDT_ERR_UNSUPPORTED;
+      }
+      double r2;
+      if (!radii) {
+        if (n_radii < 0) { set_error("local_thickness: n_radii < 0"); return EDT_ERR_BAD_ARG; }
+        return thickness_radius_squared(step, "local_thickness (the ladder's step)", &r2);
+      }
+      if (n_radii < 1) { set_error("local_thickness: an explicit list needs n_radii >= 1"); return EDT_ERR_BAD_ARG; }
+      for (int64_t j = 0; j < n_radii; ++j) {
+        if (const int bad = thickness_radius_squared(radii[j], "local_thickness", &r2)) return bad;
+        if (j > 0 && !(radii[j] > radii[j - 1])) { set_error("local_thickness: radii must be strictly ascending"); return EDT_ERR_BAD_ARG; }
+      }
+    }
+    if (what == After::pointers) {
+      const size_t voxels = (size_t)(sx * sy * sz);
+      const auto overlap = [](const void *p, size_t pb, const void *q, size_t qb) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return pb > 0 && qb > 0 && a < b + qb && b < a + pb;
+      };
+      const size_t lbytes = voxels * dtype_size(dtype), tbytes = voxels * sizeof(float), sbytes = (size_t)n_radii * sizeof(int64_t);
+      if (overlap(labels, lbytes, thickness, tbytes) || overlap(labels, lbytes, sizes, sbytes) || overlap(thickness, tbytes, sizes, sbytes)) {
+        set_error("local_thickness: thickness, sizes and the labels may not overlap");
+        return EDT_ERR_BAD_ARG;
+      }
+    }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const int64_t voxels = sx * sy * sz;
+  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
+  const int generic = env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0;
+  const int bb = flags & EDT_FLAG_BLACK_BORDER;
+  const bool binary = (flags & EDT_FLAG_MORPH_BINARY) || dtype == EDT_BOOL;
+  size_t wbytes = edt_hip_workspace_bytes_flags(EDT_U8, ndim, sx, sy, sz, generic);
+  if (!binary) wbytes = std::max(wbytes, edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, generic));
+  const size_t counters = align_up((size_t)voxels, 256);           // k int64 sizes, then the bits of Smax
+  const size_t cbytes = (size_t)n_radii * sizeof(int64_t) + sizeof(int64_t);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, fbytes}, {kWorkspace, wbytes}, {kAux, counters + cbytes}, {kSecondField, fbytes},
+                      {kThirdField, fbytes}})) != EDT_OK)
+    return rc;
+  void *const d_labels = st.p[kLabels], *const d_ws = st.p[kWorkspace];
+  float *const S = st.at<float>(kSecondField), *const B = st.at<float>(kThirdField), *const T = st.at<float>(kOut);
+  uint8_t *const mask = st.at<uint8_t>(kAux);
+  int64_t *const d_sizes = reinterpret_cast<int64_t *>(mask + counters);
+  uint32_t *const d_smax = reinterpret_cast<uint32_t *>(d_sizes + n_radii);
+  const auto transform = [&](const void *of, int of_dtype, int border, float *field) {
+    return run_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, border | generic, field, d_ws, wbytes, nullptr);
+  };
+  st.expect(thickness, fbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  if (binary) {
+    if ((rc = launch_is_foreground(dtype, d_labels, mask, voxels, nullptr)) != EDT_OK) return rc;
+    rc = transform(mask, EDT_U8, bb, S);
+  } else {
+    rc = transform(d_labels, dtype, bb, S);
+  }
+  if (rc != EDT_OK || (rc = launch_fill_words(d_sizes, 0u, cbytes / sizeof(uint32_t), nullptr)) != EDT_OK) return rc;
+  // step 0: T = 0 and the mask of the first radius (the default ladder's first radius is its step, whatever Smax turns out to be)
+  std::vector<double> ladder;
+  const double first = radii ? radii[0] : step;
+  double r2 = 0.0, next2 = first * first;
+  if ((rc = launch_thickness_step(S, nullptr, 0.0, 0.0f, next2, T, mask, nullptr, radii ? nullptr : d_smax, voxels, nullptr)) != EDT_OK) return rc;
+  int64_t k = n_radii;
+  if (!radii) {
+    uint32_t bits = 0;
+    EDT_HIP_TRY(hipMemcpy(&bits, d_smax, sizeof(bits), hipMemcpyDeviceToHost));
+    float smax_f;
+    std::memcpy(&smax_f, &bits, sizeof(smax_f));
+    const double smax = (double)smax_f;
+    // the j >= 1 with (j * step)^2 < Smax are a prefix (rounding is monotone): estimate its length, then settle it on the very test
+    const auto below = [&](int64_t j) { const double r = (double)j * step; return r * r < smax; };
+    const double q = std::sqrt(smax) / step;
+    k = q >= 9.0e15 ? INT64_MAX : (int64_t)q;
+    if (k < INT64_MAX) {
+      while (below(k + 1)) ++k;
+      while (k > 0 && !below(k)) --k;
+    }
+    if (k > n_radii) {
+      *n_used = k;
+      set_error("local_thickness: the default ladder has " + std::to_string(k) + " radii, sizes has room for " + std::to_string(n_radii));
+      return EDT_ERR_BAD_ARG;
+    }
+    for (int64_t j = 1; j <= k; ++j) ladder.push_back((double)j * step);
+    radii = ladder.data();
+  }
+  for (int64_t j = 0; j < k; ++j) {
+    r2 = next2;
+    const bool more = j + 1 < k;
+    if (more) next2 = radii[j + 1] * radii[j + 1];
+    if ((rc = transform(mask, EDT_U8, 0, B)) != EDT_OK ||
+        (rc = launch_thickness_step(S, B, r2, (float)radii[j], next2, T, more ? mask : nullptr, d_sizes + j, nullptr, voxels, nullptr)) != EDT_OK)
+      return rc;
+  }
+  if ((rc = st.down(thickness, kOut, fbytes)) != EDT_OK) return rc;
+  if (k > 0 && (rc = st.down(sizes, kAux, (size_t)k * sizeof(int64_t), counters)) != EDT_OK) return rc;
+  *n_used = k;
+  return EDT_OK;
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -694,6 +809,12 @@ int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy
 int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                        int op, double radius, int flags, void *output) {
   return morphology_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, op, radius, flags, output);
+}
+
+int edt_hip_local_thickness(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                            int flags, const double *radii, int64_t n_radii, double step, float *thickness, int64_t *sizes,
+                            int64_t *n_used) {
+  return thickness_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, radii, n_radii, step, thickness, sizes, n_used);
 }
 
 }  // extern "C"

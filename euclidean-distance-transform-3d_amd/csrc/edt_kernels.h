@@ -92,6 +92,13 @@ int launch_morph_select(int dtype, const void *values, const void *guard, const 
                         uint8_t *mask, int64_t count, hipStream_t stream);
 // *r2 = radius * radius in fp64; EDT_ERR_BAD_ARG, named "<who>: ...", unless radius >= 0 and *r2 is finite (inf_allowed: or radius is +inf)
 int morph_radius_squared(double radius, bool inf_allowed, const char *who, double *r2);
+// one step of local thickness (include/edt_hip.h, "local thickness").  B != nullptr: T[i] = rf where S[i] > 0 && B[i] <= r2 (in
+// fp64), *size += their number; B == nullptr: T[i] = 0, *smax_bits = max(*smax_bits, bits of the largest finite S[i]);
+// mask != nullptr: mask[i] = S[i] > next2 ? 0 : 1.  size, smax_bits and mask may be null.
+int launch_thickness_step(const float *S, const float *B, double r2, float rf, double next2, float *T, uint8_t *mask, int64_t *size,
+                          uint32_t *smax_bits, int64_t count, hipStream_t stream);
+// *r2 = radius * radius; EDT_ERR_BAD_ARG, named "<who>: ...", unless radius is finite and > 0 and *r2 is finite
+int thickness_radius_squared(double radius, const char *who, double *r2);
 
 }  // namespace edt_amd
 

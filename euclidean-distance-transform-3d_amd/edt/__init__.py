@@ -37,7 +37,7 @@ __all__ = [
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
     "label_stats", "connected_components", "fill_holes", "dust", "DustCounts",
-    "erode", "dilate", "opening", "closing",
+    "erode", "dilate", "opening", "closing", "local_thickness", "ThicknessSizes",
 ]
 
 
@@ -516,6 +516,69 @@ def closing(data, radius=1.0, anisotropy=None, parallel=1):
     them; every voxel of ``data`` keeps its label.  For a mask, scipy's ``binary_erosion(binary_dilation(m, ball), ball,
     border_value=1)``."""
     return _morphology("closing", _lib.MORPH_CLOSE, data, radius, anisotropy, 0)
+
+
+ThicknessSizes = collections.namedtuple("ThicknessSizes", ["radii", "voxels"])
+
+
+def _thickness_radii(radii, who="local_thickness"):
+    """The radii of a local_thickness call as a float64 array: at least one, each > 0 with a finite square (``_morph_radius``),
+    strictly ascending; anything else is a ValueError."""
+    try:
+        r = np.array([_morph_radius(v, who) for v in np.asarray(radii, dtype=np.float64).reshape(-1)], dtype=np.float64)
+    except TypeError:
+        raise ValueError(f"{who}: radii must be numbers, got {radii!r}") from None
+    if r.size < 1 or not (r > 0.0).all() or not (np.diff(r) > 0.0).all():
+        raise ValueError(f"{who}: radii must be at least one, > 0 and strictly ascending, got {radii!r}")
+    return r
+
+
+def _ladder_room(extents, w):
+    """``(step, room)`` of the default ladder r_j = j * step: step is the smallest |voxel size|, and no ladder is longer than
+    ``room``, because S <= sum_i (w_i (n_i + 1))^2 and the ladder ends where r_j^2 reaches the largest finite S."""
+    step = min(abs(float(v)) for v in w)
+    bound = sum((abs(float(v)) * (int(n) + 1)) ** 2 for v, n in zip(w, extents))
+    return step, int(np.sqrt(bound) / step) + 2
+
+
+def local_thickness(data, radii=None, anisotropy=None, black_border=False, binary=False, return_sizes=False, parallel=1):
+    """Local thickness of every label of a 1-D to 3-D label array at once (porespy's ``local_thickness``, ImageJ's "Local
+    Thickness", quantised to a ladder of radii; contract: include/edt_hip.h, "local thickness"): for every voxel the largest
+    radius ``r`` of ``radii`` whose :func:`opening` -- same ``anisotropy``, ``black_border`` and ``binary`` -- still contains
+    it, as float32; 0 for background and for voxels that lie in no opening.  "Largest" is meant literally: the openings by
+    digital balls are not nested, and a voxel may lie in a larger one and not in the next smaller.
+
+    ``radii``: strictly ascending, each > 0 with a finite square (a ValueError otherwise).  ``None`` is the ladder
+    ``step, 2 step, 3 step, ...`` with ``step`` the smallest voxel size, as far as ``r**2`` stays below the largest finite value
+    of ``edtsq(data, anisotropy, black_border)``: larger balls fit nowhere.  One label everywhere without a border has no
+    finite distance: the default ladder is then empty and the result zero, while explicit radii give ``radii[-1]`` everywhere.
+
+    Returns float32 of ``data``'s shape and memory order; with ``return_sizes=True`` the pair ``(thickness,
+    ThicknessSizes(radii, voxels))``: the radii actually used (float64) and the voxel count of each radius' opening (int64),
+    the granulometry curve.  One trip over PCIe each way; per radius one binary transform and one streaming kernel."""
+    data, an = _ft_args(data, anisotropy, "local_thickness")
+    _label_code(data)
+    r = None if radii is None else _thickness_radii(radii)
+    if data.size == 0:
+        out = np.zeros(data.shape, dtype=np.float32)
+        used = np.zeros(0, dtype=np.float64) if r is None else r
+        return (out, ThicknessSizes(used, np.zeros(used.size, dtype=np.int64))) if return_sizes else out
+    nd = data.ndim
+    data, order, code, buf, extents, w = _layout(data, an, nd)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    ww = tuple(w) + (1.0,) * (3 - nd)
+    step, room = (0.0, r.size) if r is not None else _ladder_room(extents, w)
+    out = np.empty(data.shape, dtype=np.float32, order=order)
+    sizes = np.zeros(room, dtype=np.int64)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().edt_hip_local_thickness(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
+                                                   _morph_flags(black_border, binary), None if r is None else _ptr(r), room, step,
+                                                   _ptr(out), _ptr(sizes), ctypes.byref(n)))
+    if not return_sizes:
+        return out
+    k = int(n.value)
+    used = r if r is not None else np.arange(1, k + 1, dtype=np.float64) * step
+    return out, ThicknessSizes(used, sizes[:k].copy())
 
 
 def set_devices(devices=None):

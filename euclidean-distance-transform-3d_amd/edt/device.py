@@ -708,6 +708,74 @@ def closing(labels: torch.Tensor, radius=1.0, anisotropy=None) -> torch.Tensor:
     return out
 
 
+_thickness_buffers: dict = {}
+
+
+def _thickness_scratch(labels) -> tuple:
+    """S, B (fp32) and the uint8 mask of a local_thickness call: one triple per shape and stream, kept as :func:`_morph_scratch`
+    keeps its pairs (at most 9; the one cached longest ago makes room for a new one)."""
+    key = (tuple(labels.shape), str(labels.device), torch.cuda.current_stream(labels.device).cuda_stream)
+    if key not in _thickness_buffers:
+        if len(_thickness_buffers) > 8:
+            del _thickness_buffers[next(iter(_thickness_buffers))]
+        _thickness_buffers[key] = (torch.empty(labels.shape, dtype=torch.float32, device=labels.device),
+                                   torch.empty(labels.shape, dtype=torch.float32, device=labels.device),
+                                   torch.empty(labels.shape, dtype=torch.uint8, device=labels.device))
+    return _thickness_buffers[key]
+
+
+def _thickness_step(S, B, radius, next_radius, T, mask=None, size=None, smax=None):
+    """edt_hip_thickness_step_device over ``S.numel()`` voxels; ``next_radius=None``: there is none"""
+    _lib.check(_lib.load().edt_hip_thickness_step_device(
+        _vp(S), None if B is None else _vp(B), radius, -1.0 if next_radius is None else next_radius, _vp(T),
+        None if mask is None else _vp(mask), None if size is None else _vp(size), None if smax is None else _vp(smax), S.numel(),
+        _stream_ptr()))
+
+
+def local_thickness(labels: torch.Tensor, radii=None, anisotropy=None, black_border=False, binary=False, return_sizes=False):
+    """:func:`edt.local_thickness` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
+    include/edt_hip.h, "local thickness"): the transform of the labels once, then per radius the binary transform of the mask
+    the step before left and one streaming step, on a cached (S, B, mask) triple per shape and stream.  Returns the float32
+    thickness, a new tensor; with ``return_sizes=True`` the pair ``(thickness, ThicknessSizes(radii, voxels))`` with ``radii`` a
+    float64 numpy array (the radii used) and ``voxels`` an int64 DEVICE tensor.  With explicit ``radii`` the call only enqueues
+    kernels on the current stream -- nothing is read back, and it can be captured into a graph.  ``radii=None`` SYNCHRONISES
+    once: the largest finite squared distance (4 bytes) is read back to build the ladder."""
+    from . import ThicknessSizes, _thickness_radii
+    raw = as_device_tensor(labels)
+    r = None if radii is None else _thickness_radii(radii)
+    labels, nd, ext, w = _ft_tensor(raw, anisotropy, "local_thickness")
+    dtype_code(labels.dtype)
+    if labels.numel() == 0:
+        T = torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)
+        used = np.zeros(0, dtype=np.float64) if r is None else r
+        return (T, ThicknessSizes(used, torch.zeros(used.size, dtype=torch.int64, device=labels.device))) if return_sizes else T
+    S, B, mask = _thickness_scratch(labels)
+    _eroded_field(labels, nd, ext, w, black_border, binary, S, mask)
+    T = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
+    # (the counters are zeroed by fill kernels of the stream: a captured memset does not replay, DESIGN.md 13.3)
+    if r is None:
+        step = min(abs(v) for v in w[:nd])
+        smax = torch.empty(1, dtype=torch.int32, device=labels.device).fill_(0)
+        _thickness_step(S, None, 0.0, step, T, mask=mask, smax=smax)
+        top = float(np.array([smax.item()], dtype=np.int32).view(np.float32)[0])     # the one synchronisation
+        below = lambda j: (float(j) * step) * (float(j) * step) < top  # noqa: E731  (the header's test, in its arithmetic)
+        k = int(np.sqrt(top) / step)
+        while below(k + 1):
+            k += 1
+        while k > 0 and not below(k):
+            k -= 1
+        r = np.arange(1, k + 1, dtype=np.float64) * step
+    else:
+        _thickness_step(S, None, 0.0, float(r[0]), T, mask=mask)
+    sizes = torch.empty(r.size, dtype=torch.int64, device=labels.device).fill_(0)
+    plan = _plan_for(ext[:nd], _lib.U8, labels.device) if r.size else None
+    for j in range(r.size):
+        more = j + 1 < r.size
+        plan.run(mask, w[:nd], False, out=B)
+        _thickness_step(S, B, float(r[j]), float(r[j + 1]) if more else None, T, mask=mask if more else None, size=sizes[j:])
+    return (T, ThicknessSizes(r, sizes)) if return_sizes else T
+
+
 def pass_times():
     """Durations (ms) of the kernels of the last profiled call, as ``[(name, ms), ...]``."""
     lib = _lib.load()

@@ -630,6 +630,64 @@ int edt_hip_morph_select_device(const void *d_values, const void *d_guard, int d
 int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                        int op, double radius, int flags, void *output);
 
+/* ---- local thickness: for every voxel the radius of the largest ball of a ladder whose opening still contains it -------------
+ * The granulometric ("porespy local_thickness", ImageJ "Local Thickness") thickness of every label at once, quantised to a
+ * ladder of radii.  Conventions, labels, voxel sizes, black_border (EDT_FLAG_BLACK_BORDER) and binary (EDT_FLAG_MORPH_BINARY;
+ * EDT_BOOL is always binary) as in "morphology" above; the fields are exactly what edt_hip_edtsq_device writes and every
+ * comparison widens the fp32 field value to fp64.
+ *
+ * Radii r_1 < r_2 < ... < r_k, each finite and > 0 with r_j * r_j finite in fp64.
+ *   S = edtsq(labels, w, black_border), or the field of the uint8 mask labels != 0 under binary: the field opening measures.
+ *   For each j, O_j = { p : opening(labels, r_j, black_border, binary)[p] != 0 }, exactly as "morphology" defines opening:
+ *     z_j[p] = 1 unless (double)S[p] > r_j^2;  B_j = edtsq(z_j, w, black border off);
+ *     p in O_j  iff  p is foreground and (double)B_j[p] <= r_j^2.
+ *   "Foreground" is (double)S[p] > 0, which is labels[p] != 0 under the type's own comparison (-0.0 is background, a NaN is
+ *   foreground): a foreground voxel is at least one voxel away from anything that is not of its label.
+ *   thickness[p] (fp32) = (float)r_j for the LARGEST j with p in O_j; +0.0 for background and for foreground voxels that lie in
+ *   no O_j (thinner than the smallest ball).
+ *   sizes[j] (int64) = |O_j|: the granulometry curve (cumulative size distribution).
+ * "Largest j" is meant literally.  The openings by digital balls are not nested: a voxel may lie in O_j and not in O_(j-1), and
+ * sizes need not be monotone.  The result is what overwriting in ascending order gives: T = 0; for j = 1..k: T[O_j] = r_j.
+ *
+ * The default ladder (radii == NULL): r_j = j * step in fp64, over all j >= 1 with r_j * r_j < Smax, where Smax is the largest
+ * FINITE value of S widened to fp64, or 0 if S has none.  A ball with r^2 >= Smax erodes every voxel with a finite S.  The
+ * Python layers pass step = the smallest |voxel size|.
+ * One label everywhere and no black border: S = +inf everywhere.  The default ladder is then empty: thickness is zero and no radius
+ * is used.  Explicit radii give thickness = (float)r_k everywhere and sizes[j] = voxels: no ball ever leaves the label.
+ *
+ * One step on device-resident fields.  Enqueue-only on `stream`: no allocation, no synchronisation, no scratch; pointers as in
+ * "Alignment" above: any element offset is served, four voxels per thread where d_S, d_B and d_T are 16-byte and d_mask is 4-byte
+ * aligned, one voxel per thread otherwise, with the same bits; offsets are 64-bit.
+ *   d_B != NULL (a radius step): in(i) = (double)S[i] > 0 && (double)B[i] <= radius^2;  T[i] = (float)radius where in(i), and is
+ *     left as it is elsewhere;  d_size != NULL: *d_size += the number of voxels with in(i).
+ *   d_B == NULL (step 0; `radius` is ignored): T[i] = +0.0 for every i;  d_smax_bits != NULL: *d_smax_bits = max(*d_smax_bits, the
+ *     bit pattern of the largest S[i] that is finite and >= 0) -- non-negative floats order as their bits.
+ *   d_mask != NULL: mask[i] = (double)S[i] > next_radius^2 ? 0 : 1, the z of the next radius.  next_radius < 0 means none, and
+ *     d_mask is given exactly when there is one.
+ * The counters are accumulated into: the caller initialises them (zero) on the stream.  d_size belongs to a radius step,
+ * d_smax_bits to step 0.  EDT_ERR_BAD_ARG before any device work: count < 0; d_S or d_T NULL; a radius (with d_B) or a next
+ * radius >= 0 that is not finite and > 0 with a finite square, or NaN; d_mask without a next radius or a next radius without
+ * d_mask; d_size without d_B; d_smax_bits with d_B.  count == 0 is EDT_OK once the arguments are through. */
+int edt_hip_thickness_step_device(const float *d_S, const float *d_B, double radius, double next_radius, float *d_T,
+                                  uint8_t *d_mask, int64_t *d_size, uint32_t *d_smax_bits, int64_t count, void *stream);
+
+/* The whole operation on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, thickness and sizes down once, everything between on the
+ * device -- S once, then per radius one binary transform and one step.
+ * ndim in {1,2,3}, unused extents 1.  flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY, anything else is EDT_ERR_UNSUPPORTED.
+ * radii != NULL: n_radii >= 1 radii as above; `step` is ignored; sizes has n_radii entries; *n_used = n_radii.
+ * radii == NULL: the default ladder with `step` (finite, > 0, finite square); Smax is read back once (4 bytes); n_radii (>= 0)
+ *   is the room in sizes (sizes may be NULL if it is 0); *n_used = the ladder's length and sizes[0 .. *n_used) are written.  A
+ *   ladder longer than n_radii is EDT_ERR_BAD_ARG after the first transform: *n_used then holds the length it needs and
+ *   nothing else is written.  r_j of that ladder is j * step.
+ * thickness: voxels floats.  Refused with EDT_ERR_BAD_ARG before any device work: radii that are not strictly ascending, not
+ * positive, not finite or whose square overflows; an explicit list with n_radii < 1; n_radii < 0; a bad step for the default
+ * ladder; bad voxel sizes; NULL pointers (thickness, n_used, labels; sizes where it has entries); thickness or sizes
+ * overlapping the labels or each other.  An empty volume is EDT_OK with nothing touched. */
+int edt_hip_local_thickness(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                            float wz, int flags, const double *radii, int64_t n_radii, double step, float *thickness,
+                            int64_t *sizes, int64_t *n_used);
+
 #ifdef __cplusplus
 }
 #endif
