@@ -17,7 +17,7 @@ namespace edt_amd {
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
 // what a pooled buffer is for -- one slot each, so two roles never share memory within a call
-enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count, morphology's mask, local thickness' mask and counters */, kSecondField, kThirdField /* local thickness: S, B and T are alive together */, kSlotCount };
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count, morphology's mask, local thickness' mask and counters, the medial axis' mask */, kSecondField, kThirdField /* local thickness: S, B and T are alive together; the medial axis: feature planes and field, and the radius */, kSlotCount };
 struct DevicePool {
   static constexpr int kSlots = kSlotCount;
   void *p[kSlots] = {};
@@ -623,6 +623,75 @@ static int thickness_host(const void *labels, int dtype, int ndim, int64_t sx, i
   return EDT_OK;
 }
 
+// the medial axis on host buffers (kernel: k_medial_axis, edt_medial.hip; contract: include/edt_hip.h, "medial axis"): labels up
+// once; the mask (under binary), the feature transform, the field (when the radius is wanted) and one step on the device; out and
+// radius down once.  The buffers: the feature planes in kSecondField with the field behind them, the mask in kAux, the radius in
+// kThirdField, one workspace that serves the feature transform and the transform of the field.
+static int medial_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                       int flags, double gamma, double ratio, void *out, float *radius) {
+  double g2 = 0.0;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !out, &empty, [&](After what) -> int {
+    if (what == After::shape) {
+      if (flags & ~(EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY)) {
+        set_error("medial_axis takes EDT_FLAG_BLACK_BORDER and EDT_FLAG_MORPH_BINARY only");
+        return EDT_ERR_UNSUPPORTED;
+      }
+      return medial_check_params(gamma, ratio, "medial_axis", &g2);
+    }
+    if (what == After::pointers) {
+      const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), rbytes = radius ? voxels * sizeof(float) : 0;
+      const auto overlap = [](const void *p, size_t pb, const void *q, size_t qb) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return pb > 0 && qb > 0 && a < b + qb && b < a + pb;
+      };
+      if (overlap(labels, lbytes, out, lbytes) || overlap(labels, lbytes, radius, rbytes) || overlap(out, lbytes, radius, rbytes)) {
+        set_error("medial_axis: out, radius and the labels may not overlap");
+        return EDT_ERR_BAD_ARG;
+      }
+    }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const int64_t voxels = sx * sy * sz;
+  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
+  const size_t pbytes = align_up((size_t)voxels * ndim * sizeof(int32_t), 256);
+  const int generic = env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0;
+  const int bb = flags & EDT_FLAG_BLACK_BORDER;
+  const bool binary = (flags & EDT_FLAG_MORPH_BINARY) || dtype == EDT_BOOL;
+  const int of_dtype = binary ? EDT_U8 : dtype;  // what the transforms read: the mask, or the labels
+  size_t wbytes = edt_hip_feature_workspace_bytes(of_dtype, ndim, sx, sy, sz, bb);
+  if (radius) wbytes = std::max(wbytes, edt_hip_workspace_bytes_flags(of_dtype, ndim, sx, sy, sz, generic));
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}, {kSecondField, pbytes + (radius ? fbytes : 0)}})) != EDT_OK)
+    return rc;
+  if (binary && (rc = st.alloc(kAux, (size_t)voxels)) != EDT_OK) return rc;
+  if (radius && (rc = st.alloc(kThirdField, fbytes)) != EDT_OK) return rc;
+  void *const d_labels = st.p[kLabels], *const d_ws = st.p[kWorkspace];
+  int32_t *const planes = st.at<int32_t>(kSecondField);
+  float *const field = radius ? reinterpret_cast<float *>(st.at<char>(kSecondField) + pbytes) : nullptr;
+  float *const d_radius = radius ? st.at<float>(kThirdField) : nullptr;
+  st.expect(out, lbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  const void *of = d_labels;
+  if (binary) {
+    if ((rc = launch_is_foreground(dtype, d_labels, st.at<uint8_t>(kAux), voxels, nullptr)) != EDT_OK) return rc;
+    of = st.p[kAux];
+  }
+  if ((rc = edt_hip_feature_transform_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, bb, planes, d_ws, wbytes, nullptr)) != EDT_OK)
+    return rc;
+  if (radius && (rc = run_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, bb | EDT_FLAG_SQRT | generic, field, d_ws, wbytes, nullptr)) != EDT_OK)
+    return rc;
+  if ((rc = launch_medial_axis(dtype, d_labels, ndim, sx, sy, sz, wx, wy, wz, planes, flags, g2, ratio, st.p[kOut], field, d_radius,
+                               nullptr)) != EDT_OK ||
+      (rc = st.down(out, kOut, lbytes)) != EDT_OK)
+    return rc;
+  return radius ? st.down(radius, kThirdField, fbytes) : EDT_OK;
+}
+
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -815,6 +884,11 @@ int edt_hip_local_thickness(const void *labels, int dtype, int ndim, int64_t sx,
                             int flags, const double *radii, int64_t n_radii, double step, float *thickness, int64_t *sizes,
                             int64_t *n_used) {
   return thickness_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, radii, n_radii, step, thickness, sizes, n_used);
+}
+
+int edt_hip_medial_axis(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                        int flags, double gamma, double ratio, void *out, float *radius) {
+  return medial_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, gamma, ratio, out, radius);
 }
 
 }  // extern "C"

@@ -99,6 +99,15 @@ int launch_thickness_step(const float *S, const float *B, double r2, float rf, d
                           uint32_t *smax_bits, int64_t count, hipStream_t stream);
 // *r2 = radius * radius; EDT_ERR_BAD_ARG, named "<who>: ...", unless radius is finite and > 0 and *r2 is finite
 int thickness_radius_squared(double radius, const char *who, double *r2);
+// ---- the stencil of the integer medial axis: edt_medial.hip ------------------------------
+// *g2 = gamma * gamma; EDT_ERR_BAD_ARG, named "<who>: ...", unless gamma >= 0 with *g2 finite and ratio is finite and >= 0
+int medial_check_params(double gamma, double ratio, const char *who, double *g2);
+// one step (include/edt_hip.h, "medial axis") over the ndim feature planes `feat` of the labels (or of their mask, under
+// EDT_FLAG_MORPH_BINARY): out[p] = labels[p] on the axis, zero bits elsewhere; radius (with field; both may be null): field[p] on
+// the axis, +0.0 elsewhere.  flags: EDT_FLAG_BLACK_BORDER (every voxel has a feature), EDT_FLAG_MORPH_BINARY.
+int launch_medial_axis(int dtype, const void *labels, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                       const int32_t *feat, int flags, double g2, double ratio, void *out, const float *field, float *radius,
+                       hipStream_t stream);
 
 }  // namespace edt_amd
 

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import multiprocessing
 
 import numpy as np
@@ -38,6 +39,7 @@ __all__ = [
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
     "label_stats", "connected_components", "fill_holes", "dust", "DustCounts",
     "erode", "dilate", "opening", "closing", "local_thickness", "ThicknessSizes",
+    "medial_axis",
 ]
 
 
@@ -579,6 +581,72 @@ def local_thickness(data, radii=None, anisotropy=None, black_border=False, binar
     k = int(n.value)
     used = r if r is not None else np.arange(1, k + 1, dtype=np.float64) * step
     return out, ThicknessSizes(used, sizes[:k].copy())
+
+
+def _medial_ratio(min_angle, who="medial_axis"):
+    """The angle pruning of a medial_axis call, ``min_angle`` in degrees in [0, 180), as the ``ratio`` of the C ABI:
+    ``tan(radians(a) / 2) ** 2`` (0 switches it off); anything else is a ValueError.  Both Python layers convert here."""
+    try:
+        a = float(min_angle)
+    except TypeError:
+        raise ValueError(f"{who}: min_angle must be a number, got {min_angle!r}") from None
+    if not (0.0 <= a < 180.0):
+        raise ValueError(f"{who}: min_angle must be in [0, 180) degrees, got {min_angle!r}")
+    ratio = math.tan(math.radians(a) / 2.0) ** 2
+    if not np.isfinite(ratio):
+        raise ValueError(f"{who}: min_angle {min_angle!r} is too close to 180 degrees")
+    return ratio
+
+
+def _medial_gamma(gamma, w, who="medial_axis"):
+    """The constant pruning of a medial_axis call as a float: ``None`` is the largest |voxel size| (the paper's "features more
+    than one voxel apart"); otherwise finite, >= 0 and with a finite square, else ValueError."""
+    if gamma is None:
+        return max(abs(float(v)) for v in w)
+    try:
+        g = float(gamma)
+    except TypeError:
+        raise ValueError(f"{who}: gamma must be a number, got {gamma!r}") from None
+    if not g >= 0.0 or not np.isfinite(g * g):
+        raise ValueError(f"{who}: gamma must be finite and >= 0 with a finite square, got {gamma!r}")
+    return g
+
+
+def medial_axis(data, gamma=None, min_angle=0.0, anisotropy=None, black_border=False, binary=False, return_distance=False,
+                parallel=1):
+    """The integer medial axis (Hesselink & Roerdink 2008) of every label of a 1-D to 3-D label array at once: the centre lines
+    and centre surfaces of the objects, straight from the feature transform (contract: include/edt_hip.h, "medial axis").  A
+    voxel is on the axis iff it has a face neighbour of its own label whose nearest voxel of another label (its feature) lies
+    farther than ``gamma`` from the voxel's own feature, and the bisector of the two features passes on the voxel's side of
+    the midpoint between the two voxels.
+
+    ``gamma``: constant pruning, a physical distance; ``None`` is the largest voxel size (the paper's "more than one voxel
+    apart").  ``min_angle``: angle pruning in degrees, in [0, 180): the two features must subtend at least this angle at the
+    midpoint of the two voxels (0: off; larger angles keep only the centre of the object and drop the branches into its
+    corners).  ``anisotropy``, ``black_border`` and ``binary`` as for :func:`erode`: with ``binary=True`` the axis is that of
+    the mask ``data != 0`` (a bool array is always binary), otherwise neighbouring labels bound each other.  Without a black
+    border an object that fills the array has no axis.
+
+    Returns an array of ``data``'s shape, dtype and memory order: the label on the axis, 0 elsewhere.  With
+    ``return_distance=True`` the pair ``(axis, distance)``: ``distance`` is float32, ``edt(data)`` (of the mask under binary) on
+    the axis and 0 elsewhere -- the radius function.  One trip over PCIe each way."""
+    data, an = _ft_args(data, anisotropy, "medial_axis")
+    _label_code(data)
+    ratio = _medial_ratio(min_angle)
+    if data.size == 0:
+        _medial_gamma(gamma, (1.0,))
+        return (data.copy(), np.zeros(data.shape, dtype=np.float32)) if return_distance else data.copy()
+    nd = data.ndim
+    data, order, code, buf, extents, w = _layout(data, an, nd)
+    g = _medial_gamma(gamma, w)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    ww = tuple(w) + (1.0,) * (3 - nd)
+    out = np.empty(data.shape, dtype=data.dtype, order=order)
+    dist = np.empty(data.shape, dtype=np.float32, order=order) if return_distance else None
+    _lib.check(_lib.load().edt_hip_medial_axis(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
+                                               _morph_flags(black_border, binary), g, ratio, _ptr(out),
+                                               None if dist is None else _ptr(dist)))
+    return (out, dist) if return_distance else out
 
 
 def set_devices(devices=None):

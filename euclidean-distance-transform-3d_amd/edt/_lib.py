@@ -120,6 +120,8 @@ SIGNATURES = {
     "edt_hip_morphology": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _i, _vp]),
     "edt_hip_thickness_step_device": (_i, [_vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _i64, _vp]),
     "edt_hip_local_thickness": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp, _i64, _d, _vp, _vp, _vp]),
+    "edt_hip_medial_axis_step_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    "edt_hip_medial_axis": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _d, _vp, _vp]),
 }
 
 _lib = None

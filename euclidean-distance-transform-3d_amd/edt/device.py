@@ -776,6 +776,71 @@ def local_thickness(labels: torch.Tensor, radii=None, anisotropy=None, black_bor
     return (T, ThicknessSizes(r, sizes)) if return_sizes else T
 
 
+_medial_buffers: dict = {}
+
+
+def _medial_scratch(labels, nd, ext, code, flags, binary, want_field) -> dict:
+    """The scratch of a medial_axis call: the feature planes and the feature transform's workspace, plus the uint8 mask under
+    binary and the fp32 field where the radius is wanted (each allocated by the first call that needs it): one set per shape,
+    transformed dtype and stream, kept as :func:`_morph_scratch` keeps its pairs (at most 9; the one cached longest ago makes
+    room for a new one)."""
+    key = (tuple(labels.shape), code, str(labels.device), torch.cuda.current_stream(labels.device).cuda_stream)
+    if key not in _medial_buffers:
+        nbytes = _lib.load().edt_hip_feature_workspace_bytes(code, nd, *ext, flags & _lib.FLAG_BLACK_BORDER)
+        if nbytes == 0:
+            _lib.check(-2)
+        if len(_medial_buffers) > 8:
+            del _medial_buffers[next(iter(_medial_buffers))]
+        _medial_buffers[key] = {"planes": torch.empty((nd,) + tuple(labels.shape), dtype=torch.int32, device=labels.device),
+                                "ws": torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)}
+    s = _medial_buffers[key]
+    if binary and "mask" not in s:
+        s["mask"] = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    if want_field and "field" not in s:
+        s["field"] = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
+    return s
+
+
+def _medial_step(labels, nd, ext, w, planes, flags, gamma, ratio, out, field=None, radius=None):
+    """edt_hip_medial_axis_step_device on the x, y, z feature planes ``planes`` of ``labels``"""
+    _lib.check(_lib.load().edt_hip_medial_axis_step_device(
+        _vp(labels), dtype_code(labels.dtype), nd, *ext, *w, _vp(planes), flags, gamma, ratio, _vp(out),
+        None if field is None else _vp(field), None if radius is None else _vp(radius), _stream_ptr()))
+    return out
+
+
+def medial_axis(labels: torch.Tensor, gamma=None, min_angle=0.0, anisotropy=None, black_border=False, binary=False,
+                return_distance=False):
+    """:func:`edt.medial_axis` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
+    include/edt_hip.h, "medial axis"): the mask under binary, the feature transform, the distance transform where the radius
+    is wanted, and one streaming stencil, all enqueued on the current stream -- nothing is read back.  The scratch (feature
+    planes, the transform's workspace, mask and field) is cached per shape and stream: a second call of one shape allocates
+    only what it returns.  Returns a new tensor of the labels' dtype and shape; with ``return_distance=True`` the pair
+    ``(axis, distance)``, distance float32."""
+    from . import _medial_gamma, _medial_ratio, _morph_flags
+    raw = as_device_tensor(labels)
+    ratio = _medial_ratio(min_angle)
+    labels, nd, ext, w = _ft_tensor(raw, anisotropy, "medial_axis")
+    code = dtype_code(labels.dtype)
+    g = _medial_gamma(gamma, w[:nd])
+    if labels.numel() == 0:
+        return (labels.clone(), torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)) if return_distance else labels.clone()
+    flags = _morph_flags(black_border, binary)
+    binary = bool(binary) or labels.dtype == torch.bool
+    of_code = _lib.U8 if binary else code
+    s = _medial_scratch(labels, nd, ext, of_code, flags, binary, return_distance)
+    of = _is_foreground(labels, s["mask"]) if binary else labels
+    _lib.check(_lib.load().edt_hip_feature_transform_device(
+        _vp(of), of_code, nd, *ext, *w, flags & _lib.FLAG_BLACK_BORDER, _vp(s["planes"]), _vp(s["ws"]), s["ws"].numel(), _stream_ptr()))
+    out = torch.empty_like(labels)
+    if not return_distance:
+        return _medial_step(labels, nd, ext, w, s["planes"], flags, g, ratio, out)
+    _plan_for(ext[:nd], of_code, labels.device).run(of, w[:nd], black_border, sqrt=True, out=s["field"])
+    radius = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
+    _medial_step(labels, nd, ext, w, s["planes"], flags, g, ratio, out, s["field"], radius)
+    return out, radius
+
+
 def pass_times():
     """Durations (ms) of the kernels of the last profiled call, as ``[(name, ms), ...]``."""
     lib = _lib.load()

@@ -688,6 +688,65 @@ int edt_hip_local_thickness(const void *labels, int dtype, int ndim, int64_t sx,
                             float wz, int flags, const double *radii, int64_t n_radii, double step, float *thickness,
                             int64_t *sizes, int64_t *n_used);
 
+/* ---- medial axis: the integer medial axis of every label at once, a stencil on the feature transform ---------------------------
+ * The method of Hesselink & Roerdink, "Euclidean skeletons of digital image and volume data in linear time by the integer medial
+ * axis transform" (IEEE PAMI 30(12), 2008), in gather form: centre lines and centre surfaces of the objects of a label volume.
+ * Conventions as in "feature transform": x fastest, idx = x + sx * (y + sy * z), label 0 is background, labels compared at full
+ * width with their type's == (-0.0 is background, a NaN voxel equals nothing); voxel sizes as for edt_hip_edtsq_device.
+ * F(p) is the feature of p from edt_hip_feature_transform_device with the same voxel sizes and border flag: the feature of the
+ * labels themselves, or of the uint8 mask labels != 0 under EDT_FLAG_MORPH_BINARY (EDT_BOOL is always binary; a NaN is non-zero).
+ *
+ * A pair (p, q), q one of the 2 * ndim face neighbours of p INSIDE the volume, is eligible iff
+ *   labels[p] != 0;  labels[q] == labels[p] under the type's own == (under binary: both non-zero);  and both voxels have a
+ *   feature ("no feature" is every component -1 with the border off; with EDT_FLAG_BLACK_BORDER every voxel has one).
+ * For an eligible pair, over the ndim axes c (the axes a call does not use contribute nothing):
+ *   d_c = F(p)_c - F(q)_c   and   s_c = F(p)_c + F(q)_c - p_c - q_c   as 64-bit integers, then converted to fp64;
+ *   A_c = (double)w_c * (double)w_c;
+ *   sep  = (A_x (d_x d_x) + A_y (d_y d_y)) + A_z (d_z d_z)      the squared distance between the two features
+ *   h    = (A_x (s_x s_x) + A_y (s_y s_y)) + A_z (s_z s_z)      four times the squared distance from the midpoint of p and q to
+ *                                                               the midpoint of the features
+ *   crit = (A_x (d_x s_x) + A_y (d_y s_y)) + A_z (d_z s_z)      which side of the features' bisector that midpoint lies on
+ * in fp64, the product of the two integers first, then the product with A_c, then the sums in the order shown: every product and
+ * sum rounded once, nothing contracted into an fma.
+ * p is ON THE AXIS iff some eligible q has   sep > gamma * gamma   and   sep >= ratio * h   and   crit >= 0.
+ *   gamma: constant pruning, a physical distance (the paper's test is gamma = 1 in voxel units: features more than one voxel apart);
+ *   ratio = tan^2(theta / 2): angle pruning -- theta is the angle the two features subtend at the midpoint of p and q; 0 = off.
+ * The two pruning tests are symmetric in (p, q) and crit is antisymmetric, bit for bit: of two neighbours whose features pass the
+ * pruning, the one on whose side of the midpoint the bisector passes is on the axis -- both if it passes through the midpoint.
+ * Every voxel decides for itself from what it reads (no atomics, no iteration): the same call gives the same output.
+ * Where the voxel sizes share a quantum and the extents are small enough for every term to be an exact integer in fp64, the axis
+ * is fully determined by the feature transform's tie rule; otherwise by the features the transform returned and by the evaluation
+ * order above.
+ * Output: out, of the labels' dtype: labels[p] bit for bit on the axis (a NaN keeps its payload), zero bits elsewhere.  Optionally
+ * the radius function: radius[p] = field[p] on the axis and +0.0 elsewhere, for an fp32 field of the caller's choice. */
+
+/* One step on device-resident data: d_features are the ndim planes edt_hip_feature_transform_device wrote for these labels (or
+ * for their mask, under binary).  Enqueue-only on `stream`: no allocation, no synchronisation, no scratch.  Pointers as in
+ * "Alignment" above: any element offset is served, by the same code (one element per lane).  Offsets are 64-bit.  All seven label
+ * dtypes; 8-byte and float labels move as bit patterns.
+ * flags: EDT_FLAG_BLACK_BORDER -- the border flag the features were computed with: it says which "no feature" convention
+ *   applies -- and EDT_FLAG_MORPH_BINARY; anything else is EDT_ERR_UNSUPPORTED.
+ * d_field and d_radius come both or neither.  d_out may not alias d_labels (the neighbours are still being read); any other
+ * overlap is the caller's error.
+ * EDT_ERR_BAD_ARG before any device work: a bad dtype, ndim or extent (unused extents 1); gamma or ratio NaN, negative or
+ * infinite, or gamma * gamma not finite; bad voxel sizes; d_field without d_radius or d_radius without d_field; for a volume
+ * that is not empty NULL d_labels, d_features or d_out, and d_out == d_labels.  A volume of more than 2^33 tiles of 62 x 4 x 16
+ * voxels is EDT_ERR_UNSUPPORTED.  An empty volume is EDT_OK once the arguments are through. */
+int edt_hip_medial_axis_step_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                                    float wz, const int32_t *d_features, int flags, double gamma, double ratio, void *d_out,
+                                    const float *d_field, float *d_radius, void *stream);
+
+/* The whole operation on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once; on the device the mask (under binary), the feature transform,
+ * the field when `radius` is wanted, and one step; out -- and radius if it is not NULL -- down once.
+ * The field of `radius` is what edt_hip_edt3d / edt_hip_edt2d / the 1-D transform with sqrt write for the same labels (under
+ * binary: for the mask), voxel sizes and border: the distance to the nearest voxel of another label, the radius function.
+ * ndim in {1,2,3}, unused extents 1.  flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY, anything else is EDT_ERR_UNSUPPORTED.
+ * `out` has the labels' dtype.  Refused with EDT_ERR_BAD_ARG before any device work: what the step refuses; NULL labels or out;
+ * out or radius overlapping the labels or each other.  An empty volume is EDT_OK with nothing touched. */
+int edt_hip_medial_axis(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                        int flags, double gamma, double ratio, void *out, float *radius);
+
 #ifdef __cplusplus
 }
 #endif
