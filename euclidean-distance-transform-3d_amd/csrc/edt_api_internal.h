@@ -52,6 +52,17 @@ int require_device();
 bool label_op_begin(const char *who, int own_rc, void *d_result, size_t result_words, int64_t voxels, bool null_data,
                     bool aliased, const void *d_workspace, size_t workspace_bytes, size_t needed, const char *query,
                     hipStream_t stream, int *rc);
+// What morphology, local thickness and the medial axis refuse after the shape and before the voxel sizes, on host buffers and on
+// device-resident data alike (edt_fieldops.hip): a bad op, flags the operation does not take, bad radii, gamma or ratio.
+// *r2 = radius^2, *g2 = gamma^2.
+int morphology_check_args(int op, double radius, int flags, double *r2);
+int thickness_check_args(int flags, const double *radii, int64_t n_radii, double step);
+int medial_check_args(int flags, double gamma, double ratio, double *g2);
+// whether [p, p + pb) and [q, q + qb) share a byte (an empty range shares none)
+inline bool ranges_overlap(const void *p, size_t pb, const void *q, size_t qb) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return pb > 0 && qb > 0 && a < b + qb && b < a + pb;
+}
 // the pass pipeline on device-resident data
 int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                int flags, float *d_out, void *d_ws, size_t ws_bytes, hipStream_t stream);

@@ -17,7 +17,7 @@ namespace edt_amd {
 // process-wide pool, one host call at a time (the mutex is held for the whole call); released by
 // edt_hip_release_cache() or at exit.  EDT_HIP_NO_CACHE=1 restores allocate-per-call.
 // what a pooled buffer is for -- one slot each, so two roles never share memory within a call
-enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, the label-stats table, the component / filled-voxel count, morphology's mask, local thickness' mask and counters, the medial axis' mask */, kSecondField, kThirdField /* local thickness: S, B and T are alive together; the medial axis: feature planes and field, and the radius */, kSlotCount };
+enum Slot : int { kLabels, kOut, kWorkspace, kAux /* sdf's mask, the voxel graph, tables and counts */, kSecondField, kSlotCount };
 struct DevicePool {
   static constexpr int kSlots = kSlotCount;
   void *p[kSlots] = {};
@@ -430,268 +430,6 @@ static int label_op_host(const LabelOp &op, const void *labels, int dtype, int n
   return st.down(result, kAux, rbytes);
 }
 
-// erode / dilate / opening / closing on host buffers (kernels: edt_morph.hip; contract: include/edt_hip.h, "morphology"): labels
-// up once, the transforms (run_device), the mask and select kernels and expand_labels on the device, the output down once.  The
-// composition owns its buffers: the fp32 field in kSecondField, the uint8 mask in kAux, one workspace that serves every step.
-static int morphology_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
-                           float wz, int op, double radius, int flags, void *output) {
-  const bool measures = op == EDT_MORPH_ERODE || op == EDT_MORPH_OPEN;  // the ops that take flags: their first step is a transform of the labels
-  double r2 = 0.0;
-  float *const w[3] = {&wx, &wy, &wz};
-  bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !output, &empty, [&](After what) -> int {
-    if (what == After::shape) {
-      if (op < EDT_MORPH_ERODE || op > EDT_MORPH_CLOSE) { set_error("morphology: op must be one of EDT_MORPH_*"); return EDT_ERR_BAD_ARG; }
-      if (flags & ~(measures ? (EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY) : 0)) {
-        set_error(measures ? "morphology: erode / opening take EDT_FLAG_BLACK_BORDER and EDT_FLAG_MORPH_BINARY only"
-                           : "morphology: dilate / closing take no flags");
-        return EDT_ERR_UNSUPPORTED;
-      }
-      return morph_radius_squared(radius, op == EDT_MORPH_DILATE, "morphology", &r2);
-    }
-    if (what == After::pointers) {
-      const size_t bytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
-      const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(output);
-      if (a < b + bytes && b < a + bytes) { set_error("morphology: the output may not overlap the labels"); return EDT_ERR_BAD_ARG; }
-    }
-    return EDT_OK;
-  });
-  if (rc != EDT_OK || empty) return rc;
-  ListedDevice on_listed_device;
-  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const int64_t voxels = sx * sy * sz;
-  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
-  const int generic = env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0;
-  const int bb = flags & EDT_FLAG_BLACK_BORDER;
-  const bool binary = (flags & EDT_FLAG_MORPH_BINARY) || dtype == EDT_BOOL;
-  size_t wbytes = edt_hip_workspace_bytes_flags(EDT_U8, ndim, sx, sy, sz, generic);
-  if (measures && !binary) wbytes = std::max(wbytes, edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, generic));
-  if (!measures) wbytes = std::max(wbytes, edt_hip_expand_labels_workspace_bytes(dtype, ndim, sx, sy, sz));
-  Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}})) != EDT_OK) return rc;
-  if (op != EDT_MORPH_DILATE && (rc = st.alloc({{kAux, (size_t)voxels}, {kSecondField, fbytes}})) != EDT_OK) return rc;
-  void *const d_labels = st.p[kLabels], *const d_out = st.p[kOut], *const d_ws = st.p[kWorkspace];
-  float *const field = st.at<float>(kSecondField);
-  uint8_t *const mask = st.at<uint8_t>(kAux);
-  const auto transform = [&](const void *of, int of_dtype, int border) {
-    return run_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, border | generic, field, d_ws, wbytes, nullptr);
-  };
-  st.expect(output, lbytes);
-  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  if (measures) {
-    // S: the transform of the labels, or of the mask labels != 0
-    if (binary) {
-      if ((rc = launch_is_foreground(dtype, d_labels, mask, voxels, nullptr)) != EDT_OK) return rc;
-      rc = transform(mask, EDT_U8, bb);
-    } else {
-      rc = transform(d_labels, dtype, bb);
-    }
-    if (rc != EDT_OK) return rc;
-    if (op == EDT_MORPH_ERODE) {
-      rc = launch_morph_select(dtype, d_labels, nullptr, field, r2, EDT_MORPH_FARTHER, d_out, nullptr, voxels, nullptr);
-    } else {
-      // z = not eroded, B = its transform without a border, out = the labels within r of the eroded set
-      if ((rc = launch_morph_select(dtype, nullptr, nullptr, field, r2, EDT_MORPH_FARTHER, nullptr, mask, voxels, nullptr)) != EDT_OK ||
-          (rc = transform(mask, EDT_U8, 0)) != EDT_OK)
-        return rc;
-      rc = launch_morph_select(dtype, d_labels, nullptr, field, r2, EDT_MORPH_WITHIN, d_out, nullptr, voxels, nullptr);
-    }
-  } else {
-    rc = edt_hip_expand_labels_device(d_labels, dtype, ndim, sx, sy, sz, wx, wy, wz, radius, d_out, d_ws, wbytes, nullptr);
-    if (rc == EDT_OK && op == EDT_MORPH_CLOSE) {
-      // the dilation eroded again: D kept where the labels were, or farther than r from what the dilation left empty
-      if ((rc = launch_is_foreground(dtype, d_out, mask, voxels, nullptr)) != EDT_OK || (rc = transform(mask, EDT_U8, 0)) != EDT_OK)
-        return rc;
-      rc = launch_morph_select(dtype, d_out, d_labels, field, r2, EDT_MORPH_FARTHER, d_out, nullptr, voxels, nullptr);
-    }
-  }
-  return rc != EDT_OK ? rc : st.down(output, kOut, lbytes);
-}
-
-// local thickness on host buffers (kernel: k_thickness_step, edt_morph.hip; contract: include/edt_hip.h, "local thickness"):
-// labels up once, S by one transform, then per radius the binary transform of the mask the step before left and one step; T and
-// the sizes down once.  The buffers: S in kSecondField, B in kThirdField, T in kOut, the byte mask in kAux with the counters
-// (k sizes, then Smax's bits) behind it, one workspace that serves every transform.
-static int thickness_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
-                          int flags, const double *radii, int64_t n_radii, double step, float *thickness, int64_t *sizes,
-                          int64_t *n_used) {
-  float *const w[3] = {&wx, &wy, &wz};
-  bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !thickness || !n_used || (n_radii > 0 && !sizes), &empty, [&](After what) -> int {
-    if (what == After::shape) {
-      if (flags & ~(EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY)) {
-        set_error("local_thickness takes EDT_FLAG_BLACK_BORDER and EDT_FLAG_MORPH_BINARY only");
-        return EDT_ERR_UNSUPPORTED;
-      }
-      double r2;
-      if (!radii) {
-        if (n_radii < 0) { set_error("local_thickness: n_radii < 0"); return EDT_ERR_BAD_ARG; }
-        return thickness_radius_squared(step, "local_thickness (the ladder's step)", &r2);
-      }
-      if (n_radii < 1) { set_error("local_thickness: an explicit list needs n_radii >= 1"); return EDT_ERR_BAD_ARG; }
-      for (int64_t j = 0; j < n_radii; ++j) {
-        if (const int bad = thickness_radius_squared(radii[j], "local_thickness", &r2)) return bad;
-        if (j > 0 && !(radii[j] > radii[j - 1])) { set_error("local_thickness: radii must be strictly ascending"); return EDT_ERR_BAD_ARG; }
-      }
-    }
-    if (what == After::pointers) {
-      const size_t voxels = (size_t)(sx * sy * sz);
-      const auto overlap = [](const void *p, size_t pb, const void *q, size_t qb) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return pb > 0 && qb > 0 && a < b + qb && b < a + pb;
-      };
-      const size_t lbytes = voxels * dtype_size(dtype), tbytes = voxels * sizeof(float), sbytes = (size_t)n_radii * sizeof(int64_t);
-      if (overlap(labels, lbytes, thickness, tbytes) || overlap(labels, lbytes, sizes, sbytes) || overlap(thickness, tbytes, sizes, sbytes)) {
-        set_error("local_thickness: thickness, sizes and the labels may not overlap");
-        return EDT_ERR_BAD_ARG;
-      }
-    }
-    return EDT_OK;
-  });
-  if (rc != EDT_OK || empty) return rc;
-  ListedDevice on_listed_device;
-  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const int64_t voxels = sx * sy * sz;
-  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
-  const int generic = env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0;
-  const int bb = flags & EDT_FLAG_BLACK_BORDER;
-  const bool binary = (flags & EDT_FLAG_MORPH_BINARY) || dtype == EDT_BOOL;
-  size_t wbytes = edt_hip_workspace_bytes_flags(EDT_U8, ndim, sx, sy, sz, generic);
-  if (!binary) wbytes = std::max(wbytes, edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, generic));
-  const size_t counters = align_up((size_t)voxels, 256);           // k int64 sizes, then the bits of Smax
-  const size_t cbytes = (size_t)n_radii * sizeof(int64_t) + sizeof(int64_t);
-  Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, fbytes}, {kWorkspace, wbytes}, {kAux, counters + cbytes}, {kSecondField, fbytes},
-                      {kThirdField, fbytes}})) != EDT_OK)
-    return rc;
-  void *const d_labels = st.p[kLabels], *const d_ws = st.p[kWorkspace];
-  float *const S = st.at<float>(kSecondField), *const B = st.at<float>(kThirdField), *const T = st.at<float>(kOut);
-  uint8_t *const mask = st.at<uint8_t>(kAux);
-  int64_t *const d_sizes = reinterpret_cast<int64_t *>(mask + counters);
-  uint32_t *const d_smax = reinterpret_cast<uint32_t *>(d_sizes + n_radii);
-  const auto transform = [&](const void *of, int of_dtype, int border, float *field) {
-    return run_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, border | generic, field, d_ws, wbytes, nullptr);
-  };
-  st.expect(thickness, fbytes);
-  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  if (binary) {
-    if ((rc = launch_is_foreground(dtype, d_labels, mask, voxels, nullptr)) != EDT_OK) return rc;
-    rc = transform(mask, EDT_U8, bb, S);
-  } else {
-    rc = transform(d_labels, dtype, bb, S);
-  }
-  if (rc != EDT_OK || (rc = launch_fill_words(d_sizes, 0u, cbytes / sizeof(uint32_t), nullptr)) != EDT_OK) return rc;
-  // step 0: T = 0 and the mask of the first radius (the default ladder's first radius is its step, whatever Smax turns out to be)
-  std::vector<double> ladder;
-  const double first = radii ? radii[0] : step;
-  double r2 = 0.0, next2 = first * first;
-  if ((rc = launch_thickness_step(S, nullptr, 0.0, 0.0f, next2, T, mask, nullptr, radii ? nullptr : d_smax, voxels, nullptr)) != EDT_OK) return rc;
-  int64_t k = n_radii;
-  if (!radii) {
-    uint32_t bits = 0;
-    EDT_HIP_TRY(hipMemcpy(&bits, d_smax, sizeof(bits), hipMemcpyDeviceToHost));
-    float smax_f;
-    std::memcpy(&smax_f, &bits, sizeof(smax_f));
-    const double smax = (double)smax_f;
-    // the j >= 1 with (j * step)^2 < Smax are a prefix (rounding is monotone): estimate its length, then settle it on the very test
-    const auto below = [&](int64_t j) { const double r = (double)j * step; return r * r < smax; };
-    const double q = std::sqrt(smax) / step;
-    k = q >= 9.0e15 ? INT64_MAX : (int64_t)q;
-    if (k < INT64_MAX) {
-      while (below(k + 1)) ++k;
-      while (k > 0 && !below(k)) --k;
-    }
-    if (k > n_radii) {
-      *n_used = k;
-      set_error("local_thickness: the default ladder has " + std::to_string(k) + " radii, sizes has room for " + std::to_string(n_radii));
-      return EDT_ERR_BAD_ARG;
-    }
-    for (int64_t j = 1; j <= k; ++j) ladder.push_back((double)j * step);
-    radii = ladder.data();
-  }
-  for (int64_t j = 0; j < k; ++j) {
-    r2 = next2;
-    const bool more = j + 1 < k;
-    if (more) next2 = radii[j + 1] * radii[j + 1];
-    if ((rc = transform(mask, EDT_U8, 0, B)) != EDT_OK ||
-        (rc = launch_thickness_step(S, B, r2, (float)radii[j], next2, T, more ? mask : nullptr, d_sizes + j, nullptr, voxels, nullptr)) != EDT_OK)
-      return rc;
-  }
-  if ((rc = st.down(thickness, kOut, fbytes)) != EDT_OK) return rc;
-  if (k > 0 && (rc = st.down(sizes, kAux, (size_t)k * sizeof(int64_t), counters)) != EDT_OK) return rc;
-  *n_used = k;
-  return EDT_OK;
-}
-
-// the medial axis on host buffers (kernel: k_medial_axis, edt_medial.hip; contract: include/edt_hip.h, "medial axis"): labels up
-// once; the mask (under binary), the feature transform, the field (when the radius is wanted) and one step on the device; out and
-// radius down once.  The buffers: the feature planes in kSecondField with the field behind them, the mask in kAux, the radius in
-// kThirdField, one workspace that serves the feature transform and the transform of the field.
-static int medial_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
-                       int flags, double gamma, double ratio, void *out, float *radius) {
-  double g2 = 0.0;
-  float *const w[3] = {&wx, &wy, &wz};
-  bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !out, &empty, [&](After what) -> int {
-    if (what == After::shape) {
-      if (flags & ~(EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY)) {
-        set_error("medial_axis takes EDT_FLAG_BLACK_BORDER and EDT_FLAG_MORPH_BINARY only");
-        return EDT_ERR_UNSUPPORTED;
-      }
-      return medial_check_params(gamma, ratio, "medial_axis", &g2);
-    }
-    if (what == After::pointers) {
-      const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), rbytes = radius ? voxels * sizeof(float) : 0;
-      const auto overlap = [](const void *p, size_t pb, const void *q, size_t qb) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return pb > 0 && qb > 0 && a < b + qb && b < a + pb;
-      };
-      if (overlap(labels, lbytes, out, lbytes) || overlap(labels, lbytes, radius, rbytes) || overlap(out, lbytes, radius, rbytes)) {
-        set_error("medial_axis: out, radius and the labels may not overlap");
-        return EDT_ERR_BAD_ARG;
-      }
-    }
-    return EDT_OK;
-  });
-  if (rc != EDT_OK || empty) return rc;
-  ListedDevice on_listed_device;
-  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const int64_t voxels = sx * sy * sz;
-  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
-  const size_t pbytes = align_up((size_t)voxels * ndim * sizeof(int32_t), 256);
-  const int generic = env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0;
-  const int bb = flags & EDT_FLAG_BLACK_BORDER;
-  const bool binary = (flags & EDT_FLAG_MORPH_BINARY) || dtype == EDT_BOOL;
-  const int of_dtype = binary ? EDT_U8 : dtype;  // what the transforms read: the mask, or the labels
-  size_t wbytes = edt_hip_feature_workspace_bytes(of_dtype, ndim, sx, sy, sz, bb);
-  if (radius) wbytes = std::max(wbytes, edt_hip_workspace_bytes_flags(of_dtype, ndim, sx, sy, sz, generic));
-  Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}, {kSecondField, pbytes + (radius ? fbytes : 0)}})) != EDT_OK)
-    return rc;
-  if (binary && (rc = st.alloc(kAux, (size_t)voxels)) != EDT_OK) return rc;
-  if (radius && (rc = st.alloc(kThirdField, fbytes)) != EDT_OK) return rc;
-  void *const d_labels = st.p[kLabels], *const d_ws = st.p[kWorkspace];
-  int32_t *const planes = st.at<int32_t>(kSecondField);
-  float *const field = radius ? reinterpret_cast<float *>(st.at<char>(kSecondField) + pbytes) : nullptr;
-  float *const d_radius = radius ? st.at<float>(kThirdField) : nullptr;
-  st.expect(out, lbytes);
-  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  const void *of = d_labels;
-  if (binary) {
-    if ((rc = launch_is_foreground(dtype, d_labels, st.at<uint8_t>(kAux), voxels, nullptr)) != EDT_OK) return rc;
-    of = st.p[kAux];
-  }
-  if ((rc = edt_hip_feature_transform_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, bb, planes, d_ws, wbytes, nullptr)) != EDT_OK)
-    return rc;
-  if (radius && (rc = run_device(of, of_dtype, ndim, sx, sy, sz, wx, wy, wz, bb | EDT_FLAG_SQRT | generic, field, d_ws, wbytes, nullptr)) != EDT_OK)
-    return rc;
-  if ((rc = launch_medial_axis(dtype, d_labels, ndim, sx, sy, sz, wx, wy, wz, planes, flags, g2, ratio, st.p[kOut], field, d_radius,
-                               nullptr)) != EDT_OK ||
-      (rc = st.down(out, kOut, lbytes)) != EDT_OK)
-    return rc;
-  return radius ? st.down(radius, kThirdField, fbytes) : EDT_OK;
-}
-
 }  // namespace edt_amd
 
 using namespace edt_amd;
@@ -875,20 +613,103 @@ int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy
       });
 }
 
+// erode / dilate / opening / closing, local thickness and the medial axis on host buffers (contracts: include/edt_hip.h,
+// "morphology", "local thickness", "medial axis"): staging around the one composition of each, its *_device entry point
+// (edt_fieldops.hip) -- labels up once, the call on the pooled buffers with one workspace, the outputs down once.  What the host
+// entries refuse beyond their device siblings: every overlap of their buffers.
 int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                        int op, double radius, int flags, void *output) {
-  return morphology_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, op, radius, flags, output);
+  double r2;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !output, &empty, [&](After what) -> int {
+    if (what == After::shape) return morphology_check_args(op, radius, flags, &r2);
+    if (what == After::pointers) {
+      const size_t bytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
+      if (ranges_overlap(labels, bytes, output, bytes)) { set_error("morphology: the output may not overlap the labels"); return EDT_ERR_BAD_ARG; }
+    }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
+  const size_t wbytes = edt_hip_morphology_workspace_bytes(dtype, ndim, sx, sy, sz, op, flags);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}})) != EDT_OK) return rc;
+  st.expect(output, lbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = edt_hip_morphology_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, op, radius, flags, st.p[kOut], st.p[kWorkspace],
+                                 wbytes, nullptr);
+  return rc != EDT_OK ? rc : st.down(output, kOut, lbytes);
 }
 
+// (the sizes travel in kAux: n_radii int64)
 int edt_hip_local_thickness(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                             int flags, const double *radii, int64_t n_radii, double step, float *thickness, int64_t *sizes,
                             int64_t *n_used) {
-  return thickness_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, radii, n_radii, step, thickness, sizes, n_used);
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !thickness || !n_used || (n_radii > 0 && !sizes), &empty, [&](After what) -> int {
+    if (what == After::shape) return thickness_check_args(flags, radii, n_radii, step);
+    if (what == After::pointers) {
+      const size_t voxels = (size_t)(sx * sy * sz);
+      const size_t lbytes = voxels * dtype_size(dtype), tbytes = voxels * sizeof(float), sbytes = (size_t)n_radii * sizeof(int64_t);
+      if (ranges_overlap(labels, lbytes, thickness, tbytes) || ranges_overlap(labels, lbytes, sizes, sbytes) ||
+          ranges_overlap(thickness, tbytes, sizes, sbytes)) {
+        set_error("local_thickness: thickness, sizes and the labels may not overlap");
+        return EDT_ERR_BAD_ARG;
+      }
+    }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), fbytes = voxels * sizeof(float);
+  const size_t wbytes = edt_hip_local_thickness_workspace_bytes(dtype, ndim, sx, sy, sz, flags);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, fbytes}, {kWorkspace, wbytes}, {kAux, (size_t)n_radii * sizeof(int64_t)}})) != EDT_OK) return rc;
+  st.expect(thickness, fbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = edt_hip_local_thickness_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, flags, radii, n_radii, step, st.at<float>(kOut),
+                                      st.at<int64_t>(kAux), n_used, st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(thickness, kOut, fbytes)) != EDT_OK) return rc;
+  return *n_used > 0 ? st.down(sizes, kAux, (size_t)*n_used * sizeof(int64_t)) : EDT_OK;
 }
 
+// (the radius travels in kSecondField)
 int edt_hip_medial_axis(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                         int flags, double gamma, double ratio, void *out, float *radius) {
-  return medial_host(labels, dtype, ndim, sx, sy, sz, wx, wy, wz, flags, gamma, ratio, out, radius);
+  double g2;
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, w, !labels || !out, &empty, [&](After what) -> int {
+    if (what == After::shape) return medial_check_args(flags, gamma, ratio, &g2);
+    if (what == After::pointers) {
+      const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), rbytes = radius ? voxels * sizeof(float) : 0;
+      if (ranges_overlap(labels, lbytes, out, lbytes) || ranges_overlap(labels, lbytes, radius, rbytes) ||
+          ranges_overlap(out, lbytes, radius, rbytes)) {
+        set_error("medial_axis: out, radius and the labels may not overlap");
+        return EDT_ERR_BAD_ARG;
+      }
+    }
+    return EDT_OK;
+  });
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t voxels = (size_t)(sx * sy * sz), lbytes = voxels * dtype_size(dtype), fbytes = voxels * sizeof(float);
+  const size_t wbytes = edt_hip_medial_axis_workspace_bytes(dtype, ndim, sx, sy, sz, flags, radius != nullptr);
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, lbytes}, {kWorkspace, wbytes}})) != EDT_OK) return rc;
+  if (radius && (rc = st.alloc(kSecondField, fbytes)) != EDT_OK) return rc;
+  st.expect(out, lbytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  rc = edt_hip_medial_axis_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, flags, gamma, ratio, st.p[kOut],
+                                  radius ? st.at<float>(kSecondField) : nullptr, st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(out, kOut, lbytes)) != EDT_OK) return rc;
+  return radius ? st.down(radius, kSecondField, fbytes) : EDT_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // edt_medial.hip -- the integer medial axis of every label at once (include/edt_hip.h, "medial axis"): one streaming stencil over
 // the feature planes of edt_hip_feature_transform_device and the labels, and its device entry point.  The composition -- mask,
-// feature transform, field, step -- lives one layer up: edt_hip_medial_axis (edt_host.hip) and edt/device.py.
+// feature transform, field, step -- lives one layer up: edt_hip_medial_axis_device (edt_fieldops.hip).
 //
 // Form.  A WAVE owns a tile of 62 x kRows x kMarch voxels (x, y, z) and marches along z; a workgroup is four such waves on
 // consecutive tiles.  The 64 lanes sit on 64 consecutive x, so the x neighbours of the inner 62 are the adjacent lanes' registers

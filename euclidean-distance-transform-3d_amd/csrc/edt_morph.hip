@@ -1,7 +1,7 @@
 // edt_morph.hip -- the two streaming kernels of the morphology operations (include/edt_hip.h, "morphology") and their device
 // entry points: the mask labels != 0, and the select that turns a squared-distance field into an eroded / opened / closed label
 // volume (or into the mask of the voxels that did not pass).  The composition -- which transform feeds which select -- lives one
-// layer up: edt_hip_morphology (edt_host.hip) and edt/device.py own the field and the mask.  Further down, in the same form: the
+// layer up: edt_hip_morphology_device (edt_fieldops.hip) carves the field and the mask.  Further down, in the same form: the
 // step kernel of local thickness (include/edt_hip.h, "local thickness") and its device entry point.
 //
 // Form.  Both kernels move 2 to 29 bytes per voxel and compute next to nothing: a fixed grid of 2048 workgroups of 256 threads

@@ -117,10 +117,16 @@ SIGNATURES = {
     "edt_hip_dust": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp]),
     "edt_hip_is_foreground_device": (_i, [_vp, _i, _vp, _i64, _vp]),
     "edt_hip_morph_select_device": (_i, [_vp, _vp, _i, _vp, _d, _i, _vp, _vp, _i64, _vp]),
+    "edt_hip_morphology_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64, _i, _i]),
+    "edt_hip_morphology_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _i, _vp, _vp, _sz, _vp]),
     "edt_hip_morphology": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _i, _vp]),
     "edt_hip_thickness_step_device": (_i, [_vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "edt_hip_local_thickness_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64, _i]),
+    "edt_hip_local_thickness_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp, _i64, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_local_thickness": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _vp, _i64, _d, _vp, _vp, _vp]),
     "edt_hip_medial_axis_step_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    "edt_hip_medial_axis_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64, _i, _i]),
+    "edt_hip_medial_axis_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_medial_axis": (_i, [_vp, _i, _i, _i64, _i64, _i64, _f, _f, _f, _i, _d, _d, _vp, _vp]),
 }
 

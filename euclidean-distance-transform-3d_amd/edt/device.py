@@ -508,21 +508,24 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
     return LabelStats(keys, counts, mx, argmax, lo, hi)
 
 
-_cc_workspaces: dict = {}
-_fh_workspaces: dict = {}      # fill_holes and dust: the same bytes (edt_hip_dust_workspace_bytes), one cache
+_workspaces: dict = {}         # query name -> {(bytes, device, stream): scratch}
 
 
-def _label_op_workspace(cache, query, ext, code, nd, device, who) -> torch.Tensor:
-    # one scratch buffer per shape and stream (a workspace is only ever used on the stream it was allocated for); at most 9 are
-    # kept per cache, and the one cached longest ago makes room for a new one
-    key = (tuple(ext), code, str(device), torch.cuda.current_stream(device).cuda_stream)
+def _workspace(query, *query_args, device) -> torch.Tensor:
+    """The scratch of one library call: ``query(*query_args)`` bytes on ``device``.  One buffer per query name, byte count, device
+    and current stream (a workspace is only ever used on the stream it was allocated for; calls that need the same bytes share
+    it, whatever their shape or dtype: every call initialises what it reads).  At most 9 are kept per query name, and the one
+    cached longest ago makes room for a new one."""
+    nbytes = int(getattr(_lib.load(), query)(*query_args))
+    if nbytes == 0:
+        raise ValueError(f"{query}{query_args} is 0: this dtype, shape (at most 2^31 - 1 voxels for the label operations) or "
+                         "flags is not served")
+    cache = _workspaces.setdefault(query, {})
+    key = (nbytes, str(device), torch.cuda.current_stream(device).cuda_stream)
     if key not in cache:
-        nbytes = getattr(_lib.load(), query)(code, nd, *ext)
-        if nbytes == 0:
-            raise ValueError(f"{who}: a volume of {tuple(ext[:nd])} is not served (at most 2^31 - 1 voxels)")
         if len(cache) > 8:
             del cache[next(iter(cache))]
-        cache[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
     return cache[key]
 
 
@@ -557,8 +560,7 @@ def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
         return out, torch.zeros((), dtype=torch.int64, device=labels.device)
     n = torch.empty((), dtype=torch.int64, device=labels.device)
     labels = labels.contiguous()
-    ws = _label_op_workspace(_cc_workspaces, "edt_hip_components_workspace_bytes", ext, code, nd, labels.device,
-                             "connected_components")
+    ws = _workspace("edt_hip_components_workspace_bytes", code, nd, *ext, device=labels.device)
     _lib.check(_lib.load().edt_hip_connected_components_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, _vp(out),
                                                                _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
@@ -580,7 +582,7 @@ def fill_holes(labels: torch.Tensor, connectivity=None, binary=False):
     labels = labels.contiguous()
     out = torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
     n = torch.empty((), dtype=torch.int64, device=labels.device)
-    ws = _label_op_workspace(_fh_workspaces, "edt_hip_fill_holes_workspace_bytes", ext, code, nd, labels.device, "fill_holes")
+    ws = _workspace("edt_hip_fill_holes_workspace_bytes", code, nd, *ext, device=labels.device)
     _lib.check(_lib.load().edt_hip_fill_holes_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, _vp(out), _vp(n),
                                                      _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
@@ -607,31 +609,10 @@ def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, inver
     labels = labels.contiguous()
     out = labels if in_place else torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
     counts = torch.empty(3, dtype=torch.int64, device=labels.device)
-    ws = _label_op_workspace(_fh_workspaces, "edt_hip_fill_holes_workspace_bytes", ext, code, nd, labels.device, "dust")
+    ws = _workspace("edt_hip_fill_holes_workspace_bytes", code, nd, *ext, device=labels.device)
     _lib.check(_lib.load().edt_hip_dust_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, lo, hi, 1 if invert else 0,
                                                _vp(out), _vp(counts), _vp(ws), ws.numel(), _stream_ptr()))
     return out, counts
-
-
-_morph_buffers: dict = {}
-
-
-def _morph_scratch(labels) -> tuple:
-    """The fp32 field and the uint8 mask of a morphology call: one pair per shape and stream, as the plans' scratch (at most
-    9 pairs are kept; the one cached longest ago makes room for a new one)."""
-    key = (tuple(labels.shape), str(labels.device), torch.cuda.current_stream(labels.device).cuda_stream)
-    if key not in _morph_buffers:
-        if len(_morph_buffers) > 8:
-            del _morph_buffers[next(iter(_morph_buffers))]
-        _morph_buffers[key] = (torch.empty(labels.shape, dtype=torch.float32, device=labels.device),
-                               torch.empty(labels.shape, dtype=torch.uint8, device=labels.device))
-    return _morph_buffers[key]
-
-
-def _is_foreground(labels, mask):
-    _lib.check(_lib.load().edt_hip_is_foreground_device(_vp(labels), dtype_code(labels.dtype), _vp(mask), labels.numel(),
-                                                        _stream_ptr()))
-    return mask
 
 
 def _morph_select(code, values, field, radius, rule, out=None, mask=None, guard=None):
@@ -641,13 +622,6 @@ def _morph_select(code, values, field, radius, rule, out=None, mask=None, guard=
         None if out is None else _vp(out), None if mask is None else _vp(mask), field.numel(), _stream_ptr()))
 
 
-def _eroded_field(labels, nd, ext, w, black_border, binary, field, mask):
-    """S of the contract: the squared transform of the labels, or of the mask labels != 0 (bool: always)"""
-    if binary or labels.dtype == torch.bool:
-        return _plan_for(ext[:nd], _lib.U8, labels.device).run(_is_foreground(labels, mask), w[:nd], black_border, out=field)
-    return _plan_for(ext[:nd], dtype_code(labels.dtype), labels.device).run(labels, w[:nd], black_border, out=field)
-
-
 def _morph_input(labels, radius, anisotropy, who, in_place=False, inf_allowed=False):
     from . import _morph_radius
     raw = as_device_tensor(labels)
@@ -655,27 +629,32 @@ def _morph_input(labels, radius, anisotropy, who, in_place=False, inf_allowed=Fa
     if in_place and not raw.is_contiguous():
         raise ValueError(f"{who}: in_place needs a contiguous tensor")
     labels, nd, ext, w = _ft_tensor(raw, anisotropy, who)
-    dtype_code(labels.dtype)
-    return labels, nd, ext, w, r
+    return labels, nd, dtype_code(labels.dtype), ext, w, r
+
+
+def _morphology(who, op, labels, radius, anisotropy, flags=0, in_place=False):
+    """One call of edt_hip_morphology_device on the current stream, on the cached workspace of its size."""
+    labels, nd, code, ext, w, r = _morph_input(labels, radius, anisotropy, who, in_place)
+    if labels.numel() == 0:
+        return labels if in_place else labels.clone()
+    ws = _workspace("edt_hip_morphology_workspace_bytes", code, nd, *ext, op, flags, device=labels.device)
+    out = labels if in_place else torch.empty_like(labels)
+    _lib.check(_lib.load().edt_hip_morphology_device(_vp(labels), code, nd, *ext, *w, op, r, flags, _vp(out), _vp(ws), ws.numel(),
+                                                     _stream_ptr()))
+    return out
 
 
 def erode(labels: torch.Tensor, radius=1.0, anisotropy=None, black_border=False, binary=False, in_place=False) -> torch.Tensor:
     """:func:`edt.erode` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
     include/edt_hip.h, "morphology"): one transform and one streaming select on the current stream, nothing read back.
     ``in_place=True`` writes the result into the (contiguous) input tensor and returns it."""
-    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "erode", in_place)
-    if labels.numel() == 0:
-        return labels if in_place else labels.clone()
-    field, mask = _morph_scratch(labels)
-    _eroded_field(labels, nd, ext, w, black_border, binary, field, mask)
-    out = labels if in_place else torch.empty_like(labels)
-    _morph_select(dtype_code(labels.dtype), labels, field, r, _lib.MORPH_FARTHER, out=out)
-    return out
+    from . import _morph_flags
+    return _morphology("erode", _lib.MORPH_ERODE, labels, radius, anisotropy, _morph_flags(black_border, binary), in_place)
 
 
 def dilate(labels: torch.Tensor, radius=1.0, anisotropy=None) -> torch.Tensor:
     """:func:`edt.dilate` on a device array: exactly :func:`expand_labels`."""
-    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "dilate", inf_allowed=True)
+    labels, nd, code, ext, w, r = _morph_input(labels, radius, anisotropy, "dilate", inf_allowed=True)
     return expand_labels(labels, r, anisotropy)
 
 
@@ -683,140 +662,57 @@ def opening(labels: torch.Tensor, radius=1.0, anisotropy=None, black_border=Fals
     """:func:`edt.opening` on a device array: the transform of the labels, the mask of what the erosion removes, its
     binary transform, and the select of the voxels within ``radius`` of what survived -- two transforms and two streaming
     kernels on the current stream.  ``in_place=True`` writes the result into the (contiguous) input tensor and returns it."""
-    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "opening", in_place)
-    if labels.numel() == 0:
-        return labels if in_place else labels.clone()
-    field, mask = _morph_scratch(labels)
-    _eroded_field(labels, nd, ext, w, black_border, binary, field, mask)
-    _morph_select(_lib.U8, None, field, r, _lib.MORPH_FARTHER, mask=mask)
-    _plan_for(ext[:nd], _lib.U8, labels.device).run(mask, w[:nd], False, out=field)
-    out = labels if in_place else torch.empty_like(labels)
-    _morph_select(dtype_code(labels.dtype), labels, field, r, _lib.MORPH_WITHIN, out=out)
-    return out
+    from . import _morph_flags
+    return _morphology("opening", _lib.MORPH_OPEN, labels, radius, anisotropy, _morph_flags(black_border, binary), in_place)
 
 
 def closing(labels: torch.Tensor, radius=1.0, anisotropy=None) -> torch.Tensor:
     """:func:`edt.closing` on a device array: :func:`expand_labels`, the binary transform of what it left empty, and the
     select that keeps the input's voxels and the new voxels farther than ``radius`` from the emptiness."""
-    labels, nd, ext, w, r = _morph_input(labels, radius, anisotropy, "closing")
-    if labels.numel() == 0:
-        return labels.clone()
-    out = expand_labels(labels, r, anisotropy)
-    field, mask = _morph_scratch(labels)
-    _plan_for(ext[:nd], _lib.U8, labels.device).run(_is_foreground(out, mask), w[:nd], False, out=field)
-    _morph_select(dtype_code(labels.dtype), out, field, r, _lib.MORPH_FARTHER, out=out, guard=labels)
-    return out
-
-
-_thickness_buffers: dict = {}
-
-
-def _thickness_scratch(labels) -> tuple:
-    """S, B (fp32) and the uint8 mask of a local_thickness call: one triple per shape and stream, kept as :func:`_morph_scratch`
-    keeps its pairs (at most 9; the one cached longest ago makes room for a new one)."""
-    key = (tuple(labels.shape), str(labels.device), torch.cuda.current_stream(labels.device).cuda_stream)
-    if key not in _thickness_buffers:
-        if len(_thickness_buffers) > 8:
-            del _thickness_buffers[next(iter(_thickness_buffers))]
-        _thickness_buffers[key] = (torch.empty(labels.shape, dtype=torch.float32, device=labels.device),
-                                   torch.empty(labels.shape, dtype=torch.float32, device=labels.device),
-                                   torch.empty(labels.shape, dtype=torch.uint8, device=labels.device))
-    return _thickness_buffers[key]
-
-
-def _thickness_step(S, B, radius, next_radius, T, mask=None, size=None, smax=None):
-    """edt_hip_thickness_step_device over ``S.numel()`` voxels; ``next_radius=None``: there is none"""
-    _lib.check(_lib.load().edt_hip_thickness_step_device(
-        _vp(S), None if B is None else _vp(B), radius, -1.0 if next_radius is None else next_radius, _vp(T),
-        None if mask is None else _vp(mask), None if size is None else _vp(size), None if smax is None else _vp(smax), S.numel(),
-        _stream_ptr()))
+    return _morphology("closing", _lib.MORPH_CLOSE, labels, radius, anisotropy)
 
 
 def local_thickness(labels: torch.Tensor, radii=None, anisotropy=None, black_border=False, binary=False, return_sizes=False):
     """:func:`edt.local_thickness` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
-    include/edt_hip.h, "local thickness"): the transform of the labels once, then per radius the binary transform of the mask
-    the step before left and one streaming step, on a cached (S, B, mask) triple per shape and stream.  Returns the float32
-    thickness, a new tensor; with ``return_sizes=True`` the pair ``(thickness, ThicknessSizes(radii, voxels))`` with ``radii`` a
-    float64 numpy array (the radii used) and ``voxels`` an int64 DEVICE tensor.  With explicit ``radii`` the call only enqueues
-    kernels on the current stream -- nothing is read back, and it can be captured into a graph.  ``radii=None`` SYNCHRONISES
-    once: the largest finite squared distance (4 bytes) is read back to build the ladder."""
-    from . import ThicknessSizes, _thickness_radii
+    include/edt_hip.h, "local thickness"): one call of edt_hip_local_thickness_device on the cached workspace of its size -- the
+    transform of the labels once, then per radius the binary transform of the mask the step before left and one streaming
+    step.  Returns the float32 thickness, a new tensor; with ``return_sizes=True`` the pair ``(thickness, ThicknessSizes(radii,
+    voxels))`` with ``radii`` a float64 numpy array (the radii used) and ``voxels`` an int64 DEVICE tensor.  With explicit
+    ``radii`` the call only enqueues kernels on the current stream -- nothing is read back, and it can be captured into a graph.
+    ``radii=None`` SYNCHRONISES once: the largest finite squared distance (4 bytes) is read back to build the ladder; on a
+    stream that is being captured it is refused (``EdtHipError``)."""
+    from . import ThicknessSizes, _ladder_room, _morph_flags, _thickness_radii
     raw = as_device_tensor(labels)
     r = None if radii is None else _thickness_radii(radii)
     labels, nd, ext, w = _ft_tensor(raw, anisotropy, "local_thickness")
-    dtype_code(labels.dtype)
+    code = dtype_code(labels.dtype)
     if labels.numel() == 0:
         T = torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)
         used = np.zeros(0, dtype=np.float64) if r is None else r
         return (T, ThicknessSizes(used, torch.zeros(used.size, dtype=torch.int64, device=labels.device))) if return_sizes else T
-    S, B, mask = _thickness_scratch(labels)
-    _eroded_field(labels, nd, ext, w, black_border, binary, S, mask)
+    step, room = (0.0, r.size) if r is not None else _ladder_room(ext[:nd], w[:nd])
+    flags = _morph_flags(black_border, binary)
+    ws = _workspace("edt_hip_local_thickness_workspace_bytes", code, nd, *ext, flags, device=labels.device)
     T = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
-    # (the counters are zeroed by fill kernels of the stream: a captured memset does not replay, DESIGN.md 13.3)
-    if r is None:
-        step = min(abs(v) for v in w[:nd])
-        smax = torch.empty(1, dtype=torch.int32, device=labels.device).fill_(0)
-        _thickness_step(S, None, 0.0, step, T, mask=mask, smax=smax)
-        top = float(np.array([smax.item()], dtype=np.int32).view(np.float32)[0])     # the one synchronisation
-        below = lambda j: (float(j) * step) * (float(j) * step) < top  # noqa: E731  (the header's test, in its arithmetic)
-        k = int(np.sqrt(top) / step)
-        while below(k + 1):
-            k += 1
-        while k > 0 and not below(k):
-            k -= 1
-        r = np.arange(1, k + 1, dtype=np.float64) * step
-    else:
-        _thickness_step(S, None, 0.0, float(r[0]), T, mask=mask)
-    sizes = torch.empty(r.size, dtype=torch.int64, device=labels.device).fill_(0)
-    plan = _plan_for(ext[:nd], _lib.U8, labels.device) if r.size else None
-    for j in range(r.size):
-        more = j + 1 < r.size
-        plan.run(mask, w[:nd], False, out=B)
-        _thickness_step(S, B, float(r[j]), float(r[j + 1]) if more else None, T, mask=mask if more else None, size=sizes[j:])
-    return (T, ThicknessSizes(r, sizes)) if return_sizes else T
-
-
-_medial_buffers: dict = {}
-
-
-def _medial_scratch(labels, nd, ext, code, flags, binary, want_field) -> dict:
-    """The scratch of a medial_axis call: the feature planes and the feature transform's workspace, plus the uint8 mask under
-    binary and the fp32 field where the radius is wanted (each allocated by the first call that needs it): one set per shape,
-    transformed dtype and stream, kept as :func:`_morph_scratch` keeps its pairs (at most 9; the one cached longest ago makes
-    room for a new one)."""
-    key = (tuple(labels.shape), code, str(labels.device), torch.cuda.current_stream(labels.device).cuda_stream)
-    if key not in _medial_buffers:
-        nbytes = _lib.load().edt_hip_feature_workspace_bytes(code, nd, *ext, flags & _lib.FLAG_BLACK_BORDER)
-        if nbytes == 0:
-            _lib.check(-2)
-        if len(_medial_buffers) > 8:
-            del _medial_buffers[next(iter(_medial_buffers))]
-        _medial_buffers[key] = {"planes": torch.empty((nd,) + tuple(labels.shape), dtype=torch.int32, device=labels.device),
-                                "ws": torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)}
-    s = _medial_buffers[key]
-    if binary and "mask" not in s:
-        s["mask"] = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
-    if want_field and "field" not in s:
-        s["field"] = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
-    return s
-
-
-def _medial_step(labels, nd, ext, w, planes, flags, gamma, ratio, out, field=None, radius=None):
-    """edt_hip_medial_axis_step_device on the x, y, z feature planes ``planes`` of ``labels``"""
-    _lib.check(_lib.load().edt_hip_medial_axis_step_device(
-        _vp(labels), dtype_code(labels.dtype), nd, *ext, *w, _vp(planes), flags, gamma, ratio, _vp(out),
-        None if field is None else _vp(field), None if radius is None else _vp(radius), _stream_ptr()))
-    return out
+    sizes = torch.empty(room, dtype=torch.int64, device=labels.device)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().edt_hip_local_thickness_device(
+        _vp(labels), code, nd, *ext, *w, flags, None if r is None else ctypes.c_void_p(r.ctypes.data), room, step, _vp(T), _vp(sizes),
+        ctypes.byref(n), _vp(ws), ws.numel(), _stream_ptr()))
+    if not return_sizes:
+        return T
+    k = int(n.value)
+    return T, ThicknessSizes(r if r is not None else np.arange(1, k + 1, dtype=np.float64) * step, sizes[:k])
 
 
 def medial_axis(labels: torch.Tensor, gamma=None, min_angle=0.0, anisotropy=None, black_border=False, binary=False,
                 return_distance=False):
     """:func:`edt.medial_axis` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
-    include/edt_hip.h, "medial axis"): the mask under binary, the feature transform, the distance transform where the radius
-    is wanted, and one streaming stencil, all enqueued on the current stream -- nothing is read back.  The scratch (feature
-    planes, the transform's workspace, mask and field) is cached per shape and stream: a second call of one shape allocates
-    only what it returns.  Returns a new tensor of the labels' dtype and shape; with ``return_distance=True`` the pair
-    ``(axis, distance)``, distance float32."""
+    include/edt_hip.h, "medial axis"): one call of edt_hip_medial_axis_device -- the mask under binary, the feature transform,
+    the distance transform where the radius is wanted, and one streaming stencil, all enqueued on the current stream; nothing is
+    read back.  The workspace is cached by its size and stream: a second call of one shape allocates only what it returns.
+    Returns a new tensor of the labels' dtype and shape; with ``return_distance=True`` the pair ``(axis, distance)``, distance
+    float32."""
     from . import _medial_gamma, _medial_ratio, _morph_flags
     raw = as_device_tensor(labels)
     ratio = _medial_ratio(min_angle)
@@ -826,19 +722,13 @@ def medial_axis(labels: torch.Tensor, gamma=None, min_angle=0.0, anisotropy=None
     if labels.numel() == 0:
         return (labels.clone(), torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)) if return_distance else labels.clone()
     flags = _morph_flags(black_border, binary)
-    binary = bool(binary) or labels.dtype == torch.bool
-    of_code = _lib.U8 if binary else code
-    s = _medial_scratch(labels, nd, ext, of_code, flags, binary, return_distance)
-    of = _is_foreground(labels, s["mask"]) if binary else labels
-    _lib.check(_lib.load().edt_hip_feature_transform_device(
-        _vp(of), of_code, nd, *ext, *w, flags & _lib.FLAG_BLACK_BORDER, _vp(s["planes"]), _vp(s["ws"]), s["ws"].numel(), _stream_ptr()))
+    ws = _workspace("edt_hip_medial_axis_workspace_bytes", code, nd, *ext, flags, 1 if return_distance else 0, device=labels.device)
     out = torch.empty_like(labels)
-    if not return_distance:
-        return _medial_step(labels, nd, ext, w, s["planes"], flags, g, ratio, out)
-    _plan_for(ext[:nd], of_code, labels.device).run(of, w[:nd], black_border, sqrt=True, out=s["field"])
-    radius = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
-    _medial_step(labels, nd, ext, w, s["planes"], flags, g, ratio, out, s["field"], radius)
-    return out, radius
+    radius = torch.empty(labels.shape, dtype=torch.float32, device=labels.device) if return_distance else None
+    _lib.check(_lib.load().edt_hip_medial_axis_device(
+        _vp(labels), code, nd, *ext, *w, flags, g, ratio, _vp(out), None if radius is None else _vp(radius), _vp(ws), ws.numel(),
+        _stream_ptr()))
+    return (out, radius) if return_distance else out
 
 
 def pass_times():

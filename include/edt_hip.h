@@ -621,12 +621,27 @@ int edt_hip_is_foreground_device(const void *d_labels, int dtype, uint8_t *d_mas
 int edt_hip_morph_select_device(const void *d_values, const void *d_guard, int dtype, const float *d_field, double radius,
                                 int rule, void *d_out, uint8_t *d_mask, int64_t count, void *stream);
 
-/* The four operations on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
- * edt_hip_set_devices on the first listed device): labels up once, output down once, everything between on the device.
- * op: EDT_MORPH_*.  ndim in {1,2,3}, unused extents 1.  `output` has the labels' dtype and may not overlap `labels`.
- * flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY for erode / opening; 0 for dilate / closing.  Refused before any device
- * work: a bad op, a bad radius (EDT_ERR_BAD_ARG); a flag the op does not take (EDT_ERR_UNSUPPORTED); bad voxel sizes; NULL
- * pointers and overlapping buffers (EDT_ERR_BAD_ARG).  An empty volume is EDT_OK with nothing touched. */
+/* Scratch of edt_hip_morphology_device, in this order, each part rounded up to 256 bytes: the fp32 field (4 bytes per voxel), the
+ * uint8 mask (1 byte per voxel), then the scratch of the operation's transforms -- the largest any of its steps needs:
+ * edt_hip_workspace_bytes_flags of EDT_U8, of the labels' dtype too where erode / opening measure the labels themselves, and
+ * edt_hip_expand_labels_workspace_bytes for closing.  Dilate is expand_labels and needs only that scratch.  0 for a bad dtype,
+ * shape or op, or flags the op does not take. */
+size_t edt_hip_morphology_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int op, int flags);
+/* The four operations on device-resident data, x fastest.  op: EDT_MORPH_*.  ndim in {1,2,3}, unused extents 1.  d_out has the
+ * labels' dtype.  flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY for erode / opening; 0 for dilate / closing.  Refused
+ * before any device work, in this order: a bad dtype or shape, a bad op (EDT_ERR_BAD_ARG); a flag the op does not take
+ * (EDT_ERR_UNSUPPORTED); a bad radius, bad voxel sizes; for a volume that is not empty NULL pointers, d_out == d_labels for
+ * dilate and closing, a missing or too small workspace, a workspace that is not 256-byte aligned (EDT_ERR_BAD_ARG).
+ * d_out == d_labels is allowed for erode and opening (in place: the last step reads and writes voxel i only, and the transforms
+ * have finished with the labels); any other overlap is the caller's error.  Enqueue-only on `stream`: no allocation, no
+ * synchronisation; the call initialises whatever it reads of its scratch (a reused workspace needs no memset).  An empty
+ * volume is EDT_OK with nothing touched. */
+int edt_hip_morphology_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                              float wz, int op, double radius, int flags, void *d_out, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, edt_hip_morphology_device, output down once.  Refusals as
+ * above, in the same order; `output` may not overlap `labels` at all (EDT_ERR_BAD_ARG), for any op. */
 int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                        int op, double radius, int flags, void *output);
 
@@ -671,19 +686,35 @@ int edt_hip_morphology(const void *labels, int dtype, int ndim, int64_t sx, int6
 int edt_hip_thickness_step_device(const float *d_S, const float *d_B, double radius, double next_radius, float *d_T,
                                   uint8_t *d_mask, int64_t *d_size, uint32_t *d_smax_bits, int64_t count, void *stream);
 
-/* The whole operation on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
- * edt_hip_set_devices on the first listed device): labels up once, thickness and sizes down once, everything between on the
- * device -- S once, then per radius one binary transform and one step.
+/* Scratch of edt_hip_local_thickness_device, in this order, each part rounded up to 256 bytes: S and B (fp32, 4 bytes per voxel
+ * each), the uint8 mask (1 byte per voxel), the word of Smax, then the scratch of the transforms: edt_hip_workspace_bytes_flags
+ * of EDT_U8, and of the labels' dtype where S is measured on the labels themselves.  0 for a bad dtype, shape or flags. */
+size_t edt_hip_local_thickness_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags);
+/* The whole operation on device-resident data, x fastest: S once, then per radius one binary transform and one step.
  * ndim in {1,2,3}, unused extents 1.  flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY, anything else is EDT_ERR_UNSUPPORTED.
- * radii != NULL: n_radii >= 1 radii as above; `step` is ignored; sizes has n_radii entries; *n_used = n_radii.
- * radii == NULL: the default ladder with `step` (finite, > 0, finite square); Smax is read back once (4 bytes); n_radii (>= 0)
- *   is the room in sizes (sizes may be NULL if it is 0); *n_used = the ladder's length and sizes[0 .. *n_used) are written.  A
- *   ladder longer than n_radii is EDT_ERR_BAD_ARG after the first transform: *n_used then holds the length it needs and
- *   nothing else is written.  r_j of that ladder is j * step.
- * thickness: voxels floats.  Refused with EDT_ERR_BAD_ARG before any device work: radii that are not strictly ascending, not
- * positive, not finite or whose square overflows; an explicit list with n_radii < 1; n_radii < 0; a bad step for the default
- * ladder; bad voxel sizes; NULL pointers (thickness, n_used, labels; sizes where it has entries); thickness or sizes
- * overlapping the labels or each other.  An empty volume is EDT_OK with nothing touched. */
+ * radii and n_used are HOST pointers; d_thickness (voxels floats) and d_sizes (int64) are on the device.
+ * radii != NULL: n_radii >= 1 radii as above; `step` is ignored; d_sizes has n_radii entries; *n_used = n_radii.  The call is
+ *   enqueue-only on `stream`: no allocation, no synchronisation, and it can be captured into a graph.
+ * radii == NULL: the default ladder with `step` (finite, > 0, finite square).  The call SYNCHRONISES `stream` once, after the
+ *   first transform, to read Smax back (4 bytes); a stream that is being captured is EDT_ERR_UNSUPPORTED before any device
+ *   work.  n_radii (>= 0) is the room in d_sizes (d_sizes may be NULL if it is 0); *n_used = the ladder's length and
+ *   d_sizes[0 .. *n_used) hold the sizes.  A ladder longer than n_radii is EDT_ERR_BAD_ARG after the first transform: *n_used
+ *   then holds the length it needs and neither output holds a result.  r_j of that ladder is j * step.
+ * d_sizes[0 .. n_radii) and the word of Smax are zeroed on the stream by kernels of the call (a replayed graph counts from
+ * zero); the call initialises whatever it reads of its scratch (a reused workspace needs no memset).
+ * Refused before any device work, in this order: a bad dtype or shape (EDT_ERR_BAD_ARG); flags (EDT_ERR_UNSUPPORTED); radii that
+ * are not strictly ascending, not positive, not finite or whose square overflows, an explicit list with n_radii < 1, n_radii < 0,
+ * a bad step for the default ladder; bad voxel sizes; for a volume that is not empty NULL pointers (d_labels, d_thickness,
+ * n_used; d_sizes where it has entries), a missing or too small workspace, a workspace that is not 256-byte aligned
+ * (EDT_ERR_BAD_ARG).  The outputs may not overlap the labels, the workspace or each other: the caller's error.  An empty volume
+ * is EDT_OK with nothing touched. */
+int edt_hip_local_thickness_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                                   float wz, int flags, const double *radii, int64_t n_radii, double step, float *d_thickness,
+                                   int64_t *d_sizes, int64_t *n_used, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, edt_hip_local_thickness_device, thickness and
+ * sizes[0 .. *n_used) down once.  Refusals as above, in the same order; thickness or sizes overlapping the labels or each other
+ * is EDT_ERR_BAD_ARG.  After a ladder longer than n_radii nothing but *n_used is written. */
 int edt_hip_local_thickness(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
                             float wz, int flags, const double *radii, int64_t n_radii, double step, float *thickness,
                             int64_t *sizes, int64_t *n_used);
@@ -736,14 +767,28 @@ int edt_hip_medial_axis_step_device(const void *d_labels, int dtype, int ndim, i
                                     float wz, const int32_t *d_features, int flags, double gamma, double ratio, void *d_out,
                                     const float *d_field, float *d_radius, void *stream);
 
-/* The whole operation on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
- * edt_hip_set_devices on the first listed device): labels up once; on the device the mask (under binary), the feature transform,
- * the field when `radius` is wanted, and one step; out -- and radius if it is not NULL -- down once.
- * The field of `radius` is what edt_hip_edt3d / edt_hip_edt2d / the 1-D transform with sqrt write for the same labels (under
- * binary: for the mask), voxel sizes and border: the distance to the nearest voxel of another label, the radius function.
+/* Scratch of edt_hip_medial_axis_device, in this order, each part rounded up to 256 bytes: the ndim feature planes (int32, 4 bytes
+ * per voxel each), the uint8 mask under binary (1 byte per voxel), the fp32 field with with_radius != 0 (4 bytes per voxel), then
+ * the scratch of the transforms of what they read (the mask under binary, else the labels): edt_hip_feature_workspace_bytes, and
+ * with_radius edt_hip_workspace_bytes_flags too, whichever is larger.  0 for a bad dtype, shape or flags. */
+size_t edt_hip_medial_axis_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags, int with_radius);
+/* The whole operation on device-resident data, x fastest: the mask (under binary), the feature transform, the field when
+ * d_radius is wanted (not NULL: the workspace is then sized with with_radius = 1), and one step.
+ * The field of d_radius is what edt_hip_edtsq_device with EDT_FLAG_SQRT writes for the same labels (under binary: for the mask),
+ * voxel sizes and border: the distance to the nearest voxel of another label, the radius function.
  * ndim in {1,2,3}, unused extents 1.  flags: EDT_FLAG_BLACK_BORDER | EDT_FLAG_MORPH_BINARY, anything else is EDT_ERR_UNSUPPORTED.
- * `out` has the labels' dtype.  Refused with EDT_ERR_BAD_ARG before any device work: what the step refuses; NULL labels or out;
- * out or radius overlapping the labels or each other.  An empty volume is EDT_OK with nothing touched. */
+ * d_out has the labels' dtype.  Refused before any device work, in this order: a bad dtype or shape (EDT_ERR_BAD_ARG); flags
+ * (EDT_ERR_UNSUPPORTED); gamma or ratio as the step refuses them; bad voxel sizes; for a volume that is not empty NULL d_labels or
+ * d_out, d_out == d_labels, a missing or too small workspace, a workspace that is not 256-byte aligned (EDT_ERR_BAD_ARG).  Any
+ * other overlap is the caller's error.  Enqueue-only on `stream`: no allocation, no synchronisation; the call initialises
+ * whatever it reads of its scratch (a reused workspace needs no memset).  An empty volume is EDT_OK with nothing touched. */
+int edt_hip_medial_axis_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
+                               float wz, int flags, double gamma, double ratio, void *d_out, float *d_radius, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels up once, edt_hip_medial_axis_device, out -- and radius if it is not
+ * NULL -- down once.  Refusals as above, in the same order; out or radius overlapping the labels or each other is
+ * EDT_ERR_BAD_ARG. */
 int edt_hip_medial_axis(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
                         int flags, double gamma, double ratio, void *out, float *radius);
 

@@ -236,13 +236,16 @@ def test_two_calls_of_one_shape_share_the_scratch_and_a_dirty_scratch_does_not_s
     shape = (9, 11, 70)
     a, b = labels_of(shape, np.int32, seed=31), labels_of(shape, np.int32, seed=32)
     ta, tb = to_device(a), to_device(b)
-    device._medial_buffers.clear()
+    query = "edt_hip_medial_axis_workspace_bytes"
+    cache = device._workspaces.setdefault(query, {})
+    cache.clear()
     kw = dict(black_border=True, return_distance=True, binary=True)
     first, first_radius = device.medial_axis(ta, **kw)
-    assert len(device._medial_buffers) == 1
-    scratch = next(iter(device._medial_buffers.values()))
-    assert set(scratch) == {"planes", "ws", "mask", "field"}
-    where = {k: v.data_ptr() for k, v in scratch.items()}
+    assert len(cache) == 1
+    scratch = next(iter(cache.values()))
+    ext = shape[::-1]
+    assert scratch.numel() == getattr(lib(), query)(2, 3, *ext, BLACK_BORDER | MORPH_BINARY, 1) > 4 * 4 * ta.numel()
+    where = scratch.data_ptr()
     torch.cuda.synchronize()
     before = torch.cuda.memory_allocated()
     other, _ = device.medial_axis(tb, **kw)
@@ -250,16 +253,15 @@ def test_two_calls_of_one_shape_share_the_scratch_and_a_dirty_scratch_does_not_s
     torch.cuda.synchronize()
     # a second call of one shape allocates only what it returns: an axis and a radius each
     assert torch.cuda.memory_allocated() - before <= 4 * (ta.numel() * 4 + 2048)
-    assert len(device._medial_buffers) == 1 and {k: v.data_ptr() for k, v in scratch.items()} == where
+    assert len(cache) == 1 and next(iter(cache.values())) is scratch and scratch.data_ptr() == where
     assert torch.equal(first, again) and torch.equal(first_radius, again_radius) and not torch.equal(first, other)
     # whatever the scratch holds
-    for v in scratch.values():
-        v.view(torch.uint8).fill_(0x7F)
+    scratch.fill_(0x7F)
     dirty, dirty_radius = device.medial_axis(ta, **kw)
     assert torch.equal(first, dirty) and torch.equal(first_radius, dirty_radius)
     assert same_bytes(to_host(first, np.int32), oracle.medial_axis(a, black_border=True, binary=True))
-    # another dtype of the same shape under binary transforms the same mask: the same scratch
-    device.medial_axis(to_device(a.astype(np.uint8)), binary=True, black_border=True)
-    assert len(device._medial_buffers) == 1
+    # another dtype of the same shape under binary transforms the same mask: the same bytes, the same scratch
+    device.medial_axis(to_device(a.astype(np.uint8)), **kw)
+    assert len(cache) == 1
     device.medial_axis(ta, black_border=True)
-    assert len(device._medial_buffers) == 2
+    assert len(cache) == 2

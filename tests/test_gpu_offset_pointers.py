@@ -28,6 +28,9 @@ import dust_oracle
 import fill_holes_oracle
 import ft_oracle
 import label_stats_oracle
+import medial_oracle
+import morph_oracle
+import thickness_oracle
 from synth import bits_of, blocky_labels, offset_out, offset_view, outside_intact
 
 pytestmark = pytest.mark.gpu
@@ -495,6 +498,56 @@ def test_dust_on_offset_pointers(ext, c):
             assert torch.equal(buf[:lo_], before[:lo_]) and torch.equal(buf[hi_:], before[hi_:])
 
 
+# ---- 9b. morphology, local thickness and the medial axis: the compositions ------------------------------------------------------
+FIELD_OFFSETS = [(np.uint8, 0, 0), (np.uint8, 1, 0), (np.uint8, 0, 1), (np.uint8, 3, 1), (np.uint16, 1, 3), (np.uint32, 1, 1), (np.uint64, 1, 1)]
+
+
+def test_field_operations_on_offset_labels_and_outputs(oracle_port):
+    """The workspace keeps its alignment, so the fields and masks carved from it are 16-byte aligned while the labels, the
+    output, T or the radius are not: the element form of the select and step kernels next to aligned fields.  sx = 33 is no
+    multiple of 4.  (The sizes are int64 at offset 1: 8-byte aligned, as their type asks.)"""
+    L = lib()
+    ext, w = (33, 20, 12), (6.0, 6.0, 30.0)
+    lab8 = labels_c(ext, np.uint8, seed=ext[0], zero_frac=0.3, block=4)
+    an = w[::-1]
+    r = 6.0
+    opened, closed = morph_oracle.opening(lab8, r, an, black_border=True), morph_oracle.closing(lab8, r, an)
+    assert 0 < np.count_nonzero(opened) < np.count_nonzero(lab8) < np.count_nonzero(closed) < lab8.size
+    radii = np.array([6.0, 12.0, 21.0], dtype=np.float64)
+    T_want, _, sizes_want = thickness_oracle.local_thickness(lab8, radii, an, black_border=True)
+    assert 0 < sizes_want[-1] < sizes_want[0]
+    on = medial_oracle.on_axis(lab8, anisotropy=an, black_border=True)
+    assert 0 < np.count_nonzero(on) < np.count_nonzero(lab8)
+    radius_want = np.where(on, np.sqrt(oracle_port.edtsq(lab8, an, True)), np.float32(0.0)).astype(np.float32)
+    for dtype, k_lab, k_out in FIELD_OFFSETS:
+        lab = lab8.astype(dtype)
+        code = CODE[np.dtype(dtype).name]
+        bits = f"u{lab.dtype.itemsize}"
+        what = (dtype, k_lab, k_out)
+        _, lview = offset_view(lab, k_lab)
+        for op, flags, want in ((2, 1, opened), (3, 0, closed)):
+            obuf, oview = out_buffer(lab.shape, dtype, k_out)
+            ws = workspace(L.edt_hip_morphology_workspace_bytes(code, 3, *ext, op, flags))
+            ok(L.edt_hip_morphology_device(vp(lview), code, 3, *ext, *w, op, r, flags, vp(oview), vp(ws), ws.numel(), stream()))
+            out_matches(obuf, oview, k_out, want.astype(dtype).view(bits), ("morphology", op) + what)
+        tbuf, tview = out_buffer(lab.shape, np.float32, k_out)
+        sbuf, sview = out_buffer((radii.size,), np.int64, 1)
+        n_used = ctypes.c_int64(-1)
+        ws = workspace(L.edt_hip_local_thickness_workspace_bytes(code, 3, *ext, 1))
+        ok(L.edt_hip_local_thickness_device(vp(lview), code, 3, *ext, *w, 1, ctypes.c_void_p(radii.ctypes.data), radii.size, 0.0, vp(tview),
+                                            vp(sview), ctypes.byref(n_used), vp(ws), ws.numel(), stream()))
+        out_matches(tbuf, tview, k_out, f32_bits(T_want), ("local_thickness",) + what)
+        out_matches(sbuf, sview, 1, sizes_want.view(np.uint64), ("local_thickness sizes",) + what)
+        assert n_used.value == radii.size
+        obuf, oview = out_buffer(lab.shape, dtype, k_out)
+        rbuf, rview = out_buffer(lab.shape, np.float32, (k_out + 1) % 4)
+        ws = workspace(L.edt_hip_medial_axis_workspace_bytes(code, 3, *ext, 1, 1))
+        ok(L.edt_hip_medial_axis_device(vp(lview), code, 3, *ext, *w, 1, float(max(w)), 0.0, vp(oview), vp(rview), vp(ws), ws.numel(),
+                                        stream()))
+        out_matches(obuf, oview, k_out, np.where(on, lab, np.zeros((), dtype)).astype(dtype).view(bits), ("medial_axis",) + what)
+        out_matches(rbuf, rview, (k_out + 1) % 4, f32_bits(radius_want), ("medial_axis radius",) + what)
+
+
 # ---- 10. the sharded phases ------------------------------------------------------------------------------------------------
 def test_shard_phases_with_an_offset_partial_field(oracle_port):
     """edt_hip_shard_xy_device and edt_hip_shard_z_device as ONE virtual rank (tests/test_gpu_paths.py drives several): the fp32
@@ -656,6 +709,18 @@ def test_misaligned_workspace_is_refused_by_every_device_entry_point():
     refused(L.edt_hip_fill_holes_device(vp(lab), U8, 3, *ext, 1, 0, vp(o8), vp(i64), p, nb, stream()), o8, i64)
     p, nb, keep = ws_at_4(L.edt_hip_dust_workspace_bytes(U8, 3, *ext))
     refused(L.edt_hip_dust_device(vp(lab), U8, 3, *ext, 1, 0, 2, (1 << 63) - 1, 0, vp(o8), vp(i64), p, nb, stream()), o8, i64)
+    # the compositions of the field operations
+    for op in (0, 1, 2, 3):
+        p, nb, keep = ws_at_4(L.edt_hip_morphology_workspace_bytes(U8, 3, *ext, op, 0))
+        refused(L.edt_hip_morphology_device(vp(lab), U8, 3, *ext, 1.0, 1.0, 1.0, op, 2.0, 0, vp(o8), p, nb, stream()), o8)
+    radii = np.array([1.0, 2.0], dtype=np.float64)
+    n_used = ctypes.c_int64(fill)
+    p, nb, keep = ws_at_4(L.edt_hip_local_thickness_workspace_bytes(U8, 3, *ext, 0))
+    refused(L.edt_hip_local_thickness_device(vp(lab), U8, 3, *ext, 1.0, 1.0, 1.0, 0, ctypes.c_void_p(radii.ctypes.data), 2, 0.0, vp(f),
+                                             vp(i64), ctypes.byref(n_used), p, nb, stream()), f, i64)
+    assert n_used.value == fill
+    p, nb, keep = ws_at_4(L.edt_hip_medial_axis_workspace_bytes(U8, 3, *ext, 0, 1))
+    refused(L.edt_hip_medial_axis_device(vp(lab), U8, 3, *ext, 1.0, 1.0, 1.0, 0, 1.0, 0.0, vp(o8), vp(f), p, nb, stream()), o8, f)
     # the sharded phases
     z8 = out(torch.int8)
     p, nb, keep = ws_at_4(L.edt_hip_shard_workspace_bytes(U8, *ext))

@@ -339,7 +339,7 @@ def test_two_calls_of_one_shape_share_the_scratch_and_nothing_else():
     torch.cuda.synchronize()
     for (T, sizes), (want, used, voxels) in zip(outs, wants):
         assert same_bytes(T.cpu().numpy(), want) and np.array_equal(sizes.radii, used) and np.array_equal(sizes.voxels.cpu().numpy(), voxels)
-    assert len(device._thickness_buffers) <= 9
+    assert len(device._workspaces["edt_hip_local_thickness_workspace_bytes"]) <= 9
 
 
 def test_explicit_radii_are_captured_on_a_side_stream_and_replay_on_changed_input():
@@ -368,6 +368,29 @@ def test_explicit_radii_are_captured_on_a_side_stream_and_replay_on_changed_inpu
         torch.cuda.synchronize()
         assert same_bytes(out.cpu().numpy(), wants[which][0]), which
         assert np.array_equal(sizes.voxels.cpu().numpy(), wants[which][2]), which
+
+
+def test_the_default_ladder_is_refused_on_a_capturing_stream_and_the_capture_goes_on():
+    """radii=None reads Smax back: on a stream that is being captured the library refuses before any device work (EdtHipError,
+    not a failed synchronisation inside the capture), and the capture is still good for the explicit call that follows"""
+    import torch
+    from edt import _lib, device
+    lab = np.ascontiguousarray(voronoi_labels((64, 40, 24), 10, seed=6, upsample=8, membrane=0.1).T)
+    radii = [1, 2, 3.5]
+    want = oracle.local_thickness(lab, radii, None, black_border=True)
+    t = device_labels(lab)
+    side = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        device.local_thickness(t, radii, black_border=True)                 # warm-up: scratch and code objects of this stream
+        side.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            with pytest.raises(_lib.EdtHipError, match="captured"):
+                device.local_thickness(t, None, black_border=True)
+            out, sizes = device.local_thickness(t, radii, black_border=True, return_sizes=True)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert same_bytes(out.cpu().numpy(), want[0]) and np.array_equal(sizes.voxels.cpu().numpy(), want[2])
 
 
 def test_host_entry_runs_on_the_first_listed_device():

@@ -36,6 +36,9 @@ import pytest
 import dust_oracle
 import fill_holes_oracle
 import label_stats_oracle
+import medial_oracle
+import morph_oracle
+import thickness_oracle
 from synth import _signed_bits, bits_of, blocky_labels, box_edtsq_closed_form
 from test_gpu_offset_pointers import MARK, NAN, U8, U16, U32, component_labels, f32_bits, ft_want, labels_c, lib, ok, stream, sync, vp
 from test_gpu_q16 import slab_labels
@@ -840,6 +843,73 @@ def case_empty_volumes(oracle_port, v):
     return Case(("empty volumes", e), 256, call, check, outputs=(n_cc, n_fh, n_ls, n_runs, counts))
 
 
+# -- the compositions of the field operations: one workspace each, carved into fields, mask, planes and the transforms' scratch ---
+MORPH_OPEN, MORPH_BINARY = 2, 128
+FIELD_RADIUS = 6.0                                           # one voxel of x and y at FT_W: the outer voxel of every object erodes
+
+
+def case_morphology(oracle_port, v):
+    """opening of uint16 labels: both transforms, the select into the mask and the select into the output"""
+    lab = ft_labels(v).astype(np.uint16)
+    eroded = morph_oracle.erode(lab, FIELD_RADIUS, FT_W[::-1], black_border=True)
+    assert 0 < np.count_nonzero(eroded) < np.count_nonzero(lab)
+    want = morph_oracle.opening(lab, FIELD_RADIUS, FT_W[::-1], black_border=True)
+    assert 0 < np.count_nonzero(want) < np.count_nonzero(lab)
+    labels, out = upload(lab), device_out(lab.shape, np.uint16)
+
+    def call(ws):
+        ok(lib().edt_hip_morphology_device(vp(labels), U16, 3, *FT_EXT, *FT_W, MORPH_OPEN, FIELD_RADIUS, FLAG_BB, vp(out), vp(ws),
+                                           ws.numel(), stream()))
+    return Case(("morphology_device", v), lib().edt_hip_morphology_workspace_bytes(U16, 3, *FT_EXT, MORPH_OPEN, FLAG_BB), call,
+                lambda what: equal_bits(out, want, what), outputs=(out,))
+
+
+def case_local_thickness(oracle_port, v):
+    """explicit radii: enqueue-only.  The sizes hold the sentinel before every call and replay: they are zeroed by a kernel"""
+    lab = ft_labels(v)
+    radii = np.array([1.0, 2.0, 3.5], dtype=np.float64) * min(FT_W)
+    want, _, want_sizes = thickness_oracle.local_thickness(lab, radii, FT_W[::-1], black_border=True)
+    assert 0 < want_sizes[-1] < want_sizes[0] < np.count_nonzero(lab)
+    labels, T, sizes = upload(lab), device_out(lab.shape, np.float32), device_out((radii.size,), np.int64)
+    n_used = ctypes.c_int64(-1)
+
+    def call(ws):
+        ok(lib().edt_hip_local_thickness_device(vp(labels), U8, 3, *FT_EXT, *FT_W, FLAG_BB, ctypes.c_void_p(radii.ctypes.data), radii.size,
+                                                0.0, vp(T), vp(sizes), ctypes.byref(n_used), vp(ws), ws.numel(), stream()))
+
+    def check(what):
+        assert n_used.value == radii.size and sizes.tolist() == want_sizes.tolist(), (what, sizes.tolist(), want_sizes.tolist())
+        equal_bits(T, f32_bits(want), what)
+    return Case(("local_thickness_device", v), lib().edt_hip_local_thickness_workspace_bytes(U8, 3, *FT_EXT, FLAG_BB), call, check,
+                outputs=(T, sizes))
+
+
+MEDIAL_EXT = (65, 9, 17)                                     # more than one tile of 62 x 4 x 16 along every axis
+
+
+def case_medial_axis(oracle_port, v):
+    """with the radius, under binary: the planes, the mask and the field of the carve, and both transforms on one scratch"""
+    lab = labels_c(MEDIAL_EXT, np.int32, seed=MEDIAL_EXT[0] + v, zero_frac=0.3, block=6 + v)
+    kw = dict(anisotropy=FT_W[::-1], black_border=True, binary=True)
+    on = medial_oracle.on_axis(lab, **kw)
+    assert 0 < np.count_nonzero(on) < np.count_nonzero(lab)
+    want = medial_oracle.medial_axis(lab, **kw)
+    field = np.sqrt(oracle_port.edtsq((lab != 0).astype(np.uint8), FT_W[::-1], True))
+    want_radius = np.where(on, field, np.float32(0.0)).astype(np.float32)
+    labels, out, radius = upload(lab), device_out(lab.shape, np.int32), device_out(lab.shape, np.float32)
+    gamma = float(max(FT_W))
+
+    def call(ws):
+        ok(lib().edt_hip_medial_axis_device(vp(labels), U32, 3, *MEDIAL_EXT, *FT_W, FLAG_BB | MORPH_BINARY, gamma, 0.0, vp(out), vp(radius),
+                                            vp(ws), ws.numel(), stream()))
+
+    def check(what):
+        equal_bits(out, want.view(np.uint32), what)
+        equal_bits(radius, f32_bits(want_radius), (what, "radius"))
+    return Case(("medial_axis_device", v), lib().edt_hip_medial_axis_workspace_bytes(U32, 3, *MEDIAL_EXT, FLAG_BB | MORPH_BINARY, 1), call,
+                check, outputs=(out, radius))
+
+
 ENTRY = {
     "edtsq_voxel_graph_device": lambda o, v: case_voxel_graph(o, v, True),
     "edtsq_voxel_graph_device_fp32": lambda o, v: case_voxel_graph(o, v, False),
@@ -859,6 +929,9 @@ ENTRY = {
     "fill_holes_device": case_fill_holes,
     "dust_device": case_dust,
     "empty_volumes": case_empty_volumes,
+    "morphology_device": case_morphology,
+    "local_thickness_device": case_local_thickness,
+    "medial_axis_device": case_medial_axis,
 }
 _cases = {}
 

@@ -1,6 +1,6 @@
 """CPU tier of the medial axis (include/edt_hip.h, "medial axis"): the numpy oracle (tests/medial_oracle.py) states the definition
 twice -- the header's gather form and the paper's scatter loop -- and the two are held against each other and against the
-pictures and properties the definition promises; the two symbols are exported and bound, every refusal comes back with its code
+pictures and properties the definition promises; the four symbols are exported and bound, every refusal comes back with its code
 before any device work and with the outputs untouched (host stand-ins that are never dereferenced serve as device pointers), and
 the Python layers raise before the library is asked."""
 import ctypes
@@ -215,11 +215,28 @@ def host(lib, b, **kw):
                                    p(a["out"]), p(a["radius"]))
 
 
+def aligned_workspace(nbytes):
+    """a host stand-in for a 256-byte aligned device workspace of nbytes (never dereferenced)"""
+    raw = np.zeros(int(nbytes) + 256, dtype=np.uint8)
+    return raw[(-raw.ctypes.data) % 256:][:int(nbytes)]
+
+
+def on_device(lib, b, **kw):
+    """edt_hip_medial_axis_device with a workspace of the size its query gives, unless ws / ws_bytes say otherwise"""
+    a = dict(labels=b.labels, dtype=U32, ndim=3, ext=EXT, w=(1.0, 1.0, 1.0), flags=0, gamma=1.0, ratio=0.0, out=b.out, radius=b.radius)
+    a.update({k: v for k, v in kw.items() if k not in ("ws", "ws_bytes")})
+    need = max(lib.edt_hip_medial_axis_workspace_bytes(a["dtype"], a["ndim"], *a["ext"], a["flags"], 0 if a["radius"] is None else 1), 256)
+    ws = kw["ws"] if "ws" in kw else aligned_workspace(need)
+    return lib.edt_hip_medial_axis_device(p(a["labels"]), a["dtype"], a["ndim"], *a["ext"], *a["w"], a["flags"], a["gamma"], a["ratio"],
+                                          p(a["out"]), p(a["radius"]), p(ws), kw.get("ws_bytes", need), None)
+
+
 def test_symbols_are_exported_and_bound(lib):
     from edt import _lib
     import edt
     from edt import device
-    for name in ("edt_hip_medial_axis_step_device", "edt_hip_medial_axis"):
+    for name in ("edt_hip_medial_axis_step_device", "edt_hip_medial_axis", "edt_hip_medial_axis_workspace_bytes",
+                 "edt_hip_medial_axis_device"):
         assert name in _lib.SIGNATURES and getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
     assert "medial_axis" in edt.__all__ and callable(edt.medial_axis) and callable(device.medial_axis)
     assert "d_workspace" not in " ".join(str(t) for t in _lib.SIGNATURES["edt_hip_medial_axis_step_device"][1])
@@ -270,6 +287,48 @@ def test_host_refusals(lib):
     assert host(lib, b, ext=(9, 0, 5), ratio=float("nan")) == BAD_ARG
 
 
+def test_device_entry_refuses_what_its_host_sibling_refuses(lib):
+    """the same codes for the same bad arguments, before any device work (never EDT_ERR_NO_DEVICE) and with the outputs untouched"""
+    b = Buffers()
+    for what, kw, code in COMMON_REFUSALS:
+        assert on_device(lib, b, **kw) == code, (what, lib.edt_hip_last_error())
+        assert b.untouched(), what
+    # the workspace: missing, too small, misaligned
+    for radius in (b.radius, None):
+        need = lib.edt_hip_medial_axis_workspace_bytes(U32, 3, *EXT, 0, 0 if radius is None else 1)
+        ws = aligned_workspace(need + 256)
+        assert on_device(lib, b, radius=radius, ws=None) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+        assert on_device(lib, b, radius=radius, ws=ws, ws_bytes=need - 1) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+        assert on_device(lib, b, radius=radius, ws=ws[4:], ws_bytes=need) == BAD_ARG and b"256-byte aligned" in lib.edt_hip_last_error()
+    # a workspace sized without the radius does not serve a call with it
+    assert on_device(lib, b, ws=ws, ws_bytes=need) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+    # d_out == d_labels: the neighbours are still being read
+    assert on_device(lib, b, out=b.labels) == BAD_ARG and b"alias" in lib.edt_hip_last_error()
+    assert b.untouched() and bool((b.labels == 1).all())
+    # an empty volume: nothing touched, whatever the pointers -- but not whatever the pruning
+    assert on_device(lib, b, ext=(9, 0, 5), labels=None, out=None, radius=None, ws=None, ws_bytes=0) == OK
+    assert on_device(lib, b, ext=(0, 1, 1), ndim=1) == OK and b.untouched()
+    assert on_device(lib, b, ext=(9, 0, 5), ratio=float("nan")) == BAD_ARG
+
+
+def test_workspace_query(lib):
+    query = lib.edt_hip_medial_axis_workspace_bytes
+    for dtype in (U8, U32, F64, BOOL):
+        for flags in (0, BLACK_BORDER, MORPH_BINARY, BLACK_BORDER | MORPH_BINARY):
+            binary = bool(flags & MORPH_BINARY) or dtype == BOOL
+            of = U8 if binary else dtype
+            for with_radius in (0, 1):
+                n = query(dtype, 3, *EXT, flags, with_radius)
+                assert n > 0 and n % 256 == 0, (dtype, flags, with_radius, n)
+                # the planes, the mask under binary, the field with the radius, the scratch of the feature transform
+                parts = 12 * N + N * binary + 4 * N * with_radius
+                assert n >= parts + lib.edt_hip_feature_workspace_bytes(of, 3, *EXT, flags & BLACK_BORDER), (dtype, flags, with_radius)
+            assert query(dtype, 3, *EXT, flags, 1) > query(dtype, 3, *EXT, flags, 0)
+    assert query(U32, 3, *EXT, MORPH_BINARY, 1) == query(U8, 3, *EXT, MORPH_BINARY, 1) != query(U32, 3, *EXT, 0, 1)
+    assert query(9, 3, *EXT, 0, 0) == 0 and query(U8, 4, *EXT, 0, 0) == 0 and query(U8, 2, *EXT, 0, 1) == 0
+    assert query(U8, 3, 9, -1, 5, 0, 0) == 0 and query(U8, 3, *EXT, SQRT, 0) == 0 and query(U8, 3, *EXT, 256, 1) == 0
+
+
 def test_a_valid_call_reaches_the_device_check(lib):
     """what is left of a call that passes every check above is the device: without one, EDT_ERR_NO_DEVICE and untouched outputs"""
     from edt import _lib
@@ -280,6 +339,7 @@ def test_a_valid_call_reaches_the_device_check(lib):
     assert step(lib, b) == NO_DEVICE and step(lib, b, field=None, radius=None, flags=BLACK_BORDER | MORPH_BINARY) == NO_DEVICE
     assert step(lib, b, gamma=0.0, ratio=3.0, w=(1.0, -2.0, -0.5)) == NO_DEVICE
     assert host(lib, b) == NO_DEVICE and host(lib, b, radius=None, flags=BLACK_BORDER | MORPH_BINARY, dtype=BOOL, labels=b.labels.view(np.uint8)) == NO_DEVICE
+    assert on_device(lib, b) == NO_DEVICE and on_device(lib, b, radius=None, flags=BLACK_BORDER | MORPH_BINARY) == NO_DEVICE
     assert b.untouched()
     with pytest.raises(_lib.EdtHipError) as e:
         edt.medial_axis(np.ones((4, 4, 4), dtype=np.uint8), return_distance=True)

@@ -1,4 +1,4 @@
-"""CPU tier of the morphology operations (include/edt_hip.h, "morphology"): the three symbols are exported and bound, every
+"""CPU tier of the morphology operations (include/edt_hip.h, "morphology"): the five symbols are exported and bound, every
 refusal comes back with its code before any device work and with the outputs untouched (host stand-ins that are never
 dereferenced serve as device pointers), the Python layers raise before the library is asked, and the numpy oracle
 (tests/morph_oracle.py) is held against scipy's binary morphology with a ball."""
@@ -63,7 +63,8 @@ def test_symbols_are_exported_and_bound(lib):
     from edt import _lib
     import edt
     from edt import device
-    for name in ("edt_hip_is_foreground_device", "edt_hip_morph_select_device", "edt_hip_morphology"):
+    for name in ("edt_hip_is_foreground_device", "edt_hip_morph_select_device", "edt_hip_morphology",
+                 "edt_hip_morphology_workspace_bytes", "edt_hip_morphology_device"):
         assert name in _lib.SIGNATURES and getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
     assert (_lib.MORPH_ERODE, _lib.MORPH_DILATE, _lib.MORPH_OPEN, _lib.MORPH_CLOSE) == (0, 1, 2, 3)
     assert (_lib.MORPH_FARTHER, _lib.MORPH_WITHIN, _lib.FLAG_MORPH_BINARY) == (0, 1, 128)
@@ -98,8 +99,25 @@ def test_is_foreground_refusals(lib):
     assert b.untouched()
 
 
-def test_morphology_refusals(lib):
-    b = Buffers()
+def aligned_workspace(nbytes):
+    """a host stand-in for a 256-byte aligned device workspace of nbytes (never dereferenced)"""
+    raw = np.zeros(int(nbytes) + 256, dtype=np.uint8)
+    return raw[(-raw.ctypes.data) % 256:][:int(nbytes)]
+
+
+def morphology_device(lib, b, **kw):
+    """edt_hip_morphology_device with a workspace of the size its query gives, unless ws / ws_bytes say otherwise"""
+    a = dict(labels=b.labels, dtype=U32, ndim=3, ext=EXT, w=(1.0, 1.0, 1.0), op=ERODE, radius=2.0, flags=0, out=b.out)
+    a.update({k: v for k, v in kw.items() if k not in ("ws", "ws_bytes")})
+    need = lib.edt_hip_morphology_workspace_bytes(a["dtype"], a["ndim"], *a["ext"], a["op"], a["flags"])
+    ws = kw["ws"] if "ws" in kw else aligned_workspace(max(need, 256))
+    ws = ws if isinstance(ws, (ctypes.c_void_p, type(None))) else p(ws)
+    out = a["out"] if isinstance(a["out"], (ctypes.c_void_p, type(None))) else p(a["out"])
+    return lib.edt_hip_morphology_device(p(a["labels"]), a["dtype"], a["ndim"], *a["ext"], *a["w"], a["op"], a["radius"], a["flags"], out,
+                                         ws, kw.get("ws_bytes", max(need, 256)), None)
+
+
+def bad_arguments():
     bad = [("op", dict(op=4), BAD_ARG), ("op", dict(op=-1), BAD_ARG), ("dtype", dict(dtype=9), BAD_ARG),
            ("ndim", dict(ndim=4), BAD_ARG), ("unused extent", dict(ndim=2), BAD_ARG),
            ("null labels", dict(labels=None), BAD_ARG), ("null output", dict(out=None), BAD_ARG),
@@ -110,7 +128,12 @@ def test_morphology_refusals(lib):
     for op in (DILATE, CLOSE):
         bad += [(f"flag {f} on op {op}", dict(op=op, flags=f), UNSUPPORTED) for f in (BLACK_BORDER, MORPH_BINARY, BLACK_BORDER | MORPH_BINARY)]
     bad += [(f"flag {f} on op {op}", dict(op=op, flags=f), UNSUPPORTED) for op in (ERODE, OPEN) for f in (SQRT, 4, 64, 256, MORPH_BINARY | 16)]
-    for what, kw, code in bad:
+    return bad
+
+
+def test_morphology_refusals(lib):
+    b = Buffers()
+    for what, kw, code in bad_arguments():
         assert morphology(lib, b, **kw) == code, (what, kw, lib.edt_hip_last_error())
         assert b.untouched(), what
     # the op is looked at before the flags and the radius, the flags before the radius
@@ -129,6 +152,47 @@ def test_morphology_refusals(lib):
     assert morphology(lib, b, ext=(0, 1, 1), ndim=1) == OK and b.untouched()
 
 
+def test_device_entry_refuses_what_its_host_sibling_refuses(lib):
+    """the same codes for the same bad arguments, before any device work (never EDT_ERR_NO_DEVICE) and with the output untouched"""
+    b = Buffers()
+    for what, kw, code in bad_arguments():
+        assert morphology_device(lib, b, **kw) == code, (what, kw, lib.edt_hip_last_error())
+        assert b.untouched(), what
+    assert morphology_device(lib, b, op=7, flags=BLACK_BORDER, radius=-1.0) == BAD_ARG and b"op" in lib.edt_hip_last_error()
+    assert morphology_device(lib, b, op=DILATE, flags=BLACK_BORDER, radius=-1.0) == UNSUPPORTED
+    # the workspace: missing, too small, misaligned
+    for op in (ERODE, DILATE, OPEN, CLOSE):
+        need = lib.edt_hip_morphology_workspace_bytes(U32, 3, *EXT, op, 0)
+        ws = aligned_workspace(need + 256)
+        assert morphology_device(lib, b, op=op, ws=None) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+        assert morphology_device(lib, b, op=op, ws=ws, ws_bytes=need - 1) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+        assert morphology_device(lib, b, op=op, ws=ws[4:], ws_bytes=need) == BAD_ARG and b"256-byte aligned" in lib.edt_hip_last_error()
+    # d_out == d_labels: refused where the last step still reads other voxels of the labels
+    for op in (DILATE, CLOSE):
+        assert morphology_device(lib, b, op=op, out=b.labels) == BAD_ARG and b"alias" in lib.edt_hip_last_error()
+    assert bool((b.labels == 1).all()) and b.untouched()
+    # an empty volume: nothing touched, whatever the pointers
+    assert morphology_device(lib, b, ext=(9, 0, 5), labels=None, out=None, ws=None, ws_bytes=0) == OK
+    assert morphology_device(lib, b, ext=(0, 1, 1), ndim=1) == OK and b.untouched()
+
+
+def test_workspace_query(lib):
+    query = lib.edt_hip_morphology_workspace_bytes
+    for op in (ERODE, DILATE, OPEN, CLOSE):
+        for dtype in (U8, U32, F64, BOOL):
+            n = query(dtype, 3, *EXT, op, 0)
+            assert n > 0 and n % 256 == 0, (op, dtype, n)
+        assert query(9, 3, *EXT, op, 0) == 0 and query(U8, 4, *EXT, op, 0) == 0 and query(U8, 2, *EXT, op, 0) == 0
+        assert query(U8, 3, 9, -1, 5, op, 0) == 0 and query(U8, 3, *EXT, op, SQRT) == 0
+    assert query(U8, 3, *EXT, 4, 0) == 0 and query(U8, 3, *EXT, DILATE, BLACK_BORDER) == 0
+    voxels = N
+    # erode / opening / closing hold a field and a mask besides the transforms' scratch; dilate is expand_labels' scratch alone
+    assert query(U32, 3, *EXT, DILATE, 0) == lib.edt_hip_expand_labels_workspace_bytes(U32, 3, *EXT)
+    for op in (ERODE, OPEN, CLOSE):
+        assert query(U32, 3, *EXT, op, 0) >= 5 * voxels + lib.edt_hip_workspace_bytes_flags(U8, 3, *EXT, 0)
+    assert query(U32, 3, *EXT, ERODE, 0) >= 5 * voxels + lib.edt_hip_workspace_bytes_flags(U32, 3, *EXT, 0)
+
+
 def test_without_a_device_the_host_entry_says_so(lib):
     from edt import _lib
     import edt
@@ -137,7 +201,11 @@ def test_without_a_device_the_host_entry_says_so(lib):
     b = Buffers()
     for op, flags, radius in ((ERODE, BLACK_BORDER | MORPH_BINARY, 0.0), (DILATE, 0, float("inf")), (OPEN, 0, 2.0), (CLOSE, 0, 1.5)):
         assert morphology(lib, b, op=op, flags=flags, radius=radius) == NO_DEVICE
-    assert b.untouched()
+        assert morphology_device(lib, b, op=op, flags=flags, radius=radius) == NO_DEVICE
+    # in place is not refused by the argument checks of erode and opening
+    for op in (ERODE, OPEN):
+        assert morphology_device(lib, b, op=op, out=b.labels) == NO_DEVICE
+    assert b.untouched() and bool((b.labels == 1).all())
     with pytest.raises(_lib.EdtHipError) as e:
         edt.opening(np.ones((4, 4, 4), dtype=np.uint8), 1.0)
     assert e.value.code == _lib.ERR_NO_DEVICE

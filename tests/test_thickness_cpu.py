@@ -1,4 +1,4 @@
-"""CPU tier of local thickness (include/edt_hip.h, "local thickness"): the two symbols are exported and bound, every refusal comes
+"""CPU tier of local thickness (include/edt_hip.h, "local thickness"): the four symbols are exported and bound, every refusal comes
 back with its code before any device work and with the outputs untouched (host stand-ins that are never dereferenced serve as
 device pointers), the Python layers raise before the library is asked, and the numpy oracle (tests/thickness_oracle.py) is held
 against scipy's binary morphology with a ball, label by label, on a volume whose openings are not nested."""
@@ -64,11 +64,32 @@ def thickness(lib, b, **kw):
                                        a["step"], ptr(a["T"]), ptr(a["sizes"]), ptr(a["n_used"]))
 
 
+def aligned_workspace(nbytes):
+    """a host stand-in for a 256-byte aligned device workspace of nbytes (never dereferenced)"""
+    raw = np.zeros(int(nbytes) + 256, dtype=np.uint8)
+    return raw[(-raw.ctypes.data) % 256:][:int(nbytes)]
+
+
+def thickness_device(lib, b, **kw):
+    """edt_hip_local_thickness_device with a workspace of the size its query gives, unless ws / ws_bytes say otherwise"""
+    a = dict(labels=b.labels, dtype=U32, ndim=3, ext=EXT, w=(1.0, 1.0, 1.0), flags=0, radii=b.radii, n_radii=None, step=1.0,
+             T=b.T, sizes=b.sizes, n_used=b.n_used)
+    a.update({k: v for k, v in kw.items() if k not in ("ws", "ws_bytes")})
+    n_radii = (0 if a["radii"] is None else len(a["radii"])) if a["n_radii"] is None else a["n_radii"]
+    ptr = lambda v: v if isinstance(v, (ctypes.c_void_p, type(None))) else p(v)  # noqa: E731
+    need = max(lib.edt_hip_local_thickness_workspace_bytes(a["dtype"], a["ndim"], *a["ext"], a["flags"]), 256)
+    ws = kw["ws"] if "ws" in kw else aligned_workspace(need)
+    return lib.edt_hip_local_thickness_device(ptr(a["labels"]), a["dtype"], a["ndim"], *a["ext"], *a["w"], a["flags"], ptr(a["radii"]),
+                                              n_radii, a["step"], ptr(a["T"]), ptr(a["sizes"]), ptr(a["n_used"]), ptr(ws),
+                                              kw.get("ws_bytes", need), None)
+
+
 def test_symbols_are_exported_and_bound(lib):
     from edt import _lib
     import edt
     from edt import device
-    for name in ("edt_hip_thickness_step_device", "edt_hip_local_thickness"):
+    for name in ("edt_hip_thickness_step_device", "edt_hip_local_thickness", "edt_hip_local_thickness_workspace_bytes",
+                 "edt_hip_local_thickness_device"):
         assert name in _lib.SIGNATURES and getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
     for name in ("local_thickness", "ThicknessSizes"):
         assert name in edt.__all__ and callable(getattr(edt, name))
@@ -98,9 +119,11 @@ def test_step_refusals(lib):
     assert b.untouched()
 
 
-def test_local_thickness_refusals(lib):
-    b = Buffers()
-    r = lambda *v: np.array(v, dtype=np.float64)  # noqa: E731
+def r(*v):
+    return np.array(v, dtype=np.float64)
+
+
+def bad_arguments():
     bad = [("dtype", dict(dtype=9), BAD_ARG), ("ndim", dict(ndim=4), BAD_ARG), ("ndim", dict(ndim=0), BAD_ARG),
            ("unused extent", dict(ndim=2), BAD_ARG),
            ("null labels", dict(labels=None), BAD_ARG), ("null thickness", dict(T=None), BAD_ARG),
@@ -114,7 +137,12 @@ def test_local_thickness_refusals(lib):
     bad += [(f"radius {v} last", dict(radii=r(1, 2, v)), BAD_ARG) for v in BAD_RADII]
     bad += [(f"step {v}", dict(radii=None, n_radii=3, step=v), BAD_ARG) for v in BAD_RADII]
     bad += [(f"flags {f}", dict(flags=f), UNSUPPORTED) for f in (SQRT, 4, 8, 16, 32, 64, 256, MORPH_BINARY | 16, BLACK_BORDER | SQRT)]
-    for what, kw, code in bad:
+    return bad
+
+
+def test_local_thickness_refusals(lib):
+    b = Buffers()
+    for what, kw, code in bad_arguments():
         assert thickness(lib, b, **kw) == code, (what, lib.edt_hip_last_error())
         assert b.untouched(), what
     # the flags are looked at before the radii
@@ -136,6 +164,41 @@ def test_local_thickness_refusals(lib):
     assert thickness(lib, b, ext=(9, 0, 5), radii=r(2, 1, 3)) == BAD_ARG
 
 
+def test_device_entry_refuses_what_its_host_sibling_refuses(lib):
+    """the same codes for the same bad arguments, before any device work (never EDT_ERR_NO_DEVICE) and with the outputs untouched"""
+    b = Buffers()
+    for what, kw, code in bad_arguments():
+        assert thickness_device(lib, b, **kw) == code, (what, lib.edt_hip_last_error())
+        assert b.untouched(), what
+    assert thickness_device(lib, b, flags=SQRT, radii=r(2, 1, 0)) == UNSUPPORTED
+    # the workspace: missing, too small, misaligned -- for an explicit list and for the default ladder
+    need = lib.edt_hip_local_thickness_workspace_bytes(U32, 3, *EXT, 0)
+    ws = aligned_workspace(need + 256)
+    for kw in (dict(), dict(radii=None, n_radii=3)):
+        assert thickness_device(lib, b, ws=None, **kw) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+        assert thickness_device(lib, b, ws=ws, ws_bytes=need - 1, **kw) == BAD_ARG and b"workspace" in lib.edt_hip_last_error()
+        assert thickness_device(lib, b, ws=ws[4:], ws_bytes=need, **kw) == BAD_ARG and b"256-byte aligned" in lib.edt_hip_last_error()
+    assert b.untouched()
+    # an empty volume: nothing touched, whatever the pointers -- but not whatever the radii
+    assert thickness_device(lib, b, ext=(9, 0, 5), labels=None, T=None, sizes=None, n_used=None, ws=None, ws_bytes=0) == OK
+    assert thickness_device(lib, b, ext=(0, 1, 1), ndim=1) == OK and b.untouched()
+    assert thickness_device(lib, b, ext=(9, 0, 5), radii=r(2, 1, 3)) == BAD_ARG
+
+
+def test_workspace_query(lib):
+    query = lib.edt_hip_local_thickness_workspace_bytes
+    for dtype in (U8, U32, F64, BOOL):
+        for flags in (0, BLACK_BORDER, MORPH_BINARY, BLACK_BORDER | MORPH_BINARY):
+            n = query(dtype, 3, *EXT, flags)
+            assert n > 0 and n % 256 == 0, (dtype, flags, n)
+            # S, B and the mask, the word of Smax, the scratch of the binary transform
+            assert n >= 9 * N + 4 + lib.edt_hip_workspace_bytes_flags(U8, 3, *EXT, 0)
+    assert query(U32, 3, *EXT, 0) >= 9 * N + 4 + lib.edt_hip_workspace_bytes_flags(U32, 3, *EXT, 0)
+    assert query(U32, 3, *EXT, MORPH_BINARY) == query(U8, 3, *EXT, 0) == query(BOOL, 3, *EXT, 0)
+    assert query(9, 3, *EXT, 0) == 0 and query(U8, 4, *EXT, 0) == 0 and query(U8, 2, *EXT, 0) == 0 and query(U8, 3, 9, -1, 5, 0) == 0
+    assert query(U8, 3, *EXT, SQRT) == 0 and query(U8, 3, *EXT, 256) == 0
+
+
 def test_a_valid_call_reaches_the_device_check(lib):
     """what is left of a call that passes every check above is the device: without one, EDT_ERR_NO_DEVICE and untouched outputs"""
     from edt import _lib
@@ -146,6 +209,8 @@ def test_a_valid_call_reaches_the_device_check(lib):
     assert thickness(lib, b) == NO_DEVICE
     assert thickness(lib, b, flags=BLACK_BORDER | MORPH_BINARY, radii=None, n_radii=0, sizes=None, step=0.5) == NO_DEVICE
     assert step(lib, b) == NO_DEVICE and step(lib, b, B=None, size=None, smax=b.smax) == NO_DEVICE
+    assert thickness_device(lib, b) == NO_DEVICE
+    assert thickness_device(lib, b, flags=BLACK_BORDER | MORPH_BINARY, radii=None, n_radii=0, sizes=None, step=0.5) == NO_DEVICE
     assert b.untouched()
     with pytest.raises(_lib.EdtHipError) as e:
         edt.local_thickness(np.ones((4, 4, 4), dtype=np.uint8), [1.0, 2.0])

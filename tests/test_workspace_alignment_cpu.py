@@ -79,6 +79,15 @@ def calls(lib, s):
         p(s.lab), U8, 3, *EXT, 1, 0, p(o8), p(i64), *s.ws(lib.edt_hip_fill_holes_workspace_bytes(U8, 3, *EXT)), None)
     yield "edt_hip_dust_device", lib.edt_hip_dust_device(
         p(s.lab), U8, 3, *EXT, 1, 0, 2, (1 << 63) - 1, 0, p(o8), p(i64), *s.ws(lib.edt_hip_dust_workspace_bytes(U8, 3, *EXT)), None)
+    for op in range(4):
+        yield "edt_hip_morphology_device", lib.edt_hip_morphology_device(
+            p(s.lab), U8, 3, *EXT, 1.0, 1.0, 1.0, op, 2.0, 0, p(o8), *s.ws(lib.edt_hip_morphology_workspace_bytes(U8, 3, *EXT, op, 0)), None)
+    radii, n_used = np.array([1.0, 2.0, 3.0]), s.out(np.int64, 1)
+    yield "edt_hip_local_thickness_device", lib.edt_hip_local_thickness_device(
+        p(s.lab), U8, 3, *EXT, 1.0, 1.0, 1.0, 0, p(radii), 3, 0.0, p(f), p(i64), p(n_used),
+        *s.ws(lib.edt_hip_local_thickness_workspace_bytes(U8, 3, *EXT, 0)), None)
+    yield "edt_hip_medial_axis_device", lib.edt_hip_medial_axis_device(
+        p(s.lab), U8, 3, *EXT, 1.0, 1.0, 1.0, 0, 1.0, 0.0, p(o8), p(f), *s.ws(lib.edt_hip_medial_axis_workspace_bytes(U8, 3, *EXT, 0, 1)), None)
     z8 = s.out(np.int8)
     shard = s.ws(lib.edt_hip_shard_workspace_bytes(U8, *EXT))
     yield "edt_hip_shard_xy_device", lib.edt_hip_shard_xy_device(p(s.lab), None, U8, *EXT, 1.0, 1.0, 0, p(f), p(z8), *shard, None)

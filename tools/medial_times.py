@@ -3,9 +3,9 @@
 
 Volumes (512^3 unless --n says otherwise): the dense 2000-label segmentation cfg3 (uint32) at voxel sizes (1, 1, 1) and
 synth.blob_mask (uint8) at (6, 6, 30), no black border, default pruning.  For every volume:
-  `whole_ms`    edt.device.medial_axis (feature transform and step on the cached scratch; only the output is allocated);
+  `whole_ms`    edt.device.medial_axis (feature transform and step on the cached workspace; only the output is allocated);
   `ft_ms`       edt.device.feature_transform alone, as a user calls it (it allocates its workspace and reorders the planes);
-  `ft_call_ms`  edt_hip_feature_transform_device alone on the cached scratch: the part of `whole_ms` that is not the step;
+  `ft_call_ms`  edt_hip_feature_transform_device alone on planes and scratch kept here: the part of `whole_ms` that is not the step;
   `step_ms`     edt_hip_medial_axis_step_device alone, and the same with a radius output;
   `torch_ms`    the same stencil composed from torch operations on the feature tensor (fp64, one operation per product and sum,
                 so nothing is contracted).  Checked equal to the step's output, bit for bit, before anything is timed.
@@ -91,14 +91,20 @@ def main():
         whole = lambda: device.medial_axis(t, anisotropy=an)  # noqa: E731
         ft = lambda: device.feature_transform(t, anisotropy=an)  # noqa: E731
         a = whole()
-        s = device._medial_scratch(t, 3, ext, code, 0, False, True)
-        planes, ws, field = s["planes"], s["ws"], s["field"]
-        device._plan_for(ext, code, t.device).run(t, w, False, sqrt=True, out=field)
+        # (on tensors of its own: the planes, the transform's scratch and the field, as the composition makes them)
+        planes = torch.empty((3,) + tuple(t.shape), dtype=torch.int32, device=t.device)
+        ws = torch.empty(int(lib.edt_hip_feature_workspace_bytes(code, 3, *ext, 0)), dtype=torch.uint8, device=t.device)
+        field = device.Plan(ext, code).run(t, w, sqrt=True)
         out, radius = torch.empty_like(t), torch.empty_like(field)
         ft_call = lambda: _lib.check(lib.edt_hip_feature_transform_device(  # noqa: E731
             device._vp(t), code, 3, *ext, *w, 0, device._vp(planes), device._vp(ws), ws.numel(), device._stream_ptr()))
-        step = lambda: device._medial_step(t, 3, ext, w, planes, 0, gamma, ratio, out)  # noqa: E731
-        step_radius = lambda: device._medial_step(t, 3, ext, w, planes, 0, gamma, ratio, out, field, radius)  # noqa: E731
+
+        def medial_step(field=None, radius=None):
+            _lib.check(lib.edt_hip_medial_axis_step_device(
+                device._vp(t), code, 3, *ext, *w, device._vp(planes), 0, gamma, ratio, device._vp(out),
+                None if field is None else device._vp(field), None if radius is None else device._vp(radius), device._stream_ptr()))
+        step = lambda: medial_step()  # noqa: E731
+        step_radius = lambda: medial_step(field, radius)  # noqa: E731
         composed = lambda: torch_stencil(t, planes, w, gamma, ratio)  # noqa: E731
         ft_call()
         step()
@@ -127,8 +133,8 @@ def main():
                "bare_GBps": round(t.numel() * 12 / bm / 1e6, 1)}
         print(json.dumps(row), flush=True)
         rows.append(row)
-        del t, s, planes, ws, field, out, radius, x, y, z
-        device._medial_buffers.clear()
+        del t, planes, ws, field, out, radius, x, y, z
+        device._workspaces.clear()
         torch.cuda.empty_cache()
     print()
     print("| volume | on axis / foreground | device.medial_axis ms | device.feature_transform ms | transform call ms | step ms (min .. max) | "

@@ -84,15 +84,23 @@ def main():
             print(json.dumps({"volume": vol, "pass_times_of_the_last_binary_transform": device.pass_times()}), flush=True)
             lib.edt_hip_set_profiling(0)
         # the step kernel alone (radius 2, next radius 3), and a bare stream of 12 bytes per voxel
-        S, B, mask = device._thickness_scratch(t)
-        device._eroded_field(t, 3, (n, n, n), (1.0, 1.0, 1.0), False, False, S, mask)
+        # (on tensors of its own: S, the mask of radius 2 and its transform B, as the composition makes them)
+        S, B = (torch.empty(t.shape, dtype=torch.float32, device=t.device) for _ in range(2))
+        mask = torch.empty(t.shape, dtype=torch.uint8, device=t.device)
+        device.Plan((n, n, n), device.dtype_code(t.dtype)).run(t, (1.0, 1.0, 1.0), out=S)
         device._morph_select(_lib.U8, None, S, 2.0, _lib.MORPH_FARTHER, mask=mask)
-        device._plan_for((n, n, n), _lib.U8, t.device).run(mask, (1.0, 1.0, 1.0), False, out=B)
+        device.Plan((n, n, n), _lib.U8).run(mask, (1.0, 1.0, 1.0), out=B)
         T = torch.zeros(t.shape, dtype=torch.float32, device=t.device)
         size = torch.zeros(1, dtype=torch.int64, device=t.device)
-        step = lambda: device._thickness_step(S, B, 2.0, 3.0, T, mask=mask, size=size)  # noqa: E731
-        uncounted = lambda: device._thickness_step(S, B, 2.0, 3.0, T, mask=mask)  # noqa: E731
-        last = lambda: device._thickness_step(S, B, 2.0, None, T)  # noqa: E731
+
+        def thickness_step(next_radius, mask=None, size=None):
+            _lib.check(lib.edt_hip_thickness_step_device(
+                device._vp(S), device._vp(B), 2.0, -1.0 if next_radius is None else next_radius, device._vp(T),
+                None if mask is None else device._vp(mask), None if size is None else device._vp(size), None, S.numel(),
+                device._stream_ptr()))
+        step = lambda: thickness_step(3.0, mask, size)  # noqa: E731
+        uncounted = lambda: thickness_step(3.0, mask)  # noqa: E731
+        last = lambda: thickness_step(None)  # noqa: E731
         step()
         torch.cuda.synchronize()
         inside = int(size.item()) / t.numel()
@@ -108,7 +116,7 @@ def main():
         print(json.dumps(row), flush=True)
         rows.append(row)
         del t, S, B, mask, T, x, y, z
-        device._thickness_buffers.clear()
+        device._workspaces.clear()
         torch.cuda.empty_cache()
     print()
     print("| volume | ladder | radii | voxels in some opening / foreground | new ms (min .. max) | hand composition ms (min .. max) | new / hand |")
