@@ -1,6 +1,14 @@
 """CPU tier of the randomised runs of the label operations (tools/fuzz_ops.py): the same cases the GPU tier draws
 (tests/test_gpu_fuzz_ops.py: the same seeds), with the numpy oracles held against a second opinion -- scipy.ndimage and brute
-force -- so that the GPU tier does not rest on one restatement; and the generator held to what it promises to cover."""
+force -- so that the GPU tier does not rest on one restatement; and the generator held to what it promises to cover.
+
+Two families: the label operations (seeds 701..703; their draws are pinned by a digest, so that work on the generator cannot
+move them unnoticed) and the field operations erode / opening / dilate / closing / local_thickness / medial_axis (seeds
+711..713), whose second opinions are brute forces written from the definitions in exact integer arithmetic on the quanta of the
+voxel sizes, independent of both the compiled CPU transform and tests/ft_oracle.py."""
+import hashlib
+import itertools
+import math
 import os
 import sys
 
@@ -153,3 +161,283 @@ def test_generator_covers_what_it_promises():
     # the same seed draws the same cases
     again = list(fuzz_ops.cases(SEEDS[0], NCASES))
     assert all(np.array_equal(a["data"], b["data"], equal_nan=a["data"].dtype.kind == "f") for a, b in zip(again, drawn(SEEDS[0])))
+
+
+LABEL_DRAWS_SHA256 = "7c758e19b9538028084379d20e25eb2ed4c9918025ae03787c15a5f9145bf94e"
+
+
+def test_the_label_family_draws_have_not_moved():
+    """sha256 over describe(case) and the data bytes (memory order) of the 60 cases of seeds 701, 702 and 703, taken before the
+    generator learnt the field family: what the GPU tier has run so far is what it still runs"""
+    h = hashlib.sha256()
+    for seed in SEEDS:
+        for case in drawn(seed):
+            h.update(fuzz_ops.describe(case).encode())
+            h.update(case["data"].tobytes(order="A"))
+    assert h.hexdigest() == LABEL_DRAWS_SHA256
+
+
+# ---- the field family ---------------------------------------------------------------------------------------------------------
+FIELD_SEEDS = (711, 712, 713)   # (tests/test_gpu_fuzz_ops.py runs the same)
+_drawn_field = {}
+
+
+def drawn_field(seed):
+    if seed not in _drawn_field:
+        _drawn_field[seed] = list(fuzz_ops.cases(seed, NCASES, fuzz_ops.FIELD_OPS))
+    return _drawn_field[seed]
+
+
+def test_field_generator_covers_what_it_promises():
+    from test_gpu_feature_transform import QUANTUM
+    every = [c for seed in FIELD_SEEDS for c in drawn_field(seed)]
+    assert len(every) == 3 * NCASES
+    for op in fuzz_ops.FIELD_OPS:
+        mine = [c for c in every if c["op"] == op]
+        assert len(mine) == 3 * NCASES // 6, op
+        assert {c["data"].ndim for c in mine} == {1, 2, 3}, op
+        assert {c["order"] for c in mine} == {"C", "F"}, op
+        sx = [c["data"].shape[0] if c["order"] == "F" else c["data"].shape[-1] for c in mine]
+        assert 1 in sx and 64 in sx and 65 in sx and max(sx) >= 257, (op, sorted(sx))
+        assert all(c["data"].size <= fuzz_ops.CAP[op] for c in mine), op
+        assert {c["k"] for c in mine} == {0, 1, 2, 3}, op
+        assert any(c["host"] for c in mine), op
+        assert all(len(c["w_xyz"]) == len(c["a_xyz"]) == c["data"].ndim for c in mine), op
+        if op in fuzz_ops.TAKES_FLAGS:
+            assert {c["black_border"] for c in mine} == {False, True} and {c["binary"] for c in mine} == {False, True}, op
+        else:
+            assert not any("black_border" in c or c["binary"] for c in mine), op
+    assert {c["structure"] for c in every} == set(fuzz_ops.STRUCTURES)
+    assert len({c["data"].dtype for c in every}) == 11
+    assert any(c["data"].dtype.kind == "f" and np.isnan(c["data"]).any() for c in every)
+    assert {c["w_xyz"] for c in every if c["data"].ndim == 3} == set(QUANTUM) and len(QUANTUM) == 4 and (0.5, 0.5, 1.0) in QUANTUM
+    assert all(tuple(ac * min(c["w_xyz"]) ** 2 for ac in c["a_xyz"]) == tuple(w * w for w in c["w_xyz"]) for c in every)
+    for op in ("erode", "opening", "dilate", "closing"):
+        mine = [c for c in every if c["op"] == op]
+        assert any(c["radius"] == 0.0 for c in mine), op
+        assert all(c["radius"] == c["multiple"] * min(c["w_xyz"]) for c in mine), op
+        assert any(c["radius"] == np.inf for c in mine) == (op == "dilate"), op
+    assert {c["multiple"] for c in every if "multiple" in c} == set(fuzz_ops.RADIUS_MULTIPLES) | {np.inf}
+    ladders = [c["radii"] for c in every if c["op"] == "local_thickness"]
+    assert sum(r is None for r in ladders) == 12 and {len(r) for r in ladders if r is not None} == {1, 2, 3, 4}
+    assert all(r is None or all(x < y for x, y in zip(r, r[1:])) and r[0] > 0 for r in ladders)
+    axes = [c for c in every if c["op"] == "medial_axis"]
+    assert len({c["gamma"] is None for c in axes}) == 2 and any(c["gamma"] == 0.0 for c in axes)
+    assert any(c["gamma"] == 1.5 * min(c["w_xyz"]) for c in axes)
+    assert {c["min_angle"] for c in axes} == {0.0, 60.0, 120.0}
+    assert sum(c["return_distance"] for c in axes) == len(axes) // 2
+    again = list(fuzz_ops.cases(FIELD_SEEDS[0], NCASES, fuzz_ops.FIELD_OPS))
+    assert [fuzz_ops.describe(c) for c in again] == [fuzz_ops.describe(c) for c in drawn_field(FIELD_SEEDS[0])]
+    assert all(np.array_equal(a["data"], b["data"], equal_nan=a["data"].dtype.kind == "f") for a, b in zip(again, drawn_field(FIELD_SEEDS[0])))
+
+
+# The brute forces.  A volume is indexed x first (`_xyz`), `a` are the squared voxel sizes in quanta q = min(w)^2 (integers),
+# and a radius m * min(w) is the integer r4 = 4 m^2 (m is a multiple of 1/2; None: +inf): D(p, q) <= r^2 is
+# 4 * sum_c a_c (p_c - q_c)^2 <= r4, in Python / int64 integers throughout.
+BUDGET = 6 * 10**7      # voxels times offsets (erode, opening, local_thickness), or background times foreground voxels (dilate)
+
+
+def _xyz(case):
+    """the x-first view of the case's array, and the map of such a volume back onto the array's axes"""
+    data = case["data"]
+    return (data, lambda v: v) if case["order"] == "F" else (data.T, lambda v: v.T)
+
+
+def _r4(multiple):
+    return None if multiple == np.inf else int(round(4 * multiple * multiple))
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(f"u{a.dtype.itemsize}")
+
+
+def _fg(lab):
+    with np.errstate(invalid="ignore"):
+        return np.asarray(lab != 0)
+
+
+def ball_offsets(a, r4):
+    """the integer offsets o (x first) of the ball: 4 * sum_c a_c o_c^2 <= r4"""
+    reach = [math.isqrt(r4 // (4 * ac)) for ac in a]
+    return [o for o in itertools.product(*[range(-k, k + 1) for k in reach]) if 4 * sum(ac * d * d for ac, d in zip(a, o)) <= r4]
+
+
+def _pairs(shape, o):
+    """the slices of the voxels p whose q = p + o lies inside the array, and those of the q; None where there is no such p"""
+    if any(abs(d) >= s for s, d in zip(shape, o)):
+        return None
+    return (tuple(slice(max(0, -d), s - max(0, d)) for s, d in zip(shape, o)),
+            tuple(slice(max(0, d), s - max(0, -d)) for s, d in zip(shape, o)))
+
+
+def brute_erode(lab, a, r4, black_border, binary):
+    """the survivors: foreground voxels with no voxel of another label (binary: no background) at D <= r^2, the voxels outside
+    the array included under black_border"""
+    fg = _fg(lab)
+    alive = fg.copy()
+    for o in ball_offsets(a, r4):
+        if not any(o):
+            continue
+        ok = np.full(lab.shape, not black_border)                   # (what a p whose q lies outside gets)
+        pair = _pairs(lab.shape, o)
+        if pair:
+            with np.errstate(invalid="ignore"):
+                ok[pair[0]] = fg[pair[1]] if binary else (lab[pair[0]] == lab[pair[1]])
+        alive &= ok
+    return alive
+
+
+def brute_opening(lab, a, r4, black_border, binary):
+    """the union of the balls around the survivors, cut to the label"""
+    fg = _fg(lab)
+    alive = brute_erode(lab, a, r4, black_border, binary)
+    held = alive.copy()
+    for o in ball_offsets(a, r4):
+        pair = _pairs(lab.shape, o)
+        if any(o) and pair:
+            with np.errstate(invalid="ignore"):
+                mine = fg[pair[0]] if binary else (lab[pair[0]] == lab[pair[1]])
+            held[pair[0]] |= alive[pair[1]] & mine
+    return held
+
+
+def _selected(data, passes):
+    """the bits of `data` where `passes`, zero bits elsewhere"""
+    return np.where(passes, _bits(data), 0).astype(_bits(data).dtype)
+
+
+def brute_thickness(lab, a, r4s, step, black_border, binary):
+    """(T, radii, sizes) from brute-force openings; r4s None: the default ladder j = 1, 2, ... as long as some voxel's finite
+    squared distance exceeds (j step)^2, i.e. as long as the erosion by j steps leaves a survivor in a volume whose distances
+    are finite -- under a black border, or where not every voxel carries the one label.  None where the budget runs out."""
+    fg = _fg(lab)
+    spent = 0
+    T = np.zeros(lab.shape, dtype=np.float32)
+    radii, sizes = [], []
+    if r4s is None:
+        with np.errstate(invalid="ignore"):
+            uniform = lab.size == 1 or bool(fg.all() if binary else np.all(lab == lab.reshape(-1)[0]))
+        ladder = itertools.count(1) if black_border or not uniform else iter(())
+    else:
+        ladder = iter(r4s)
+    for t in ladder:
+        r4 = 4 * t * t if r4s is None else t
+        spent += 2 * len(ball_offsets(a, r4)) * lab.size
+        if spent > BUDGET:
+            return None
+        if r4s is None and not brute_erode(lab, a, r4, black_border, binary).any():
+            break
+        held = brute_opening(lab, a, r4, black_border, binary) & fg
+        radius = math.sqrt(r4 / 4.0) * step
+        radii.append(radius)
+        sizes.append(int(np.count_nonzero(held)))
+        T[held] = np.float32(radius)
+    return T, np.array(radii, dtype=np.float64), np.array(sizes, dtype=np.int64)
+
+
+def dilate_properties(lab, out, a, r4, what):
+    """every voxel `out` filled took the label of a foreground voxel at the brute-force minimum distance, and that distance is
+    <= r^2; every voxel left empty has no foreground within r; the foreground is untouched"""
+    fg = _fg(lab)
+    ib, ob = _bits(lab).reshape(-1), _bits(out).reshape(-1)
+    flat = fg.reshape(-1)
+    assert np.array_equal(ob[flat], ib[flat]), what
+    coords = np.stack(np.meshgrid(*[np.arange(s, dtype=np.int64) for s in lab.shape], indexing="ij"), -1).reshape(-1, lab.ndim)
+    src, src_bits = coords[flat], ib[flat]
+    weights = np.array(a, dtype=np.int64)
+    empty = np.nonzero(~flat)[0]
+    filled = _fg(out).reshape(-1)[empty]
+    if not len(src):
+        assert not filled.any() and np.array_equal(ob, ib), what
+        return
+    for lo in range(0, len(empty), 512):
+        rows = empty[lo:lo + 512]
+        D = (((coords[rows][:, None, :] - src[None, :, :]) ** 2) * weights).sum(-1)
+        nearest = D.min(1)
+        within = np.ones(len(rows), dtype=bool) if r4 is None else 4 * nearest <= r4
+        assert np.array_equal(filled[lo:lo + 512], within), what
+        took = ((D == nearest[:, None]) & (src_bits[None, :] == ob[rows][:, None])).any(1)
+        assert took[within].all() and np.array_equal(ob[rows][~within], ib[rows][~within]), what
+
+
+_checked_field = {}
+
+
+def field_second_opinions(seed):
+    if seed not in _checked_field:
+        _checked_field[seed] = _field_second_opinions(seed)
+    return _checked_field[seed]
+
+
+def _field_second_opinions(seed):
+    import medial_oracle
+    import morph_oracle
+    checked = dict.fromkeys(fuzz_ops.FIELD_OPS, 0)
+    for case in drawn_field(seed):
+        op, data = case["op"], case["data"]
+        what = fuzz_ops.describe(case)
+        lab, back = _xyz(case)
+        a = case["a_xyz"]
+        binary = case["binary"] or data.dtype == np.bool_
+        if op in ("erode", "opening"):
+            r4 = _r4(case["multiple"])
+            if len(ball_offsets(a, r4)) * data.size > BUDGET:
+                continue
+            brute = (brute_erode if op == "erode" else brute_opening)(lab, a, r4, case["black_border"], binary)
+            assert np.array_equal(_bits(fuzz_ops.want_of(case)), _selected(data, back(brute))), what
+            checked[op] += 1
+        elif op == "local_thickness":
+            r4s = None if case["multiples"] is None else [_r4(m) for m in case["multiples"]]
+            brute = brute_thickness(lab, a, r4s, min(case["w_xyz"]), case["black_border"], binary)
+            if brute is None:
+                continue
+            T, radii, sizes = fuzz_ops.want_of(case)
+            assert np.array_equal(radii, brute[1]) and np.array_equal(sizes, brute[2]), (what, radii, brute[1], sizes, brute[2])
+            assert T.dtype == np.float32 and np.array_equal(_bits(T), _bits(back(brute[0]))), what
+            checked[op] += 1
+        elif op == "dilate":
+            if int(np.count_nonzero(_fg(data))) * int(np.count_nonzero(~_fg(data))) > BUDGET:
+                continue
+            out = fuzz_ops.want_of(case)
+            dilate_properties(lab, out if case["order"] == "F" else out.T, a, _r4(case["multiple"]), what)
+            checked[op] += 1
+        elif op == "closing":
+            r4 = _r4(case["multiple"])
+            if len(ball_offsets(a, r4)) * data.size > BUDGET:
+                continue
+            out = fuzz_ops.want_of(case)
+            dilated = morph_oracle.dilate(data, case["radius"], fuzz_ops.axis_order(case, case["w_xyz"]))
+            grown = dilated if case["order"] == "F" else dilated.T
+            eroded = brute_erode(_fg(grown).astype(np.uint8), a, r4, False, True)
+            keep = _fg(data) | back(eroded)
+            assert np.array_equal(_fg(out), keep), what
+            assert np.array_equal(_bits(out), _selected(dilated, keep)), what           # (under the dilation's labels)
+            assert np.array_equal(_bits(out)[_fg(data)], _bits(data)[_fg(data)]), what  # no input voxel is lost
+            checked[op] += 1
+        elif data.size <= MEDIAL_SCATTER_VOXELS:
+            kw = fuzz_ops.field_kwargs(case, fuzz_ops.axis_order(case, case["w_xyz"]))
+            assert np.array_equal(medial_oracle.on_axis(data, form=medial_oracle.scatter, **kw),
+                                  medial_oracle.on_axis(data, form=medial_oracle.gather, **kw)), what
+            checked[op] += 1
+    return checked
+
+
+MEDIAL_SCATTER_VOXELS = 6000     # (the scatter form is a Python loop over the pairs of neighbours)
+
+
+@pytest.mark.parametrize("seed", FIELD_SEEDS)
+def test_field_oracles_against_a_second_opinion(seed):
+    checked = field_second_opinions(seed)
+    assert checked["erode"] == checked["opening"] == checked["closing"] == NCASES // 6, checked
+
+
+def test_field_second_opinions_reach_every_operation():
+    """over the three seeds, how many of the 30 cases of each operation the brute forces could afford to compare"""
+    total = dict.fromkeys(fuzz_ops.FIELD_OPS, 0)
+    for seed in FIELD_SEEDS:
+        for op, n in field_second_opinions(seed).items():
+            total[op] += n
+    assert all(n >= 5 for n in total.values()), total
+    assert total["erode"] == total["opening"] == total["closing"] == total["dilate"] == 30, total
+    assert total["local_thickness"] >= 28 and total["medial_axis"] >= 23, total       # (what the budgets leave of the 30 each)

@@ -2,7 +2,11 @@
 fill_holes, dust, label_stats, feature_transform and expand_labels through edt.device.* on device buffers at a random element
 offset (every fifth case through the host module as well), against the numpy oracles of tests/, bit for bit.  The oracles
 themselves are held against scipy and brute force on the same draws in the CPU tier (tests/test_fuzz_ops_cpu.py).  Every slice
-is a fresh process: 60 cases, ten per operation."""
+is a fresh process: 60 cases, ten per operation.
+
+A second family of slices, seeds 711..713, draws the field operations the same way: erode, opening, dilate, closing,
+local_thickness (with its sizes) and medial_axis (with its radius on every second case), at voxel sizes that share a quantum and
+radii that tie with the field on purpose."""
 import os
 import re
 import subprocess
@@ -14,8 +18,10 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEEDS = (701, 702, 703)        # (tests/test_fuzz_ops_cpu.py draws the same)
+FIELD_SEEDS = (711, 712, 713)  # (the same again)
 NCASES = 60
 OPS = ("connected_components", "fill_holes", "dust", "label_stats", "feature_transform", "expand_labels")
+FIELD_OPS = ("erode", "opening", "dilate", "closing", "local_thickness", "medial_axis")
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -31,3 +37,18 @@ def test_fuzz_ops_slice(edt_gpu, seed):
     assert lines[-1].startswith(f"{NCASES} cases, 0 mismatches"), tail
     counts = dict(re.findall(r"(\w+)=(\d+)", next(line for line in lines if line.startswith("ops:"))))
     assert counts == {op: str(NCASES // len(OPS)) for op in OPS}, counts
+
+
+@pytest.mark.parametrize("seed", FIELD_SEEDS)
+def test_fuzz_field_ops_slice(edt_gpu, seed):
+    e = dict(os.environ)
+    e.pop("EDT_HIP_DEBUG_MODE", None)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_ops.py"), str(NCASES), str(seed), "field"], cwd=ROOT,
+                         env=e, capture_output=True, text=True, timeout=300)
+    tail = (res.stdout + res.stderr)[-3000:]
+    assert res.returncode == 0, tail
+    assert "MISMATCH" not in res.stdout, tail
+    lines = res.stdout.strip().splitlines()
+    assert lines[-1].startswith(f"{NCASES} cases, 0 mismatches"), tail
+    counts = dict(re.findall(r"(\w+)=(\d+)", next(line for line in lines if line.startswith("ops:"))))
+    assert counts == {op: str(NCASES // len(FIELD_OPS)) for op in FIELD_OPS}, counts

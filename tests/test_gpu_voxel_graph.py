@@ -55,6 +55,40 @@ def test_native_vs_oracle_and_upsampled_fallback(edt_gpu, oracle_port, seed):
                               equal_nan=True)
 
 
+def test_graph_bytes_of_every_value(edt_gpu, oracle_port):
+    """`_graph` only ever clears 0x01, 0x04 and 0x10 from 0x3F, the three bits the reference reads (the first two in 2-D): a
+    kernel that consulted any other bit would pass everything above.  Here the graph bytes are uniform in 0..255 -- the -x / -y /
+    -z bits, the two bits no direction owns and, in 2-D, both z bits set and clear independently of the three that count -- on the
+    native form and on the up-sampled fallback."""
+    from edt import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(540)
+    seen, rich = set(), 0
+    for t in range(12):
+        dims = 2 if t % 3 == 0 else 3
+        shape = (70, 3, 33)[:dims] if t >= 10 else tuple(int(rng.integers(1, 44)) for _ in range(dims))
+        dtype = [np.uint8, np.uint16, np.uint32, np.uint64, np.float32, bool][t % 6]
+        m = blob_mask(shape, rng=rng, p=float(rng.uniform(0.7, 1.0)), block=int(rng.integers(2, 8)))
+        lab = (m * rng.integers(1, 5, size=shape)).astype(dtype)
+        g = rng.integers(0, 256, size=shape, dtype=np.uint8)
+        if t % 2:
+            lab, g = np.asfortranarray(lab), np.asfortranarray(g)
+        an = [(1.0, 1.0, 1.0), (2.0, 2.0, 3.0), (6.0, 6.0, 30.0), (0.7, 1.3, 2.1)][t % 4][:dims]
+        bb = bool(t % 4 < 2)
+        seen.update(np.unique(g).tolist())
+        want = oracle_port.edtsq(lab, an, bb, voxel_graph=g)
+        rich += len(np.unique(want)) >= 4
+        got = edt_gpu.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=g)
+        assert got.shape == want.shape and np.array_equal(got, want, equal_nan=True), (t, shape, dtype, an, bb, explain_vg(got, want))
+        lib.edt_hip_set_debug_mode(0x20000)  # the up-sampled formulation of this library
+        try:
+            old = edt_gpu.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=g)
+        finally:
+            lib.edt_hip_set_debug_mode(0)
+        assert np.array_equal(old, want, equal_nan=True), (t, shape, "fallback", explain_vg(old, want))
+    assert len(seen) == 256 and rich >= 10        # (ten of the twelve fields take four values or more)
+
+
 @pytest.mark.parametrize("shape", [(512, 40, 6), (9, 600, 5), (12, 7, 520), (260, 260, 3)])
 def test_native_long_axes(edt_gpu, oracle_port, shape):
     """doubled axes of 1024+ rows: the 2- and 1-column wave shapes of the column kernel"""

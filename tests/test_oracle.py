@@ -47,6 +47,31 @@ def test_golden_sdf_voxel_graph(oracle_port):
         assert same(got, c["out"])
 
 
+def test_voxel_graph_reads_three_bits_and_no_other(oracle_port):
+    """the oracle's field does not move when only the bits the reference ignores change -- everything but 0x01 / 0x04 / 0x10, and
+    0x10 too in 2-D --, and does move when one of those it reads is cleared (tests/test_gpu_voxel_graph.py draws whole bytes)"""
+    rng = np.random.default_rng(77)
+    moved = 0
+    for t, shape in enumerate([(9, 7), (1, 12), (14, 3), (6, 5, 7), (1, 8, 4), (11, 4, 5)]):
+        read = 0x05 if len(shape) == 2 else 0x15
+        lab = (rng.random(shape) < 0.9).astype([np.uint8, np.uint32, np.float32][t % 3])
+        lab = np.asfortranarray(lab) if t % 2 else lab
+        g = rng.integers(0, 256, size=shape, dtype=np.uint8)
+        g = np.asfortranarray(g) if t % 2 else g
+        an, bb = ((1.0, 1.0, 1.0), (2.0, 2.0, 3.0))[t % 2][:len(shape)], t % 4 < 2
+        want = oracle_port.edtsq(lab, an, bb, voxel_graph=g)
+        for other in (g & read, g | (0xFF & ~read), (g & read) | (rng.integers(0, 256, size=shape, dtype=np.uint8) & (0xFF & ~read))):
+            other = np.asarray(other, dtype=np.uint8, order="F" if t % 2 else "C")
+            assert same(oracle_port.edtsq(lab, an, bb, voxel_graph=other), want), (t, shape)
+        if 1 in shape:      # (under a black border across a unit extent every distance is half a voxel already)
+            continue
+        for bit in (0x01, 0x04, 0x10)[:len(shape)]:
+            moved += not same(oracle_port.edtsq(lab, an, bb, voxel_graph=np.asarray(g | read, dtype=np.uint8, order="F" if t % 2 else "C")),
+                              oracle_port.edtsq(lab, an, bb, voxel_graph=np.asarray((g | read) & (0xFF & ~bit), dtype=np.uint8,
+                                                                                    order="F" if t % 2 else "C")))
+    assert moved == 2 + 2 + 3 + 3
+
+
 # ---- known answers of the reference's own test-suite (automated_test.py) -----------------
 @pytest.mark.parametrize("dtype", ALL_TYPES)
 def test_one_d_known_answers(oracle_port, dtype):

@@ -1,19 +1,33 @@
 #!/usr/bin/env python3
-"""Seeded randomised runs of the label operations against their numpy oracles, bit for bit, in the manner of tools/fuzz_gpu.py:
-connected_components, fill_holes, dust, label_stats, feature_transform and expand_labels, round-robin.
+"""Seeded randomised runs of the label operations against their numpy oracles, bit for bit, in the manner of tools/fuzz_gpu.py.
+Two families, each round-robin over its operations:
 
-usage: python tools/fuzz_ops.py [ncases] [seed]
+  label   connected_components, fill_holes, dust, label_stats, feature_transform and expand_labels (OPS);
+  field   erode, opening, dilate, closing, local_thickness and medial_axis (FIELD_OPS): the compositions of
+          csrc/edt_fieldops.hip.
+
+usage: python tools/fuzz_ops.py [ncases] [seed] [label|field]
 
 One MISMATCH line per failing case, one line of per-operation counts, a last line `N cases, M mismatches`; the exit status is
-non-zero on any mismatch.  ``cases(seed, n)`` is the generator on its own (numpy only): the CPU tier draws the same inputs and
-holds the oracles against a second opinion (tests/test_fuzz_ops_cpu.py).
+non-zero on any mismatch.  ``cases(seed, n, ops)`` is the generator on its own (numpy only): the CPU tier draws the same inputs
+and holds the oracles against a second opinion (tests/test_fuzz_ops_cpu.py; label family: seeds 701..703, field family: seeds
+711..713).
 
 A case: 1 to 3 dimensions in C or F order; an x extent from the lengths where 64-voxel groups, 256-voxel cuts and row kernels
 change (or 1..90), the other extents 1..40, the last ones clipped to the case's cap; blocks, noise near the percolation
 threshold, a solid with pin-holes, per-voxel labels, a serpentine or a comb; each of the eleven label dtypes in turn, every
 fifth case with the full-width palette (extreme keys, NaN, -0.0); a connectivity 1..ndim, binary or not.  The call goes through
 edt.device.* on device buffers at a random element offset (tests/synth.py: offset_view; the buffers, surroundings included, must
-come back unchanged), every fifth case through the host module edt.* as well, and the two must agree."""
+come back unchanged), every fifth case through the host module edt.* as well, and the two must agree.
+
+A field case is drawn the same way and adds voxel sizes that share a quantum (the QUANTUM table of
+tests/test_gpu_feature_transform.py, cut to the dimensions), black_border and binary where the operation takes them, and a radius
+of 0, 1, 1.5, 2 or 3 times the smallest voxel size (+inf too for dilate): the integer multiples have squares that the field
+attains, so the `>` / `<=` ties of the selects are hit on purpose.  local_thickness takes the default ladder on every third case
+and 1 to 4 ascending radii of the same multiples otherwise, always with its sizes; medial_axis a gamma of None, 0 or 1.5 times the
+smallest voxel size, a min_angle of 0, 60 or 120 degrees, and the radius function on every second case.  erode, opening and
+local_thickness are held against the compiled CPU transform (tests/morph_oracle.py, tests/thickness_oracle.py), dilate, closing and
+medial_axis against the pure-Python feature transform (tests/ft_oracle.py, tests/medial_oracle.py), hence their smaller cap."""
 import os
 import sys
 import time
@@ -28,11 +42,17 @@ import numpy as np  # noqa: E402
 from synth import blocky_labels, palette  # noqa: E402
 
 OPS = ("connected_components", "fill_holes", "dust", "label_stats", "feature_transform", "expand_labels")
+FIELD_OPS = ("erode", "opening", "dilate", "closing", "local_thickness", "medial_axis")
+FAMILIES = {"label": OPS, "field": FIELD_OPS}
 COMPONENT_FAMILY = OPS[:3]
 X_EXTENTS = (1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1030)
 STRUCTURES = ("blocky", "noise", "pinholes", "per_voxel", "chain")
 CAP = {op: 60000 for op in OPS}
 CAP["feature_transform"] = CAP["expand_labels"] = 16000     # (their oracle is the slow one)
+CAP.update({op: 60000 for op in ("erode", "opening", "local_thickness")})       # (the compiled CPU transform)
+CAP.update({op: 16000 for op in ("dilate", "closing", "medial_axis")})          # (tests/ft_oracle.py: pure Python)
+RADIUS_MULTIPLES = (0.0, 1.0, 1.5, 2.0, 3.0)                # times the smallest voxel size
+TAKES_FLAGS = ("erode", "opening", "local_thickness", "medial_axis")            # black_border and binary
 
 
 def _tables():
@@ -108,28 +128,28 @@ def _typed(ids, dtype, full_width):
     return table[np.where(ids == 0, 0, 1 + (ids - 1) * stride % len(pal))]
 
 
-def cases(seed, n):
-    """The `n` cases of `seed`, as dicts: op, data (numpy, C or F order; axis 0 is x in F order, the last axis in C order),
-    connectivity, binary, k (element offset of the device buffers), host (also through the host module), and the operation's
-    own parameters in the order of the array's axes."""
+def cases(seed, n, ops=OPS):
+    """The `n` cases of `seed` over the family `ops`, as dicts: op, data (numpy, C or F order; axis 0 is x in F order, the last
+    axis in C order), connectivity, binary, k (element offset of the device buffers), host (also through the host module), and
+    the operation's own parameters: per-axis ones x first (w_xyz, a_xyz)."""
     DTYPES, QUANTUM = _tables()
     rng = np.random.default_rng(seed)
     for i in range(n):
-        op = OPS[i % len(OPS)]
-        j = i // len(OPS)                               # the operation's own case number
+        op = ops[i % len(ops)]
+        j = i // len(ops)                               # the operation's own case number
         # Stratified, so that a few short slices cover what a long run would: the dimensions and the connectivity go round with
         # the operation's case number, every second case takes the next entry of X_EXTENTS (consecutive seeds continue where
         # the last one stopped), and among the others every second one of the component family is grown past 2048 or 4096
         # voxels, so that chunk and span boundaries fall inside the volume.
         nd = 1 + (j + seed) % 3
         connectivity = 1 + (j // 3 + seed) % nd
-        turn = (j // 2 + 5 * seed + 3 * OPS.index(op)) if j % 2 == 0 else -1
+        turn = (j // 2 + 5 * seed + 3 * ops.index(op)) if j % 2 == 0 else -1
         at_least = 0
         if op in COMPONENT_FAMILY and j % 4 == 1:
             at_least = 4096 if j % 8 == 1 else 2048
         ext = _shape(rng, op, nd, at_least, turn)
         order = "F" if rng.random() < 0.5 or ext[0] == 1 else "C"        # (a C-ordered array whose last extent is 1 is F-ordered too)
-        structure = STRUCTURES[(j + i % len(OPS)) % len(STRUCTURES)]
+        structure = STRUCTURES[(j + i % len(ops)) % len(STRUCTURES)]
         dtype = DTYPES[i % len(DTYPES)]
         xyz = _typed(np.asarray(_ids(rng, ext, structure)), dtype, full_width=i % 5 == 4)     # indexed [x, y, z]
         data = np.asfortranarray(xyz) if order == "F" else np.ascontiguousarray(xyz.T)
@@ -153,12 +173,41 @@ def cases(seed, n):
         elif op == "expand_labels":
             case["distance"] = float(rng.choice([0.0, 1.0, 2.5, np.inf]))
             case["w_xyz"] = tuple(float(v) for v in rng.integers(1, 4, size=nd))
+        elif op in FIELD_OPS:
+            _field_parameters(case, rng, j, nd, QUANTUM)
         yield case
+
+
+def _field_parameters(case, rng, j, nd, QUANTUM):
+    """what a field case draws on top of the common part"""
+    op = case["op"]
+    w = list(QUANTUM)[int(rng.integers(0, len(QUANTUM)))]
+    case["w_xyz"], case["a_xyz"] = w[:nd], QUANTUM[w][:nd]
+    step = min(case["w_xyz"])
+    if op in TAKES_FLAGS:
+        case["black_border"] = bool(rng.integers(0, 2))
+    else:
+        case["binary"] = False                          # (dilate and closing take neither)
+    if op in ("erode", "opening", "dilate", "closing"):
+        multiples = RADIUS_MULTIPLES + ((np.inf,) if op == "dilate" else ())
+        case["multiple"] = float(multiples[int(rng.integers(0, len(multiples)))])
+        case["radius"] = case["multiple"] * step
+    elif op == "local_thickness":
+        case["multiples"] = None
+        if j % 3:
+            picked = rng.permutation(len(RADIUS_MULTIPLES) - 1)[:int(rng.integers(1, 5))]
+            case["multiples"] = tuple(RADIUS_MULTIPLES[1 + int(t)] for t in sorted(picked))
+        case["radii"] = None if case["multiples"] is None else tuple(m * step for m in case["multiples"])
+    else:
+        case["gamma"] = (None, 0.0, 1.5 * step)[int(rng.integers(0, 3))]
+        case["min_angle"] = (0.0, 60.0, 120.0)[int(rng.integers(0, 3))]
+        case["return_distance"] = j % 2 == 0
 
 
 def describe(case):
     d = case["data"]
-    extra = {k: v for k, v in case.items() if k in ("threshold", "invert", "w_xyz", "black_border", "distance")}
+    shown = ("threshold", "invert", "w_xyz", "black_border", "distance", "radius", "radii", "gamma", "min_angle", "return_distance")
+    extra = {k: v for k, v in case.items() if k in shown}
     return (f"#{case['index']} {case['op']} {d.shape} {case['order']} {d.dtype.name} {case['structure']} c={case['connectivity']} "
             f"binary={case['binary']} k={case['k']} host={case['host']} {extra}")
 
@@ -192,7 +241,42 @@ def expand_want(data, distance, a_xyz):
     return out
 
 
+def field_kwargs(case, anisotropy):
+    """the keyword arguments of a field case for edt.<op>, edt.device.<op> and the oracles alike"""
+    op = case["op"]
+    kw = dict(anisotropy=tuple(anisotropy))
+    if op in TAKES_FLAGS:
+        kw.update(black_border=case["black_border"], binary=case["binary"])
+    if op == "medial_axis":
+        kw.update(gamma=case["gamma"], min_angle=case["min_angle"])
+    return kw
+
+
+def field_want(case):
+    """erode / opening / dilate / closing: the array; local_thickness: (T, radii, sizes); medial_axis: (axis,) or (axis, radius)"""
+    import medial_oracle
+    import morph_oracle
+    import thickness_oracle
+    op, data = case["op"], case["data"]
+    kw = field_kwargs(case, axis_order(case, case["w_xyz"]))
+    if op in ("erode", "opening", "dilate", "closing"):
+        return getattr(morph_oracle, op)(data, case["radius"], **kw)
+    if op == "local_thickness":
+        return thickness_oracle.local_thickness(data, case["radii"], **kw)
+    on = medial_oracle.on_axis(data, **kw)
+    axis = data.copy(order="K")
+    axis[~on] = np.zeros((), dtype=data.dtype)
+    if not case["return_distance"]:
+        return (axis,)
+    # the radius function: the CPU transform of what the axis is the axis of, on the axis, and +0.0 off it
+    measured = morph_oracle.foreground(data) if (case["binary"] or data.dtype == np.bool_) else data
+    field = np.sqrt(morph_oracle.edtsq(measured, kw["anisotropy"], case["black_border"]))
+    return axis, np.where(on, field, np.float32(0.0))
+
+
 def want_of(case):
+    if case["op"] in FIELD_OPS:
+        return field_want(case)
     import components_oracle
     import dust_oracle
     import fill_holes_oracle
@@ -228,6 +312,20 @@ def _back(case, t):
     return a.T if case["order"] == "F" else a
 
 
+def _field_results(case, fn, x, kw, as_labels, as_floats):
+    """a field case through `fn` (edt.<op> or edt.device.<op>) on `x`, in the form of field_want"""
+    op = case["op"]
+    if op in ("erode", "opening", "dilate", "closing"):
+        return as_labels(fn(x, case["radius"], **kw))
+    if op == "local_thickness":
+        T, sizes = fn(x, case["radii"], return_sizes=True, **kw)
+        return as_floats(T), np.asarray(sizes.radii), as_floats(sizes.voxels)
+    if case["return_distance"]:
+        axis, radius = fn(x, return_distance=True, **kw)
+        return as_labels(axis), as_floats(radius)
+    return (as_labels(fn(x, **kw)),)
+
+
 def run_device(case):
     """the case through edt.device.* on buffers at element offset k; what want_of returns, plus whether the input buffers came
     back unchanged"""
@@ -240,7 +338,10 @@ def run_device(case):
     buf, t = offset_view(tdata, k)
     held = [(buf, buf.clone())]
     nd = data.ndim
-    if op == "connected_components":
+    if op in FIELD_OPS:
+        got = _field_results(case, getattr(device, op), t, field_kwargs(case, tuple(case["w_xyz"])[::-1]),
+                             lambda x: _back(case, x), lambda x: x.cpu().numpy().T if case["order"] == "F" else x.cpu().numpy())
+    elif op == "connected_components":
         out, n = device.connected_components(t, connectivity=c, binary=binary)
         got = (_back(case, out).view(np.uint32), int(n))
     elif op == "fill_holes":
@@ -274,6 +375,8 @@ def run_host(case):
     import edt
     import label_stats_oracle
     op, data, c, binary = case["op"], case["data"], case["connectivity"], case["binary"]
+    if op in FIELD_OPS:
+        return _field_results(case, getattr(edt, op), data, field_kwargs(case, axis_order(case, case["w_xyz"])), np.asarray, np.asarray)
     if op == "connected_components":
         return edt.connected_components(data, connectivity=c, binary=binary, return_N=True)
     if op == "fill_holes":
@@ -292,6 +395,18 @@ def agrees(case, got, want):
     """'' if `got` equals `want` bit for bit, else what differs"""
     import label_stats_oracle
     op = case["op"]
+    if op in FIELD_OPS:
+        got, want = (got if isinstance(got, tuple) else (got,)), (want if isinstance(want, tuple) else (want,))
+        names = {"local_thickness": ("the thickness", "the radii", "the sizes"), "medial_axis": ("the axis", "the radius")}
+        names = names.get(op, ("the volume",))
+        if len(got) != len(want):
+            return f"{len(got)} results, not {len(want)}"
+        for name, g, w in zip(names, got, want):
+            g, w = np.asarray(g), np.asarray(w)
+            if g.dtype != w.dtype or not same_bits(g, w):
+                differ = int(np.count_nonzero(g != w)) if g.shape == w.shape else -1
+                return f"{name} differs ({g.dtype.name}{g.shape} against {w.dtype.name}{w.shape}, {differ} elements)"
+        return ""
     if op == "label_stats":
         try:
             label_stats_oracle.assert_same(got, want)
@@ -310,9 +425,14 @@ def agrees(case, got, want):
 def main(argv):
     ncases = int(argv[1]) if len(argv) > 1 else 60
     seed = int(argv[2]) if len(argv) > 2 else 1
+    family = argv[3] if len(argv) > 3 else "label"
+    if family not in FAMILIES:
+        print(f"usage: {argv[0]} [ncases] [seed] [{'|'.join(FAMILIES)}]", file=sys.stderr)
+        return 2
+    ops = FAMILIES[family]
     bad, t0 = 0, time.time()
-    ran = dict.fromkeys(OPS, 0)
-    for case in cases(seed, ncases):
+    ran = dict.fromkeys(ops, 0)
+    for case in cases(seed, ncases, ops):
         want = want_of(case)
         got, inputs_intact = run_device(case)
         why = agrees(case, got, want)
@@ -325,7 +445,7 @@ def main(argv):
         if why:
             bad += 1
             print("MISMATCH", describe(case), "--", why, flush=True)
-    print("ops:", " ".join(f"{op}={ran[op]}" for op in OPS))
+    print("ops:", " ".join(f"{op}={ran[op]}" for op in ops))
     print(f"{ncases} cases, {bad} mismatches, {time.time() - t0:.1f} s")
     return 1 if bad else 0
 
