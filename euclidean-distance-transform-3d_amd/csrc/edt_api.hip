@@ -417,6 +417,14 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
   // transposer carries the run starts alone -- 48 MiB less per 512^3 step (debug bit 0x400 keeps the planes)
   const bool skip_nz = q16_only && !signed_tf && !binary_yz && !(g_debug_mode & kDbgKeepPlanes);
   uint32_t *const nzy = skip_nz ? nullptr : p.nz_y, *const nzz = skip_nz ? nullptr : p.nz_z;
+  // ... and then the storage of the y foreground plane is nobody's: it takes the ROW FLAGS.  Pass X does not store the indices of
+  // a row without a run start -- its indices follow from x alone -- and says so in two words per (z, band of 32 rows), [z][band]
+  // [plain, plain_fg], the first 2 * bands * sz words of nz_y (which has sx words per (z, band): sx >= 4 here); pass Y puts the
+  // indices back while it fills its tile (edt_colq16.hip: q16_plain_quad).  Written by pass X, both words of every group, so the
+  // region needs no clearing.  Only where nothing else reads the indices: the integer kernel alone (q16_only: the fp32 kernel
+  // reads them too and knows nothing of the flags), unsigned and not binary_yz (skip_nz), one slab of indices, rows of one wave
+  // (sx <= 1024).  Everything else hands both kernels nullptr and stores every row.  (debug bit 0x800000: every row is stored.)
+  uint32_t *const rowflags = (skip_nz && p.xy_slab >= sz && sx <= 1024 && !(g_debug_mode & kDbgStoreEveryRow)) ? p.nz_y : nullptr;
   if (index_form) {
     const int64_t sxy = sx * sy, wpl = p.gy.sx * p.gy.nbands;  // voxels / bit words per slice
     const size_t lsz = dtype_size(dtype);
@@ -434,6 +442,7 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
         slab.labels = lab; slab.halo = z0 > 0 ? lab - (size_t)sxy * lsz : nullptr; slab.sz = zc;
         slab.nz_y = nzy ? nzy + z0 * wpl : nullptr; slab.ys_y = p.rs_y + z0 * wpl; slab.zs_y = zpass ? p.zs_y + z0 * wpl : nullptr;
         slab.codes = slab_codes; slab.codes_pitch = p.code_pitch; slab.zero_label = zero_label;
+        slab.rowflags = rowflags;
         if ((rc = launch_row_pass_wave(slab)) != EDT_OK) return rc;
         if (binary_yz) {
           AxisGeom gb = p.gy;
@@ -449,6 +458,7 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
         cp.codes = slab_codes;
         cp.codes_outer = p.code_pitch;  // (the index buffer's own pitch: the outer stride of codes -- and of the plane written over them)
         cp.wx = wx;
+        cp.rowflags = rowflags;
         cp.plane = plane16 ? slab_codes : nullptr;
         // (the slab's first word in every x-tile's row of the plane's map: pass Y of the slabs after the first)
         if (p.codes_whole && !one) cp.map += z0 / 32;

@@ -62,6 +62,9 @@ namespace edt_amd {
 
 struct Q16Args {
   const uint16_t *codes;  // index form of pass X: [outer][row][x] with the strides of F; nullptr: F holds fp32 values
+  // ... whose PLAIN rows pass X did not store (edt_rowwave.hip: rowflags): [outer][band][plain, plain_fg] words, bit r = row
+  // 32 band + r.  The indices of such a row come from q16_plain_quad, never from codes.  nullptr: every row is in codes.
+  const uint32_t *rowflags;
   float q, rq;            // the quantum and its reciprocal (rounded; the conversion is verified value by value)
   uint32_t a;             // c_d = a * d^2 quanta
   uint32_t ain;           // index form: N = k^2 * ain
@@ -100,6 +103,32 @@ namespace {
 // what a wide image word holds for an index of pass X / a value of the 16-bit plane: 0xFFFF is +inf in either
 __device__ __forceinline__ uint32_t q16_index_value(uint32_t k, uint32_t ain) { return k == 0xFFFFu ? edt_q16::kInfW : k * k * ain; }
 __device__ __forceinline__ uint32_t q16_plane_value(uint32_t v) { return v == 0xFFFFu ? edt_q16::kInfW : v; }
+
+// ---- plain rows: rows in which pass X found no run start and stored nothing (Q16Args::rowflags) ----
+typedef uint32_t q16_v2u __attribute__((ext_vector_type(2)));
+// what pass X stores for the voxels x .. x + 3 of a row that is one run from end to end, packed like a fill load: background 0;
+// with a black border min(x + 1, sx - x) (il = x - pre0 + 1, ir = suf0 - x with pre0 = 0, suf0 = sx); without one 0xFFFF
+template <bool BB>
+__device__ __forceinline__ q16_v2u q16_plain_quad(bool fg, int x, int sx) {
+  if (!fg) return (q16_v2u){0u, 0u};
+  if (!BB) return (q16_v2u){~0u, ~0u};
+  uint32_t k[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) k[c] = (uint32_t)(x + c + 1 < sx - x - c ? x + c + 1 : sx - x - c);
+  return (q16_v2u){k[0] | (k[1] << 16), k[2] | (k[3] << 16)};
+}
+// The ONE way to the indices of pass X outside the first fill's straight-line loads: W = 4: the packed indices of columns
+// x .. x + 3 of `row`; W = 1: the index of column x in the low half.  p: where (row, x) lies in codes; flags: the row flags of the
+// slice ([band][2]; nullptr: every row is stored).
+template <bool BB, int W>
+__device__ __forceinline__ q16_v2u q16_indices(const uint16_t *p, const uint32_t *flags, int row, int x, int sx) {
+  if (flags != nullptr) {
+    const uint32_t bit = 1u << (row & 31);
+    if (flags[2 * (row >> 5)] & bit) return q16_plain_quad<BB>((flags[2 * (row >> 5) + 1] & bit) != 0u, x, sx);
+  }
+  if constexpr (W == 4) return *reinterpret_cast<const q16_v2u *>(p);
+  else return (q16_v2u){*p, 0u};
+}
 
 __host__ __device__ constexpr int q16_lds_words(int NB) {
   // image (NB bands of 32 rows + 2 kPad rows, 16 words each) + run-start plane + lo/hi plane + break masks (16 pairs x 6
@@ -180,6 +209,18 @@ k_column_pass_q16(float *__restrict__ F, const uint32_t *__restrict__ rsbits, Ax
   // it), issued AHEAD of the fill's loads and put into LDS behind them: straight-line code, one trip to memory for all of it.
   // (Round 6: as a loop of load -> LDS store the compiler waited for each word before the next load and before the fill's first
   // load went out -- three dependent trips per tile, tools/yorder_probe.hip has the bare pattern at half the pass's time.)
+  // The row flags of the slice (index form; nullptr: pass X stored every row) go first: 2 NB <= 64 words, one vector load --
+  // lane l takes word min(l, 2 NB - 1) --, in flight together with the run-start words.  The fill waits for them alone.
+  const uint32_t *rflags = nullptr;
+  uint32_t rfw = 0u;
+  bool any_plain = false;  // a plain row among the tile's rows
+  const int rfk = (t & 63) < 2 * NB ? (t & 63) : 2 * NB - 1;
+  if constexpr (IN == kQ16InCodes) {
+    if (qa.rowflags != nullptr) {
+      rflags = qa.rowflags + o * (2 * NB);
+      rfw = rflags[rfk];
+    }
+  }
   uint32_t rsw[2];
   bool rsw_ok[2];
 #pragma unroll
@@ -207,17 +248,46 @@ k_column_pass_q16(float *__restrict__ F, const uint32_t *__restrict__ rsbits, Ax
     const uint16_t *src = qa.codes + x0 + o * qa.cd_outer + 4 * cg;
     const pk kmaxpk = pk_both(qa.kmax), kmaxw1pk = pk_both(qa.kmaxw + qa.inf_ok), ainpk = pk_both(qa.ain);
     const pk infadd = qa.inf_ok ? 0x00010001u : 0u;
+    // (the "plain" words are the even ones; workgroup-uniform: every wave holds the same words)
+    any_plain = rflags != nullptr && __ballot((rfk & 1) == 0 && rfw != 0u) != 0ull;
     {
       constexpr int i0 = 0;
-      // (every load from a valid address -- rows behind the column's end read its last row, columns behind the row's end the
-      // tile's first four -- and dropped afterwards: sixteen loads back to back, no branch between them)
-      const uint16_t *srcv = col_ok ? src : src - 4 * cg;
+      if (!any_plain) {
+        // (every load from a valid address -- rows behind the column's end read its last row, columns behind the row's end the
+        // tile's first four -- and dropped afterwards: sixteen loads back to back, no branch between them)
+        const uint16_t *srcv = col_ok ? src : src - 4 * cg;
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int row = i0 + RPS * j + r_in;
-        kk[j] = EDT_Q16_FILL_LOAD(reinterpret_cast<const v2u *>(srcv + (int64_t)(row < n ? row : n - 1) * st));
+        for (int j = 0; j < 16; ++j) {
+          const int row = i0 + RPS * j + r_in;
+          kk[j] = EDT_Q16_FILL_LOAD(reinterpret_cast<const v2u *>(srcv + (int64_t)(row < n ? row : n - 1) * st));
+        }
+        put_run_starts();
+      } else {
+        // The same sweep with the loads of plain rows switched off -- nothing was stored there -- and no branch between the
+        // sixteen: buffer loads over the tile's own bytes (rows 0 .. n - 1 of its 32 columns and what lies between them), with the
+        // offset of a load that must not happen put beyond the range: such a lane gets 0 and asks memory for nothing.  Rows behind
+        // the column's end and columns behind the row's end go the same way.  A wave's rows lie in one band per sweep (RPS = 32:
+        // band j; RPS = 64: band 2 j + hi), so the two flag words of a row are two lane reads.
+        const int hi = __builtin_amdgcn_readfirstlane(r_in >> 5);
+        uint32_t pm = 0u, pf = 0u;  // bit j: row RPS j + r_in is plain / is plain and not label 0
+        const __amdgpu_buffer_rsrc_t tile = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint16_t *>(qa.codes + x0 + o * qa.cd_outer), 0, (int)(((int64_t)(n - 1) * st + (cols_left < 32 ? cols_left : 32)) * 2), 0x00020000);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int row = i0 + RPS * j + r_in, band = (RPS / 32) * j + hi;  // (band <= 31: lanes 2 band, 2 band + 1 exist)
+          const uint32_t wp = __builtin_amdgcn_readlane(rfw, 2 * band), wf = __builtin_amdgcn_readlane(rfw, 2 * band + 1);
+          const uint32_t is = row < n ? (wp >> (r_in & 31)) & 1u : 0u;  // (lanes beyond word 2 NB - 1 repeat it: rows behind the end)
+          pm |= is << j;
+          pf |= (is & (wf >> (r_in & 31))) << j;
+          const uint32_t off = (is == 0u && row < n && col_ok) ? (uint32_t)((row * (int)st + 4 * cg) * 2) : 0x80000000u;
+          kk[j] = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(tile, off, 0, 0));
+        }
+        put_run_starts();
+        const v2u fgk = q16_plain_quad<BB>(true, (int)x0 + 4 * cg, (int)g.sx);  // (once per thread: its columns are the same in every row)
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if ((pm >> j) & 1u) kk[j] = ((pf >> j) & 1u) ? fgk : (v2u){0u, 0u};
       }
-      put_run_starts();
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int row = i0 + RPS * j + r_in;
@@ -434,7 +504,7 @@ k_column_pass_q16(float *__restrict__ F, const uint32_t *__restrict__ rsbits, Ax
         if constexpr (IN == kQ16InCodes) {
           const uint16_t *src = qa.codes + x0 + o * qa.cd_outer + 4 * cg;
           for (int row = r_in; row < n && notinf == 0u; row += RPS) {
-            const v2u kk = *reinterpret_cast<const v2u *>(src + (int64_t)row * st);
+            const v2u kk = q16_indices<BB, 4>(src + (int64_t)row * st, rflags, row, (int)x0 + 4 * cg, (int)g.sx);
             notinf |= ~(kk[0] & kk[1]);
           }
         } else {
@@ -462,7 +532,14 @@ k_column_pass_q16(float *__restrict__ F, const uint32_t *__restrict__ rsbits, Ax
             if (stays) atomicOr(qa.map + xt * qa.map_words + (int)(o >> 5), 1u << (o & 31));
             else atomicAnd(qa.map + xt * qa.map_words + (int)(o >> 5), ~(1u << (o & 31)));
           }
-          if (stays) return;
+          if (stays) {
+            // (... except in the plain rows, where pass X stored nothing: the tile's +inf goes there now, whole lines of all rows)
+            if (any_plain && col_ok) {
+              uint16_t *dst16 = qa.plane + x0 + o * qa.cd_outer + 4 * cg;
+              for (int row = r_in; row < n; row += RPS) *reinterpret_cast<v2u *>(dst16 + (int64_t)row * st) = (v2u){~0u, ~0u};
+            }
+            return;
+          }
         }
         const float finf = (epi & kEpiToInf) ? INFINITY : FLT_MAX;  // (sqrt of either is itself)
         float *dstF = F + x0 + o * g.outer_stride + 4 * cg;
@@ -742,7 +819,7 @@ k_column_pass_q16(float *__restrict__ F, const uint32_t *__restrict__ rsbits, Ax
                 for (int j = 0; j < 8; ++j) {
                   const int row = RPS * (jb + j) + r_in;
                   kk[j] = (v2u){0u, 0u};
-                  if (row < n && col_ok) kk[j] = *reinterpret_cast<const v2u *>(src + (int64_t)row * st);
+                  if (row < n && col_ok) kk[j] = q16_indices<BB, 4>(src + (int64_t)row * st, rflags, row, (int)x0 + 4 * cg, (int)g.sx);
                 }
   #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -803,7 +880,8 @@ k_column_pass_q16(float *__restrict__ F, const uint32_t *__restrict__ rsbits, Ax
               bool p16 = false;
               if constexpr (IN == kQ16InMixed) p16 = ((qa.map[xt * qa.map_words + (row >> 5)] >> (row & 31)) & 1u) != 0u;
               if constexpr (IN == kQ16InCodes) {
-                v = q16_index_value(qa.codes[x0 + o * qa.cd_outer + c + (int64_t)row * st], qa.ain);
+                v = q16_index_value(q16_indices<BB, 1>(qa.codes + x0 + o * qa.cd_outer + c + (int64_t)row * st, rflags, row, (int)x0 + (int)c, (int)g.sx)[0] & 0xFFFFu,
+                                    qa.ain);
               } else if (p16) {
                 v = q16_plane_value(qa.plane[x0 + o * qa.p_outer + c + (int64_t)row * qa.pst]);
               } else {
@@ -983,6 +1061,7 @@ int launch_column_pass_q16(const ColumnPass &cp, const Quantum &Q, int axis, Han
     return EDT_ERR_BAD_ARG;
   }
   qa.codes = codes;
+  qa.rowflags = codes != nullptr ? cp.rowflags : nullptr;
   qa.q = q;
   qa.rq = 1.0f / q;
   qa.a = a;

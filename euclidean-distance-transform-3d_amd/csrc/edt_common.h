@@ -41,7 +41,8 @@ enum : int {
   kDbgEveryRow = 0x40000,                            // (EDT_DIAG) output stride 2: every row evaluated, no integer column kernel
   kDbgFp32PassX = 0x100000,                          // fp32 form of pass X (no 16-bit indices)
   kDbgVgGather = 0x200000,                           // voxel graph: separate gather pass
-  // 0x400000, 0x800000: round 3's bracket-path experiment: no effect now, experiments/colwave_r03
+  // 0x400000: round 3's bracket-path experiment: no effect now, experiments/colwave_r03 (0x800000 was its second bit)
+  kDbgStoreEveryRow = 0x800000,                      // pass X stores the indices of plain rows too: no row-flag plane
   kDbgShortOnWave = 0x1000000,                       // short axes (<= 32 rows) stay on the wave kernel
   kDbgFp64Inexact = 0x2000000,   // inexact voxel sizes: fp64 candidates even where fp32 fma candidates are exact
   kDbgPhasedRows = 0x4000000,    // rows of 1025..2048 voxels: the workgroup-phased kernel of pass X, not the two-wave form

@@ -48,6 +48,9 @@ struct RowPass {
   uint16_t *codes = nullptr;   // index form: 16-bit distance indices go here INSTEAD of `out` (see XFuse) ...
   int64_t codes_pitch = 0;     // ... their slices this many elements apart (0: sx * sy)
   int zero_label = 0;          // label 0 is measured like every label (the signed transform; 2: nz_y keeps the true label != 0 bits)
+  // index form, rows of at most 1024 voxels, zero_label == 0: rows without a run start are not stored; two words per (z, band of
+  // 32 rows) say which ([z][band][plain, plain_fg]: edt_rowwave.hip) and the first column pass takes them (ColumnPass::rowflags)
+  uint32_t *rowflags = nullptr;
   // pass X is the call's LAST pass (a 1-D call): a row without a boundary keeps +inf, and the square root is taken here if asked
   bool last = false, last_sqrt = false;
   int64_t nrows() const { return sy * sz; }
@@ -190,6 +193,9 @@ struct ColumnPass {
   const uint16_t *codes = nullptr;
   int64_t codes_outer = 0;  // outer stride of codes (and of the plane written over them), 0: g.outer_stride
   float wx = 0.0f;          // voxel size of pass X
+  // ... and did not store its plain rows (RowPass::rowflags: [outer][band][2] words): the integer kernel puts their indices back
+  // from the flags.  Only where no tile can reach the fp32 kernel, which reads codes and knows nothing of this.
+  const uint32_t *rowflags = nullptr;
   // the 16-bit plane of the integer kernel (volumes whose indices fit one slab): with codes, the results stay 16-bit -- written
   // over the indices (plane == codes), the tile's bit set in map [x-tile][map_words]; without codes, every row is read from the
   // plane where map says so and from F elsewhere (the pass after such a pass).

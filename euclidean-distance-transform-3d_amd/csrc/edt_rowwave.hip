@@ -98,8 +98,13 @@ __global__ void __launch_bounds__((H >= 2 ? H : kRowWaves) * 64)
 k_row_pass_wave(const T *__restrict__ labels, float *__restrict__ out, uint32_t *__restrict__ nz_y,
                 uint32_t *__restrict__ ys_y, uint32_t *__restrict__ zs_y, int sx, int sy, int sz, float w,
                 int bb, int to_finite, int nby, int ngroups, int xcd_sched, const T *__restrict__ halo, int zero_label,
-                int64_t opitch) {
+                int64_t opitch, uint32_t *__restrict__ rowflags) {
   // (opitch: elements between the slices of `out` -- sx * sy, or the padded pitch of the index buffer: edt_api.hip, code_pitch)
+  // rowflags != nullptr (C16, H == 1, zero_label == 0: the host's part): a PLAIN row -- no run start anywhere in it, so every
+  // voxel carries the same label and its indices are a function of x alone: min(x + 1, sx - x) with a black border, 0xFFFF
+  // without, 0 for label 0 -- is not measured and not stored.  Its bit goes into two words per (z, band), [z][band][plain,
+  // plain_fg] (plain_fg: the row's label is not 0), and the first column pass puts the indices back from those
+  // (edt_colq16.hip: q16_plain_quad); what the index buffer holds in such a row is whatever it held before.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *Ttab = reinterpret_cast<float *>(smem);  // [sx + 3]: T[0..sx+1], then +inf
   int *xchg = reinterpret_cast<int *>(smem) + ((sx + 3 + 3) & ~3);  // H >= 2: [row parity][part][last, first] boundary positions
@@ -187,6 +192,9 @@ k_row_pass_wave(const T *__restrict__ labels, float *__restrict__ out, uint32_t 
     int pend[NC];  // results of the previous row, stored one iteration late (see below)
 #pragma unroll
     for (int c = 0; c < NC; ++c) pend[c] = 0;
+    const bool flag_rows = C16 && H == 1 && rowflags != nullptr;
+    uint32_t plain_w = 0, plain_fg_w = 0;  // bit r: row r of the group is plain / plain and not label 0 (wave-uniform)
+    int pend_row = -1;                     // the row `pend` belongs to; -1: none, or a plain one -- nothing of it is stored
 #pragma unroll 1
     for (int r = 0; r < nrows; ++r) {
       // ---- compares -> masks (SGPRs), bit words --------------------------------------------
@@ -211,8 +219,8 @@ k_row_pass_wave(const T *__restrict__ labels, float *__restrict__ out, uint32_t 
       all_fg |= keep_all;  // (zero_label: no voxel is zeroed)
       // ---- the previous row's results leave now: issued after this row's loads have been waited
       //      for and a whole distance stage before the next wait, they retire off the critical path
-      if (r > 0) {
-        const uint32_t poff = (uint32_t)((r - 1) * sx) * OB;
+      if (pend_row >= 0) {
+        const uint32_t poff = (uint32_t)(pend_row * sx) * OB;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
           const int x = xb + c * 64 + lane;
@@ -269,6 +277,19 @@ k_row_pass_wave(const T *__restrict__ labels, float *__restrict__ out, uint32_t 
           if (v > wave && first_v != kNone) suf_in = first_v;
         }
       }
+      // (a plain row -- wave-uniform: its two bits, no carries, no distances, and -- one iteration from now, or behind the loop -- no
+      // stores.  All of it behind the one test, so that a row with structure pays a compare for it)
+      if (flag_rows && any_start == 0) {
+        plain_w |= 1u << r;
+        plain_fg_w |= ((uint32_t)__ballot(cur[0] != T(0)) & 1u) << r;  // (the row's label, from its first voxel)
+        pend_row = -1;
+        // (nothing of `pend` is wanted any more: said here, or its registers stay live through the next row's loads -- NC more
+        // VGPRs, an occupancy step at NC = 16 and for 1- / 2- / 8-byte labels at NC = 8)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) pend[c] = 0;
+        continue;
+      }
+      pend_row = r;
       int pre[NC], suf[NC];
 #pragma unroll
       for (int c = 0; c < NC; ++c) { pre[c] = pre_in; suf[c] = suf_in; }
@@ -322,8 +343,8 @@ k_row_pass_wave(const T *__restrict__ labels, float *__restrict__ out, uint32_t 
         pend[c] = f;
       }
     }
-    {
-      const uint32_t poff = (uint32_t)((nrows - 1) * sx) * OB;
+    if (pend_row >= 0) {
+      const uint32_t poff = (uint32_t)(pend_row * sx) * OB;
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         const int x = xb + c * 64 + lane;
@@ -348,6 +369,12 @@ k_row_pass_wave(const T *__restrict__ labels, float *__restrict__ out, uint32_t 
         ys_y[wbase + x] = ys;
         if (HAS_Z) zs_y[wbase + x] = zs;
       }
+    }
+    // (both words of every group, zero bits behind a partial last band: the plane needs no clearing)
+    if (flag_rows && lane == 0) {
+      uint32_t *fw = rowflags + ((int64_t)z * nby + yb) * 2;
+      fw[0] = plain_w;
+      fw[1] = plain_fg_w;
     }
   }
 }
@@ -391,10 +418,12 @@ static int launch_row_wave_tn(const RowPass &rp) {
   float *const out = rp.codes != nullptr ? reinterpret_cast<float *>(rp.codes) : rp.out;
   const int64_t opitch = (rp.codes != nullptr && rp.codes_pitch > 0) ? rp.codes_pitch : sx * rp.sy;
   const bool full = sx == 64 * NC * H;
+  // (the row-flag plane belongs to the index form of one-wave rows whose label 0 is background: the kernel's argument)
+  uint32_t *const flags = (rp.codes != nullptr && H == 1 && rp.zero_label == 0) ? rp.rowflags : nullptr;
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVES * 64), lds, rp.stream, (const T *)rp.labels, out, rp.nz_y, rp.ys_y,
                        rp.zs_y, (int)sx, (int)rp.sy, (int)rp.sz, rp.w, rp.bb, rp.to_finite(), (int)nby, (int)ngroups, xcd_sched,
-                       (const T *)rp.halo, rp.zero_label, opitch);
+                       (const T *)rp.halo, rp.zero_label, opitch, flags);
   };
 #define LAUNCH(Z, F) do { if (rp.codes != nullptr) launch(k_row_pass_wave<T, NC, Z, F, true, H>); else launch(k_row_pass_wave<T, NC, Z, F, false, H>); } while (0)
   if (rp.zs_y != nullptr) { if (full) LAUNCH(true, true); else LAUNCH(true, false); }
