@@ -1,10 +1,9 @@
 // edt_labelstats.hip -- label_stats: per-label voxel count, maximum of a float field, its first argmax and the bounding box,
 // for every non-zero label at once, on device-resident data (include/edt_hip.h states the contract).
 //
-// Every label type is reduced to a 64-bit KEY: the value itself for integers, 1 for any non-zero bool byte, the bit pattern
-// for floats with -0.0 folded into 0 and NaN mapped to 0 (a NaN voxel belongs to no label).  Key 0 is background and the
-// empty-slot marker.  The float field is reduced through an order-preserving map to uint32 (f2ord), so that every reduction
-// is an integer min / max / add: the table does not depend on which thread arrived first.
+// Every label type is reduced to a 64-bit KEY (edt_labeltable.h, shared with label_moments: keys, the hash, the insertion, the
+// walk over the flattened volume, the sort key).  The float field is reduced through an order-preserving map to uint32
+// (f2ord), so that every reduction is an integer min / max / add: the table does not depend on which thread arrived first.
 //
 //   k_ls_clear   the global table (clear-on-use: a reused workspace needs no memset)
 //   k_ls_sweep1  count, max, bbox.  A wave takes 4 x 64 consecutive voxels per step, one voxel per lane and group.  Run starts
@@ -26,23 +25,17 @@
 // Global table: struct of arrays over `slots` (direct: 256 / 65536; hashed: a power of two >= 2 * max_labels).  Insertion is a
 // compare-and-swap on the key word with linear probing; the probe loop is bounded by the table size and leaves early once
 // the overflow word is set (more than max_labels distinct keys, or no free slot): no lane ever waits for another.
-#include "edt_api_internal.h"
+#include "edt_labeltable.h"
 
 namespace edt_amd {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kLsThreads = 256;            // 4 waves
-constexpr int kLsGroups = 4;               // 64-voxel groups per wave and step
-constexpr int kLsTile = 64 * kLsGroups;    // voxels per wave and step
 constexpr int kLsLdsSlots = 512;           // 22 KiB of LDS per workgroup
 constexpr int kLsLdsProbes = 8;
 constexpr int kLsBlocks1 = 256 * 7;         // sweep 1: the workgroups 256 compute units hold at 22 KiB of LDS each
 constexpr int kLsBlocks2 = 256 * 8;         // sweep 2
 constexpr int kLsCacheSlots = 256;          // sweep 2: look-ups a workgroup remembers (5 KiB of LDS)
 constexpr int kLsCacheProbes = 4;
-constexpr int64_t kLsMinSlots = 1024;
 
 struct LsTable {
   u64 *keys = nullptr, *counts = nullptr, *argidx = nullptr;
@@ -66,19 +59,11 @@ struct LsOut {
   int key_kind;  // 0: integer, 1: binary32 bits, 2: binary64 bits
 };
 
-// at most `voxels` labels exist: a larger max_labels buys nothing
-int64_t ls_cap(int64_t voxels, int64_t max_labels) { return std::min(max_labels, std::max<int64_t>(voxels, 1)); }
-
 LsTable carve_ls(void *ws, int dtype, int64_t cap) {
   LsTable t;
   t.cap = cap;
   t.direct = dtype_size(dtype) <= 2;
-  if (t.direct) {
-    t.slots = dtype_size(dtype) == 1 ? 256 : 65536;
-  } else {
-    t.slots = kLsMinSlots;
-    while (t.slots < 2 * cap) t.slots *= 2;
-  }
+  t.slots = ls_slots(dtype, cap);
   Carver c(ws);
   const size_t n = (size_t)t.slots;
   t.keys = c.take<u64>(n);
@@ -92,60 +77,9 @@ LsTable carve_ls(void *ws, int dtype, int64_t cap) {
   return t;
 }
 
-// ---- keys and the ordered float map ---------------------------------------------------------------------------------
-template <typename T, bool BOOL> __device__ __forceinline__ u64 ls_key(T v) { return BOOL ? (u64)(v != 0) : (u64)v; }
-template <> __device__ __forceinline__ u64 ls_key<float, false>(float v) {
-  return (v == v && v != 0.0f) ? (u64)__float_as_uint(v) : 0ull;
-}
-template <> __device__ __forceinline__ u64 ls_key<double, false>(double v) {
-  return (v == v && v != 0.0) ? (u64)__double_as_longlong(v) : 0ull;
-}
-
-// a < b  <=>  f2ord(a) < f2ord(b) for all non-NaN floats (-0.0 sorts just below +0.0); every non-NaN value maps above 0
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-__device__ __forceinline__ u64 d2ord(u64 b) { return b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull); }
-
-__device__ __forceinline__ u64 ls_hash(u64 h) {  // all 64 bits reach every bit of the result
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-
-template <typename V> __device__ __forceinline__ V ls_peek(const V *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 // monotone updates: a plain read first, the atomic only when it may change the word (a stale read costs one redundant atomic)
 __device__ __forceinline__ void ls_min(uint32_t *p, uint32_t v) { if (ls_peek(p) > v) atomicMin(p, v); }
 __device__ __forceinline__ void ls_max(uint32_t *p, uint32_t v) { if (ls_peek(p) < v) atomicMax(p, v); }
-
-// The slot of `key` (!= 0) in the global table, -1 if it has none (INSERT: and could get none -- the overflow word is set).
-template <bool INSERT>
-__device__ int64_t ls_find(const LsTable &t, u64 key) {
-  if (t.direct) return (int64_t)key;
-  const u64 mask = (u64)t.slots - 1;
-  u64 h = ls_hash(key) & mask;
-  for (int64_t p = 0; p < t.slots; ++p, h = (h + 1) & mask) {
-    u64 k = ls_peek(&t.keys[h]);
-    if (k == key) return (int64_t)h;
-    if (k == 0) {
-      if (!INSERT) return -1;
-      k = atomicCAS(&t.keys[h], 0ull, key);
-      if (k == 0) {
-        if (atomicAdd(&t.ctrl[0], 1ull) + 1 > (u64)t.cap) atomicMax(&t.ctrl[1], 1ull);
-        return (int64_t)h;
-      }
-      if (k == key) return (int64_t)h;
-    }
-    if ((p & 31) == 31 && ls_peek(&t.ctrl[1])) break;  // the table's contents no longer matter
-  }
-  if (INSERT) atomicMax(&t.ctrl[1], 1ull);
-  return -1;
-}
 
 __device__ void ls_global_add(const LsTable &t, u64 key, u64 count, uint32_t ord, uint32_t x0, uint32_t x1, uint32_t y0,
                               uint32_t y1, uint32_t z0, uint32_t z1) {
@@ -159,19 +93,6 @@ __device__ void ls_global_add(const LsTable &t, u64 key, u64 count, uint32_t ord
   ls_max(&t.bbox[3 * t.slots + s], y1);
   ls_min(&t.bbox[4 * t.slots + s], z0);
   ls_max(&t.bbox[5 * t.slots + s], z1);
-}
-
-// (x, y, z) += o voxels along the flattened volume; extents are below 2^31 (check_shape) and o <= 1024: 32-bit throughout
-__device__ __forceinline__ void ls_advance(uint32_t sx, uint32_t sy, uint32_t &x, uint32_t &y, uint32_t &z, uint32_t o) {
-  x += o;
-  if (x < sx) return;
-  uint32_t q = x / sx;
-  x -= q * sx;
-  y += q;
-  if (y < sy) return;
-  q = y / sy;
-  y -= q * sy;
-  z += q;
 }
 
 __global__ __launch_bounds__(256) void k_ls_clear(LsTable t) {
@@ -425,12 +346,7 @@ __global__ __launch_bounds__(kLsThreads) void k_ls_sweep2(const T *__restrict__ 
 
 // ---- finish ---------------------------------------------------------------------------------------------------------
 __device__ void ls_emit(const LsTable &t, const LsOut &o, int64_t slot, u64 key, int64_t rank) {
-  switch (o.key_bytes) {
-    case 1: ((uint8_t *)o.keys)[rank] = (uint8_t)key; break;
-    case 2: ((uint16_t *)o.keys)[rank] = (uint16_t)key; break;
-    case 4: ((uint32_t *)o.keys)[rank] = (uint32_t)key; break;
-    default: ((uint64_t *)o.keys)[rank] = (uint64_t)key; break;
-  }
+  ls_store_key(o.keys, o.key_bytes, rank, key);
   o.counts[rank] = (int64_t)t.counts[slot];
   o.max[rank] = ord2f(t.maxord[slot]);
   o.argmax[rank] = (int64_t)t.argidx[slot];
@@ -468,10 +384,6 @@ __global__ __launch_bounds__(256) void k_ls_compact(LsTable t) {
   if (i >= t.slots || t.keys[i] == 0) return;
   const u64 pos = atomicAdd(&t.ctrl[2], 1ull);
   if (pos < (u64)t.cap) t.list[pos] = (u64)i;
-}
-
-__device__ __forceinline__ u64 ls_sort_key(u64 key, int kind) {
-  return kind == 0 ? key : kind == 1 ? (u64)f2ord(__uint_as_float((uint32_t)key)) : d2ord(key);
 }
 
 // hashed table: the rank of an entry is the number of entries with a smaller sort key
@@ -576,7 +488,7 @@ int edt_hip_label_stats_device(const void *d_labels, int dtype, const float *d_d
     return rc;
   const LsTable t = carve_ls(d_workspace, dtype, ls_cap(voxels, max_labels));
   const LsOut o = {d_keys, d_counts, d_max, d_argmax, d_bbox, d_n_labels, dtype_size(dtype),
-                   dtype == EDT_F32 ? 1 : dtype == EDT_F64 ? 2 : 0};
+                   ls_key_kind(dtype)};
   switch (dtype) {
     case EDT_U8: return launch_ls_t<uint8_t, false>((const uint8_t *)d_labels, d_dt, voxels, sx, sy, t, o, stream);
     case EDT_BOOL: return launch_ls_t<uint8_t, true>((const uint8_t *)d_labels, d_dt, voxels, sx, sy, t, o, stream);

@@ -26,8 +26,9 @@ import multiprocessing
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _moments
 from ._lib import EdtHipError  # noqa: F401  (re-export)
+from ._moments import LabelMoments
 
 # a host that cannot run any transform fails HERE, with the reason (no built library; no GPU device node) -- _lib.probe_at_import
 _lib.probe_at_import()
@@ -37,7 +38,7 @@ __all__ = [
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
-    "label_stats", "connected_components", "fill_holes", "dust", "DustCounts",
+    "label_stats", "label_moments", "LabelMoments", "connected_components", "fill_holes", "dust", "DustCounts",
     "erode", "dilate", "opening", "closing", "local_thickness", "ThicknessSizes",
     "medial_axis",
 ]
@@ -319,6 +320,63 @@ def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, 
     if order == "C":                       # x is the LAST array axis
         lo, hi = lo[:, ::-1], hi[:, ::-1]
     return LabelStats(np.ascontiguousarray(keys), counts, mx, argmax, np.ascontiguousarray(lo), np.ascontiguousarray(hi))
+
+
+def label_moments(data, max_labels=None):
+    """Centroid and second moments of every label: one table row per distinct non-zero label of ``data`` (1-D to 3-D; contract:
+    include/edt_hip.h, "label_moments"), as the named tuple :class:`LabelMoments`
+    ``(labels, counts, first, second, centroid, covariance)`` of numpy arrays, every field per array axis -- the label values
+    ascending (signed dtypes in signed order), the voxel count, the EXACT raw first ``(n, ndim)`` and second ``(n, ndim, ndim)``
+    moments about the array's origin (int64), the centroid and the population covariance in voxel units (float64, each value
+    rounded once from exact integers; what ``cc3d.statistics`` and ``skimage.measure.regionprops`` call centroid and, up to the
+    trace, inertia tensor).  ``result.principal(anisotropy)`` gives the principal axes.  The labels cross to the device once and
+    one sweep reads them; only the table comes back.  ``-0.0`` is background and NaN voxels of float labels belong to no label.
+
+    ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x the room while it proves too
+    small; an explicit ``max_labels`` that proves too small raises ``ValueError``.  So does a volume with
+    ``voxels * (largest extent - 1)**2 >= 2**63`` (lines of millions of voxels): its sums would leave int64."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"label_moments: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    nd = data.ndim
+    if max_labels is not None and int(max_labels) < 1:
+        raise ValueError(f"label_moments: max_labels must be at least 1, got {max_labels}")
+    if data.size == 0:
+        _label_code(data)
+        return LabelMoments(np.zeros(0, dtype=data.dtype), np.zeros(0, dtype=np.int64), np.zeros((0, nd), dtype=np.int64),
+                            np.zeros((0, nd, nd), dtype=np.int64), np.zeros((0, nd), dtype=np.float64),
+                            np.zeros((0, nd, nd), dtype=np.float64))
+    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+    _moments.check_range(data.shape)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    voxels = data.size
+    if max_labels is not None:
+        cap = min(int(max_labels), voxels)
+    elif _lib.DTYPE_SIZE[code] <= 2:
+        cap = min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1)
+    else:
+        cap = min(voxels, 65536)
+    lib = _lib.load()
+    while True:
+        keys = np.empty(cap, dtype=buf.dtype)
+        counts, sums = np.empty(cap, dtype=np.int64), np.empty((cap, 9), dtype=np.int64)
+        centroid, central = np.empty((cap, 3), dtype=np.float64), np.empty((cap, 6), dtype=np.float64)
+        n = ctypes.c_int64(0)
+        _lib.check(lib.edt_hip_label_moments(_ptr(buf), code, nd, e[0], e[1], e[2], cap, _ptr(keys), _ptr(counts), _ptr(sums),
+                                             _ptr(centroid), _ptr(central), ctypes.byref(n)))
+        n = int(n.value)
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"label_moments: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    keys = keys[:n].view(data.dtype)       # (signed dtypes: the bit patterns back under their own type)
+    counts, sums, centroid, central = counts[:n], sums[:n], centroid[:n], central[:n]
+    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
+        perm = np.argsort(keys, kind="stable")
+        keys, counts, sums, centroid, central = keys[perm], counts[perm], sums[perm], centroid[perm], central[perm]
+    got = _moments.assemble(np.ascontiguousarray(keys), counts, sums, centroid, central, nd, order == "C")
+    return LabelMoments(*[np.ascontiguousarray(f) for f in got])
 
 
 _NEIGHBOUR_COUNTS = {2: {4: 1, 8: 2}, 3: {6: 1, 18: 2, 26: 3}}   # cc3d's spelling of the connectivity

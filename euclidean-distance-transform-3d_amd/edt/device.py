@@ -17,7 +17,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _moments
+from ._moments import LabelMoments
 
 _TORCH_CODE = {
     torch.uint8: _lib.U8, torch.int8: _lib.U8,
@@ -506,6 +507,64 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
     lo = bbox[:, 0:2 * nd:2].flip(1).contiguous()
     hi = bbox[:, 1:2 * nd:2].flip(1).contiguous()
     return LabelStats(keys, counts, mx, argmax, lo, hi)
+
+
+def _label_moments_raw(labels, nd, ext, cap):
+    """One call of edt_hip_label_moments_device: (n_labels, keys, counts, sums, centroid, central) with ``cap`` rows each."""
+    lib = _lib.load()
+    dev = labels.device
+    code = dtype_code(labels.dtype)
+    nbytes = lib.edt_hip_label_moments_workspace_bytes(code, labels.numel(), cap)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    keys = torch.empty(cap, dtype=labels.dtype, device=dev)
+    counts = torch.empty(cap, dtype=torch.int64, device=dev)
+    sums = torch.empty((cap, 9), dtype=torch.int64, device=dev)
+    centroid = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+    central = torch.empty((cap, 6), dtype=torch.float64, device=dev)
+    n = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(lib.edt_hip_label_moments_device(_vp(labels), code, nd, *ext, cap, _vp(keys), _vp(counts), _vp(sums), _vp(centroid),
+                                                _vp(central), _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
+    return int(n.item()), keys, counts, sums, centroid, central
+
+
+def label_moments(labels: torch.Tensor, max_labels=None) -> LabelMoments:
+    """Device-resident :func:`edt.label_moments`: one table row per distinct non-zero label in ONE streaming sweep over
+    ``labels``, nothing else is read (contract: include/edt_hip.h, "label_moments").  The named tuple
+    ``(labels, counts, first, second, centroid, covariance)`` of device tensors, every field per tensor axis: the label values
+    ascending (signed dtypes in signed order), the voxel count, the exact raw first ``(n, ndim)`` and second ``(n, ndim, ndim)``
+    moments (int64), centroid and population covariance in voxel units (float64).  The table stays on the device; the only
+    host synchronisation is reading the number of labels.  ``max_labels`` and the range bound: as :func:`edt.label_moments`."""
+    labels = as_device_tensor(labels)
+    if labels.dim() < 1 or labels.dim() > 3:
+        raise TypeError(f"label_moments: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    if max_labels is not None and int(max_labels) < 1:
+        raise ValueError(f"label_moments: max_labels must be at least 1, got {max_labels}")
+    nd = labels.dim()
+    dev = labels.device
+    code = dtype_code(labels.dtype)
+    voxels = labels.numel()
+    if voxels == 0:
+        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+        return LabelMoments(z(labels.dtype, 0), z(torch.int64, 0), z(torch.int64, 0, nd), z(torch.int64, 0, nd, nd),
+                            z(torch.float64, 0, nd), z(torch.float64, 0, nd, nd))
+    _moments.check_range(labels.shape)
+    labels = labels.contiguous()
+    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
+    cap = default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
+    while True:
+        n, keys, counts, sums, centroid, central = _label_moments_raw(labels, nd, ext, cap)
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"label_moments: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    keys, counts, sums, centroid, central = keys[:n], counts[:n], sums[:n], centroid[:n], central[:n]
+    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
+        perm = torch.argsort(keys, stable=True)
+        keys, counts, sums, centroid, central = keys[perm], counts[perm], sums[perm], centroid[perm], central[perm]
+    return _moments.assemble(keys, counts, sums, centroid, central, nd, True)
 
 
 _workspaces: dict = {}         # query name -> {(bytes, device, stream): scratch}

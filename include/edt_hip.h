@@ -462,6 +462,45 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
                         float wz, int black_border, const float *dt, int64_t max_labels, void *keys, int64_t *counts,
                         float *max, int64_t *argmax, int32_t *bbox, int64_t *n_labels);
 
+/* ---- label_moments: exact raw moments, centroid and covariance of every label ----------------------------------------
+ * Conventions, keys, order, capacity, *n_labels and overflow behaviour are label_stats': x fastest, idx = x + sx * (y + sy * z),
+ * label 0 is background, integers at full width, bool: any non-zero byte is key 1, -0.0 is background, a NaN voxel belongs to
+ * no label; ascending key; the arrays hold max_labels entries (sums 9 *, centroid 3 *, central 6 * max_labels), and with
+ * more distinct labels *n_labels is SOME value greater than max_labels, the contents are unspecified and the call returns
+ * EDT_OK.  The table has one entry for each distinct non-zero label L, over the voxels p = (x, y, z) with label L:
+ *   key       L, in the labels' dtype;
+ *   count     n, the number of those voxels (int64);
+ *   sums      nine int64 in the order Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz: the raw moments about the volume's origin in
+ *             voxel index units (Sxy = sum of x * y ...), exact;
+ *   centroid  three fp64: fl(fl(S_a) / fl(n)) -- fl of a 64-bit integer is its one round-to-nearest-even conversion, the
+ *             division is IEEE binary64; unused axes give 0.0;
+ *   central   six fp64 in the order xx, yy, zz, xy, xz, yz: the population covariance in voxel units,
+ *             fl(fl(fl(M_ab) / fl(n)) / fl(n)) with M_ab = n * S_ab - S_a * S_b taken EXACTLY as a signed 128-bit integer and
+ *             converted once, round to nearest even, its sign apart.  Nothing subtracts two rounded numbers: an elongated
+ *             object far from the origin gets the relative accuracy of one at the origin.
+ * Determinism: the same call gives the same table, bit for bit (64-bit integer adds and a compare-and-swap on the key).
+ * Range: a volume with voxels * (E - 1)^2 >= 2^63, E the largest extent, is refused with EDT_ERR_UNSUPPORTED before any
+ * device work (outputs and scratch untouched; the test is made in 128-bit arithmetic).  Below the bound every sum fits int64
+ * and every M_ab 128 bits.  Every 3-D shape the tiled kernels accept is far inside; only lines of millions of voxels are not. */
+
+/* Scratch of edt_hip_label_moments_device: nothing per voxel; label_stats' tables with wider slots -- 256 / 65536
+ * direct-indexed slots for 8- / 16-bit labels, else an open-addressing hash table of the power of two >= max(1024,
+ * 2 * max_labels) slots; 88 bytes per slot (the key and ten 64-bit sums), plus 8 bytes per label (a max_labels above
+ * `voxels` counts as `voxels`).  0 for a bad dtype or max_labels < 1. */
+size_t edt_hip_label_moments_workspace_bytes(int dtype, int64_t voxels, int64_t max_labels);
+/* ndim 1..3, unused extents 1, max_labels >= 1; NULL pointers and a missing, too small or misaligned scratch (d_scratch is
+ * the call's workspace: 256-byte aligned, at least the query's bytes) are EDT_ERR_BAD_ARG before any device work.
+ * Enqueue-only on `stream`: no allocation, no synchronisation; the scratch is cleared by the call itself (a reused one needs
+ * no memset), so the call can be captured.  d_n_labels: one int64 on the device. */
+int edt_hip_label_moments_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                                 int64_t max_labels, void *d_keys, int64_t *d_counts, int64_t *d_sums /* 9*max_labels */,
+                                 double *d_centroid /* 3*max_labels */, double *d_central /* 6*max_labels */,
+                                 int64_t *d_n_labels, void *d_scratch, size_t scratch_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device).  The labels cross once; only the table is copied back. */
+int edt_hip_label_moments(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
+                          void *keys, int64_t *counts, int64_t *sums, double *centroid, double *central, int64_t *n_labels);
+
 /* ---- connected components: multi-label component labelling on the device ---------------------------------------------
  * Conventions as above: x fastest, idx = x + sx * (y + sy * z), label 0 is background.
  * Adjacency: connectivity = c, 1 <= c <= ndim.  Two voxels are neighbours if their coordinates differ by at most 1 along
