@@ -61,6 +61,9 @@ int medial_check_args(int flags, double gamma, double ratio, double *g2);
 // What label_moments refuses after the shape, on host buffers and on device-resident data alike (edt_moments.hip): a bad
 // max_labels (EDT_ERR_BAD_ARG), a volume past the range bound of its exact sums (EDT_ERR_UNSUPPORTED).
 int moments_check_args(int64_t sx, int64_t sy, int64_t sz, int64_t max_labels);
+// What label_topology refuses after the shape, on host buffers and on device-resident data alike (edt_topology.hip): a bad
+// max_labels (EDT_ERR_BAD_ARG).
+int topology_check_args(int64_t max_labels);
 // whether [p, p + pb) and [q, q + qb) share a byte (an empty range shares none)
 inline bool ranges_overlap(const void *p, size_t pb, const void *q, size_t qb) {
   const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);

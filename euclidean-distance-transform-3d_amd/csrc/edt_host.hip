@@ -432,6 +432,43 @@ static int label_moments_host(const void *labels, int dtype, int ndim, int64_t s
   return st.down(central, kAux, m * 48, o_central);
 }
 
+// label_topology on host buffers (kernels: edt_topology.hip): labels up once, the sweep on the device, and only the table comes back.
+static int label_topology_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
+                               void *keys, int64_t *closed, int64_t *interior, int64_t *n_labels) {
+  int64_t cap = 0;
+  size_t sbytes = 0;
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !keys || !closed || !interior, &empty, [&](After what) -> int {
+    if (what == After::shape) return topology_check_args(max_labels);
+    if (what == After::voxel_sizes && !n_labels) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    if (what == After::pointers) {  // (the volume is not empty here)
+      cap = std::min(max_labels, sx * sy * sz);
+      sbytes = edt_hip_label_topology_workspace_bytes(dtype, sx * sy * sz, cap);
+    }
+    return EDT_OK;
+  });
+  if (rc == EDT_OK && empty && (rc = require_device()) == EDT_OK) *n_labels = 0;  // (the device form's answer to an empty volume)
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
+  // the table on the device, 8-byte items throughout but the keys: keys | closed | interior | n
+  const size_t n = (size_t)cap, ksz = (size_t)dtype_size(dtype);
+  const size_t o_closed = align_up(n * ksz, 8), o_interior = o_closed + 64 * n, o_n = o_interior + 64 * n, obytes = o_n + 8;
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kWorkspace, sbytes}, {kAux, obytes}})) != EDT_OK) return rc;
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  char *tab = st.at<char>(kAux);
+  rc = edt_hip_label_topology_device(st.p[kLabels], dtype, ndim, sx, sy, sz, cap, tab, (int64_t *)(tab + o_closed),
+                                     (int64_t *)(tab + o_interior), (int64_t *)(tab + o_n), st.p[kWorkspace], sbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(n_labels, kAux, sizeof(int64_t), o_n)) != EDT_OK) return rc;
+  if (*n_labels > cap) return EDT_OK;  // not an error: the caller retries with more room
+  const size_t m = (size_t)*n_labels;
+  if (m == 0) return EDT_OK;
+  if ((rc = st.down(keys, kAux, m * ksz)) != EDT_OK || (rc = st.down(closed, kAux, m * 64, o_closed)) != EDT_OK) return rc;
+  return st.down(interior, kAux, m * 64, o_interior);
+}
+
 // connected_components, fill_holes and dust on host buffers (kernels: edt_components.hip, edt_fillholes.hip, edt_dust.hip):
 // labels up once, the operation on the device, its output and its int64 results down once.  What tells the three apart:
 enum class Alias { ignored /* the output is of another type */, refused, in_place /* the result pages are the labels', and being read: no first touch */ };
@@ -626,6 +663,11 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
 int edt_hip_label_moments(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
                           void *keys, int64_t *counts, int64_t *sums, double *centroid, double *central, int64_t *n_labels) {
   return label_moments_host(labels, dtype, ndim, sx, sy, sz, max_labels, keys, counts, sums, centroid, central, n_labels);
+}
+
+int edt_hip_label_topology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
+                           void *keys, int64_t *closed, int64_t *interior, int64_t *n_labels) {
+  return label_topology_host(labels, dtype, ndim, sx, sy, sz, max_labels, keys, closed, interior, n_labels);
 }
 
 int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,

@@ -26,9 +26,10 @@ import multiprocessing
 
 import numpy as np
 
-from . import _lib, _moments
+from . import _lib, _moments, _topology
 from ._lib import EdtHipError  # noqa: F401  (re-export)
 from ._moments import LabelMoments
+from ._topology import LabelTopology
 
 # a host that cannot run any transform fails HERE, with the reason (no built library; no GPU device node) -- _lib.probe_at_import
 _lib.probe_at_import()
@@ -38,7 +39,8 @@ __all__ = [
     "edt1d", "edt1dsq", "edt2d", "edt2dsq", "edt3d", "edt3dsq",
     "each", "edt_stack", "edtsq_stack", "binary_edt", "binary_edtsq", "set_devices", "EdtHipError",
     "runs", "draw", "transfer", "erase", "reshape", "nvl", "feature_transform", "expand_labels",
-    "label_stats", "label_moments", "LabelMoments", "connected_components", "fill_holes", "dust", "DustCounts",
+    "label_stats", "label_moments", "LabelMoments", "label_topology", "LabelTopology",
+    "connected_components", "fill_holes", "dust", "DustCounts",
     "erode", "dilate", "opening", "closing", "local_thickness", "ThicknessSizes",
     "medial_axis",
 ]
@@ -377,6 +379,63 @@ def label_moments(data, max_labels=None):
         keys, counts, sums, centroid, central = keys[perm], counts[perm], sums[perm], centroid[perm], central[perm]
     got = _moments.assemble(np.ascontiguousarray(keys), counts, sums, centroid, central, nd, order == "C")
     return LabelMoments(*[np.ascontiguousarray(f) for f in got])
+
+
+def label_topology(data, max_labels=None):
+    """Euler numbers and surface of every label: one table row per distinct non-zero label of ``data`` (1-D to 3-D; contract:
+    include/edt_hip.h, "label_topology"), as the named tuple :class:`LabelTopology` ``(labels, counts, closed, interior)`` of
+    numpy arrays -- the label values ascending (signed dtypes in signed order), the voxel count, and two int64 tables of shape
+    ``(n,) + (2,) * ndim`` indexed per array axis (index 1: the cell extends along that axis): ``closed`` counts the vertices,
+    edges, faces and cubes with at least one incident voxel of the label (8- / 26-adjacency), ``interior`` those whose
+    incident voxels all carry it (4- / 6-adjacency).  Positions outside the array hold no label.  ``result.euler(connectivity)``
+    is components - tunnels + cavities (what ``skimage.measure.euler_number`` gives label by label),
+    ``result.intrinsic_volumes(anisotropy)`` the four Minkowski functionals up to their constants and
+    ``result.surface_area(anisotropy)`` the area of the exposed VOXEL FACES: exact and additive, and not an estimate of a smooth
+    surface's area, to which it does not converge (about 1.5 times larger for a ball).  Every count is an exact integer, the
+    same bits on every run.  The labels cross to the device once and one sweep reads them; only the table comes back.  ``-0.0``
+    is background and NaN voxels of float labels belong to no label.
+
+    ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x the room while it proves too
+    small; an explicit ``max_labels`` that proves too small raises ``ValueError``."""
+    data = np.asarray(data)
+    if data.ndim < 1 or data.ndim > 3:
+        raise TypeError(f"label_topology: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
+    nd = data.ndim
+    if max_labels is not None and int(max_labels) < 1:
+        raise ValueError(f"label_topology: max_labels must be at least 1, got {max_labels}")
+    if data.size == 0:
+        _label_code(data)
+        return LabelTopology(np.zeros(0, dtype=data.dtype), np.zeros(0, dtype=np.int64), np.zeros((0,) + (2,) * nd, dtype=np.int64),
+                             np.zeros((0,) + (2,) * nd, dtype=np.int64))
+    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    voxels = data.size
+    if max_labels is not None:
+        cap = min(int(max_labels), voxels)
+    elif _lib.DTYPE_SIZE[code] <= 2:
+        cap = min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1)
+    else:
+        cap = min(voxels, 65536)
+    lib = _lib.load()
+    while True:
+        keys = np.empty(cap, dtype=buf.dtype)
+        closed, interior = np.empty((cap, 8), dtype=np.int64), np.empty((cap, 8), dtype=np.int64)
+        n = ctypes.c_int64(0)
+        _lib.check(lib.edt_hip_label_topology(_ptr(buf), code, nd, e[0], e[1], e[2], cap, _ptr(keys), _ptr(closed), _ptr(interior),
+                                              ctypes.byref(n)))
+        n = int(n.value)
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"label_topology: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    keys = keys[:n].view(data.dtype)       # (signed dtypes: the bit patterns back under their own type)
+    closed, interior = closed[:n], interior[:n]
+    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
+        perm = np.argsort(keys, kind="stable")
+        keys, closed, interior = keys[perm], closed[perm], interior[perm]
+    got = _topology.assemble(np.ascontiguousarray(keys), closed, interior, nd, order == "C")
+    return LabelTopology(*[np.ascontiguousarray(f) for f in got])
 
 
 _NEIGHBOUR_COUNTS = {2: {4: 1, 8: 2}, 3: {6: 1, 18: 2, 26: 3}}   # cc3d's spelling of the connectivity

@@ -109,6 +109,9 @@ SIGNATURES = {
     "edt_hip_label_moments_workspace_bytes": (_sz, [_i, _i64, _i64]),
     "edt_hip_label_moments_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_label_moments": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "edt_hip_label_topology_workspace_bytes": (_sz, [_i, _i64, _i64]),
+    "edt_hip_label_topology_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "edt_hip_label_topology": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "edt_hip_components_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
     "edt_hip_connected_components_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_connected_components": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),

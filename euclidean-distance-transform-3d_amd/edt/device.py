@@ -17,8 +17,9 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, _moments
+from . import _lib, _moments, _topology
 from ._moments import LabelMoments
+from ._topology import LabelTopology
 
 _TORCH_CODE = {
     torch.uint8: _lib.U8, torch.int8: _lib.U8,
@@ -599,6 +600,45 @@ def _label_op_tensor(labels, who):
 
 def _vp(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+def label_topology(labels: torch.Tensor, max_labels=None) -> LabelTopology:
+    """Device-resident :func:`edt.label_topology`: one table row per distinct non-zero label in ONE sweep over ``labels``,
+    nothing else is read (contract: include/edt_hip.h, "label_topology").  The named tuple ``(labels, counts, closed, interior)``
+    of device tensors: the label values ascending (signed dtypes in signed order), the voxel count and the two int64 cell-count
+    tables of shape ``(n,) + (2,) * ndim`` per tensor axis.  ``euler``, ``intrinsic_volumes`` and ``surface_area`` of the result
+    bring the table to the host.  The table stays on the device; the only host synchronisation is reading the number of labels.
+    The scratch is cached per size and stream.  ``max_labels``: as :func:`edt.label_topology`."""
+    labels, nd, code, ext = _label_op_tensor(labels, "label_topology")
+    if max_labels is not None and int(max_labels) < 1:
+        raise ValueError(f"label_topology: max_labels must be at least 1, got {max_labels}")
+    dev = labels.device
+    voxels = labels.numel()
+    if voxels == 0:
+        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+        return LabelTopology(z(labels.dtype, 0), z(torch.int64, 0), z(torch.int64, 0, *(2,) * nd), z(torch.int64, 0, *(2,) * nd))
+    labels = labels.contiguous()
+    lib = _lib.load()
+    cap = default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
+    while True:
+        ws = _workspace("edt_hip_label_topology_workspace_bytes", code, voxels, cap, device=dev)
+        keys = torch.empty(cap, dtype=labels.dtype, device=dev)
+        closed = torch.empty((cap, 8), dtype=torch.int64, device=dev)
+        interior = torch.empty((cap, 8), dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.edt_hip_label_topology_device(_vp(labels), code, nd, *ext, cap, _vp(keys), _vp(closed), _vp(interior),
+                                                     _vp(count), _vp(ws), ws.numel(), _stream_ptr()))
+        n = int(count.item())
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"label_topology: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    keys, closed, interior = keys[:n], closed[:n], interior[:n]
+    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
+        perm = torch.argsort(keys, stable=True)
+        keys, closed, interior = keys[perm], closed[perm], interior[perm]
+    return _topology.assemble(keys, closed, interior, nd, True)
 
 
 def connected_components(labels: torch.Tensor, connectivity=None, binary=False):

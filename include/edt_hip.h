@@ -501,6 +501,54 @@ int edt_hip_label_moments_device(const void *d_labels, int dtype, int ndim, int6
 int edt_hip_label_moments(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
                           void *keys, int64_t *counts, int64_t *sums, double *centroid, double *central, int64_t *n_labels);
 
+/* ---- label_topology: exact Euler numbers and surface of every label --------------------------------------------------
+ * Conventions, keys, order, capacity, *n_labels and overflow behaviour are label_moments': x fastest, idx = x + sx * (y + sy * z),
+ * label 0 is background, integers at full width, bool: any non-zero byte is key 1, -0.0 is background, a NaN voxel belongs to
+ * no label; ascending key; the arrays hold max_labels entries (closed and interior 8 * max_labels each), and with more
+ * distinct labels *n_labels is SOME value greater than max_labels, the contents are unspecified and the call returns EDT_OK.
+ * Cells: a CELL of a voxel p is given by c in {-1, 0, +1}^3 -- the voxel's 8 vertices, 12 edges, 6 faces and the cube itself.
+ *   Its TYPE is the set of axes with c_a = 0, the axes it extends along: a 3-bit index, bit 0 = x, bit 1 = y, bit 2 = z.  Its
+ *   INCIDENT voxels are p + e with e_a in {0, c_a}.  Positions outside the volume hold no label: there is no border option,
+ *   the volume's edge ends an object, and the object's boundary cells there count.
+ * The table has one entry for each distinct non-zero label L:
+ *   key       L, in the labels' dtype;
+ *   closed    eight int64, closed[S] = the number of distinct cells of type S with AT LEAST ONE incident voxel of label L: the
+ *             closed cubical complex of L (26-adjacency in 3-D, 8-adjacency in 2-D);
+ *   interior  eight int64, interior[S] = the number of cells of type S whose incident voxels ALL carry L: the open set
+ *             (6- and 4-adjacency).  interior[7] = closed[7] = the voxel count.
+ * Always the 3-D slab: unused extents are 1.  For a missing axis a, the count of type S of the lower-dimensional image is the
+ *   slab's count of type S with bit a set: closed cells transverse to an axis of extent 1 come in two identical copies, interior
+ *   cells transverse to it are 0.  The Euler number of the slab equals that of the image.
+ * Derived, with |S| the cell's dimension and nd = 3 for the slab:
+ *   euler, full adjacency   sum over S of (-1)^|S| * closed[S]            (components - tunnels + cavities)
+ *   euler, face adjacency   sum over S of (-1)^(nd - |S|) * interior[S]
+ *   intrinsic volumes for voxel sizes w:  V_j = sum over S of (-1)^(|S| - j) * closed[S] * e_j(w_a : a in S), e_j the elementary
+ *     symmetric polynomial: V_nd the volume, 2 * V_(nd-1) the area of the exposed voxel faces (the perimeter in 2-D), V_1 the
+ *     mean-breadth functional, V_0 the Euler number.  The face area does not converge to a smooth surface's area (about 1.5
+ *     times larger for a ball); it is exact and additive.
+ * Counting: a voxel owns a cell for L when it is the first incident voxel with label L in memory order, so every cell is
+ *   counted once; the counts do not depend on that order.  The largest count is 8 * voxels.
+ * Determinism: the same call gives the same table, bit for bit (integer adds and a compare-and-swap on the key). */
+
+/* Scratch of edt_hip_label_topology_device: nothing per voxel; label_moments' tables with wider slots -- 256 / 65536
+ * direct-indexed slots for 8- / 16-bit labels, else an open-addressing hash table of the power of two >= max(1024,
+ * 2 * max_labels) slots; 136 bytes per slot (the key and sixteen 64-bit counts), plus 8 bytes per label (a max_labels above
+ * `voxels` counts as `voxels`).  0 for a bad dtype or max_labels < 1. */
+size_t edt_hip_label_topology_workspace_bytes(int dtype, int64_t voxels, int64_t max_labels);
+/* ndim 1..3, unused extents 1, max_labels >= 1; NULL pointers and a missing, too small or misaligned scratch (d_scratch is
+ * the call's workspace: 256-byte aligned, at least the query's bytes) are EDT_ERR_BAD_ARG before any device work, in this
+ * order: dtype, ndim, unused extents, max_labels, d_n_labels, the other pointers, the scratch.  Enqueue-only on `stream`: no
+ * allocation, no synchronisation; the scratch is cleared by the call itself (a reused one needs no memset), so the call can
+ * be captured.  d_n_labels: one int64 on the device. */
+int edt_hip_label_topology_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                                  int64_t max_labels, void *d_keys, int64_t *d_closed /* 8*max_labels */,
+                                  int64_t *d_interior /* 8*max_labels */, int64_t *d_n_labels, void *d_scratch,
+                                  size_t scratch_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device).  The labels cross once; only the table is copied back. */
+int edt_hip_label_topology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
+                           void *keys, int64_t *closed, int64_t *interior, int64_t *n_labels);
+
 /* ---- connected components: multi-label component labelling on the device ---------------------------------------------
  * Conventions as above: x fastest, idx = x + sx * (y + sy * z), label 0 is background.
  * Adjacency: connectivity = c, 1 <= c <= ndim.  Two voxels are neighbours if their coordinates differ by at most 1 along
