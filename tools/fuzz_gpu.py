@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle fuzz over shapes / dtypes / label structures (diagnostics; the regular
-parity tests live in tests/).  usage: [FUZZ_Q16=1 [FUZZ_INF=1 | FUZZ_FLAT=1] [FUZZ_PAD=1] | FUZZ_VG=1] python tools/fuzz_gpu.py [ncases] [seed]      (FUZZ_DUMP=1: triage a mismatch under the
+parity tests live in tests/).  usage: [FUZZ_SIGNED=1] [FUZZ_Q16=1 [FUZZ_INF=1 | FUZZ_FLAT=1] [FUZZ_PAD=1] | FUZZ_VG=1] python tools/fuzz_gpu.py [ncases] [seed]      (FUZZ_SIGNED=1: the signed
+transform instead of edtsq -- sdfsq on even, sdf on odd case numbers, against the oracle's two-transform definition; not with
+FUZZ_VG.  FUZZ_DUMP=1: triage a mismatch under the
 form-selection bits and save the case to gpurun_out/)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,6 +18,9 @@ if not harness.have_port():
     harness.build("port")
 o = harness.port()
 dtypes = [np.uint8, np.uint16, np.uint32, np.uint64, np.float32, bool]
+signed = os.environ.get("FUZZ_SIGNED") == "1"
+if signed and os.environ.get("FUZZ_VG") == "1":
+    sys.exit("FUZZ_SIGNED does not compose with FUZZ_VG: the signed transform takes no voxel graph")
 bad = 0
 t0 = time.time()
 for i in range(ncases):
@@ -124,18 +129,25 @@ for i in range(ncases):
     bb = bool(rng.integers(0, 2))
     if finf:
         bb = rng.random() < 0.1
+    fn = "edtsq"
     if vg:
         if rng.random() < 0.7:
             an = tuple(float(a) for a in rng.choice([1, 2, 6, 30, 4], size=dims))  # (sizes that share a quantum: integer kernel)
         want = o.edtsq(lab, an, bb, voxel_graph=g)
         got = edt.edtsq(lab, anisotropy=an, black_border=bb, voxel_graph=g)
+    elif signed:
+        # the signed transform (EDT_FLAG_SIGNED where the shape is served, the two-transform composition elsewhere): label 0 is a
+        # label of its own here, so the slabs, half spaces, boxes and single voxels of label 0 drawn above are its structure
+        fn = "sdfsq" if i % 2 == 0 else "sdf"
+        want = getattr(o, fn)(lab, an, bb)
+        got = getattr(edt, fn)(lab, anisotropy=an, black_border=bb)
     else:
         want = o.edtsq(lab, an, bb)
         got = edt.edtsq(lab, anisotropy=an, black_border=bb)
     if not np.array_equal(got, want, equal_nan=True):
         bad += 1
-        print("MISMATCH", shape, dt.__name__, an, bb, int((got != want).sum()))
-        if os.environ.get("FUZZ_DUMP") == "1" and not vg:
+        print("MISMATCH", fn, shape, dt.__name__, an, bb, int((got != want).sum()))
+        if os.environ.get("FUZZ_DUMP") == "1" and not vg and not signed:
             # which form selection answers this case correctly, and where the wrong voxels are; the case itself for the CPU tier
             from edt import _lib
             lib = _lib.load()
