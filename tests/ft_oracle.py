@@ -9,6 +9,9 @@ Tiny volumes only: pure Python loops over lines.
 """
 from __future__ import annotations
 
+import math
+from fractions import Fraction
+
 import numpy as np
 
 INF = np.int64(1) << 62
@@ -18,6 +21,23 @@ def x_first(data):
     """A C-ordered array's x axis is its last one: the [x, y, z] view of ``data`` (1-D / 2-D padded with unit axes)."""
     v = np.asarray(data).T
     return v.reshape(v.shape + (1,) * (3 - v.ndim))
+
+
+def exact_factors(w_xyz):
+    """The integers ``a_i`` with ``fl32(w_i)^2 = a_i * q`` for one rational ``q``, reduced by their gcd -- the ``a`` of
+    :func:`feature_transform` for any voxel sizes whose squares are exact in fp32, whether the library finds a quantum for
+    them (then these are its ``a_i``: (6, 6, 30) -> (1, 1, 25)) or refuses one because some ``a_i`` exceeds its 16-bit
+    windows ((1, 1.0078125, 1) -> (16384, 16641, 16384)).  AssertionError where a square is not exact in fp32: the fp64
+    kernels round there, and no integer rule decides their ties."""
+    w32 = [Fraction(float(np.float32(w))) for w in w_xyz]
+    sq = [v * v for v in w32]
+    assert all(v > 0 for v in sq), f"voxel sizes {tuple(w_xyz)} must be positive"
+    exact = [Fraction(float(np.float32(float(v)))) == v for v in sq]
+    assert all(exact), f"voxel sizes {tuple(w_xyz)}: a square is not exact in fp32, the integer oracle does not serve them"
+    scale = math.lcm(*[v.denominator for v in sq])
+    ints = [int(v * scale) for v in sq]
+    g = math.gcd(*ints)
+    return tuple(v // g for v in ints)
 
 
 def _runs(line):

@@ -111,11 +111,8 @@ def scatter(lab, feat, w=(1.0, 1.0, 1.0), gamma=1.0, ratio=0.0, black_border=Fal
 
 
 def quantum(w):
-    """integers a_c with w_c^2 = a_c * q for voxel sizes that share a quantum (ft_oracle's ``a``)"""
-    sq = [float(np.float32(v)) ** 2 for v in w]
-    a = [v / min(sq) for v in sq]
-    assert all(abs(v - round(v)) < 1e-9 for v in a), f"{w} share no quantum this helper finds"
-    return tuple(int(round(v)) for v in a)
+    """integers a_c with w_c^2 = a_c * q for voxel sizes whose squares are exact in fp32 (ft_oracle's ``a``)"""
+    return ft_oracle.exact_factors(w)
 
 
 def xyz_view(data, anisotropy=None):
@@ -138,7 +135,8 @@ def xyz_view(data, anisotropy=None):
 
 def on_axis(data, gamma=None, min_angle=0.0, anisotropy=None, black_border=False, binary=False, features=None, form=gather):
     """The boolean axis of a numpy array, in the array's own axes.  ``features``: ABI planes ``(ndim, ...)`` in x, y, z order
-    over the [x, y, z] view flattened x fastest (what the device step reads); None: ``ft_oracle`` on quantum voxel sizes."""
+    over the [x, y, z] view flattened x fastest (what the device step reads); None: ``ft_oracle`` on voxel sizes whose squares
+    are exact in fp32 (``ft_oracle.exact_factors``)."""
     lab, w, nd, back = xyz_view(data, anisotropy)
     if data.dtype == bool:
         binary = True

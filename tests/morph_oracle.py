@@ -3,15 +3,15 @@
 A restatement of the contract, step by step.  The squared-distance fields come from the project's CPU transform
 (oracle.harness.port(), bit-identical to the reference); every comparison is ``field.astype(float64) > R2`` or ``<= R2``
 with ``R2 = float64(radius) * float64(radius)``.  expand_labels is restated from the header's definition over the
-feature-transform oracle (tests/ft_oracle.py), so dilate and closing are served for voxel sizes that share a quantum only
-(w_i^2 = a_i q with integer a_i), and for tiny volumes only: that oracle is pure Python loops over lines.
+feature-transform oracle (tests/ft_oracle.py), so dilate and closing are served for voxel sizes whose squares are exact in
+fp32 (w_i^2 = a_i q with integer a_i, ft_oracle.exact_factors: the sizes that share a quantum, and those the library refuses
+one for because an a_i is too large for its 16-bit windows -- the fp64 kernels are exact there), and for tiny volumes only:
+that oracle is pure Python loops over lines.
 
 Arrays may be C or Fortran contiguous: the transforms and the tie rule of expand_labels follow the array's memory order, as the
 library's do (x is the fastest axis of memory; an array that is both is taken as Fortran, as in edt/__init__.py).  Outputs have
 the input's dtype, shape and memory order; voxels that do not pass are all-zero bits, the others are copied bit for bit."""
 from __future__ import annotations
-
-from fractions import Fraction
 
 import numpy as np
 
@@ -74,12 +74,8 @@ def opening(labels, radius=1.0, anisotropy=None, black_border=False, binary=Fals
 
 
 def _quantum_factors(w_xyz):
-    """integer a_i with w_i^2 = a_i q for the fp32 voxel sizes ``w_xyz`` (AssertionError if they share no such quantum)"""
-    w2 = [Fraction(float(np.float32(w))) ** 2 for w in w_xyz]
-    q = min(w2)
-    a = [v / q for v in w2]
-    assert all(f.denominator == 1 for f in a), f"voxel sizes {w_xyz} share no quantum: the oracle does not serve them"
-    return [int(f) for f in a]
+    """integer a_i with w_i^2 = a_i q for the fp32 voxel sizes ``w_xyz`` (AssertionError if a square is not exact in fp32)"""
+    return list(ft_oracle.exact_factors(w_xyz))
 
 
 def expand_labels(labels, distance=1.0, anisotropy=None):

@@ -5,7 +5,11 @@ force -- so that the GPU tier does not rest on one restatement; and the generato
 Two families: the label operations (seeds 701..703; their draws are pinned by a digest, so that work on the generator cannot
 move them unnoticed) and the field operations erode / opening / dilate / closing / local_thickness / medial_axis (seeds
 711..713), whose second opinions are brute forces written from the definitions in exact integer arithmetic on the quanta of the
-voxel sizes, independent of both the compiled CPU transform and tests/ft_oracle.py."""
+voxel sizes, independent of both the compiled CPU transform and tests/ft_oracle.py.  The field draws are pinned by a digest too.
+
+A third family (seeds 721..723, 64 cases each) draws voxel sizes the library finds no quantum for (tests/noquantum_cases.py): the
+same brute forces serve it on the sizes' exact factors (ft_oracle.exact_factors), a radius of m smallest sizes being
+4 m^2 min(a) quanta."""
 import hashlib
 import itertools
 import math
@@ -23,6 +27,7 @@ import label_stats_oracle
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import fuzz_ops  # noqa: E402
+from test_q16_logic import q16, quantum  # noqa: E402, F401  (the fixture builds the host shim of the library's quantum rule)
 
 SEEDS = (701, 702, 703)        # (tests/test_gpu_fuzz_ops.py runs the same)
 NCASES = 60
@@ -179,6 +184,7 @@ def test_the_label_family_draws_have_not_moved():
 
 # ---- the field family ---------------------------------------------------------------------------------------------------------
 FIELD_SEEDS = (711, 712, 713)   # (tests/test_gpu_fuzz_ops.py runs the same)
+FIELD_DRAWS_SHA256 = "46cac9a764190585d63cf3cd7d4bb48bcdb6d72294e90d6f729d02b7b2876ac9"
 _drawn_field = {}
 
 
@@ -229,6 +235,16 @@ def test_field_generator_covers_what_it_promises():
     again = list(fuzz_ops.cases(FIELD_SEEDS[0], NCASES, fuzz_ops.FIELD_OPS))
     assert [fuzz_ops.describe(c) for c in again] == [fuzz_ops.describe(c) for c in drawn_field(FIELD_SEEDS[0])]
     assert all(np.array_equal(a["data"], b["data"], equal_nan=a["data"].dtype.kind == "f") for a, b in zip(again, drawn_field(FIELD_SEEDS[0])))
+
+
+def test_the_field_family_draws_have_not_moved():
+    """the same digest over the 60 cases of seeds 711, 712 and 713, taken before the generator learnt the noquantum family"""
+    h = hashlib.sha256()
+    for seed in FIELD_SEEDS:
+        for case in drawn_field(seed):
+            h.update(fuzz_ops.describe(case).encode())
+            h.update(case["data"].tobytes(order="A"))
+    assert h.hexdigest() == FIELD_DRAWS_SHA256
 
 
 # The brute forces.  A volume is indexed x first (`_xyz`), `a` are the squared voxel sizes in quanta q = min(w)^2 (integers),
@@ -307,10 +323,11 @@ def _selected(data, passes):
     return np.where(passes, _bits(data), 0).astype(_bits(data).dtype)
 
 
-def brute_thickness(lab, a, r4s, step, black_border, binary):
+def brute_thickness(lab, a, r4s, step, black_border, binary, unit=1):
     """(T, radii, sizes) from brute-force openings; r4s None: the default ladder j = 1, 2, ... as long as some voxel's finite
     squared distance exceeds (j step)^2, i.e. as long as the erosion by j steps leaves a survivor in a volume whose distances
-    are finite -- under a black border, or where not every voxel carries the one label.  None where the budget runs out."""
+    are finite -- under a black border, or where not every voxel carries the one label.  None where the budget runs out.
+    ``unit``: min(a), where the quantum is not the smallest size's square (r4 counts quarter squares of the smallest size)."""
     fg = _fg(lab)
     spent = 0
     T = np.zeros(lab.shape, dtype=np.float32)
@@ -323,12 +340,12 @@ def brute_thickness(lab, a, r4s, step, black_border, binary):
         ladder = iter(r4s)
     for t in ladder:
         r4 = 4 * t * t if r4s is None else t
-        spent += 2 * len(ball_offsets(a, r4)) * lab.size
+        spent += 2 * len(ball_offsets(a, r4 * unit)) * lab.size
         if spent > BUDGET:
             return None
-        if r4s is None and not brute_erode(lab, a, r4, black_border, binary).any():
+        if r4s is None and not brute_erode(lab, a, r4 * unit, black_border, binary).any():
             break
-        held = brute_opening(lab, a, r4, black_border, binary) & fg
+        held = brute_opening(lab, a, r4 * unit, black_border, binary) & fg
         radius = math.sqrt(r4 / 4.0) * step
         radii.append(radius)
         sizes.append(int(np.count_nonzero(held)))
@@ -441,3 +458,180 @@ def test_field_second_opinions_reach_every_operation():
     assert all(n >= 5 for n in total.values()), total
     assert total["erode"] == total["opening"] == total["closing"] == total["dilate"] == 30, total
     assert total["local_thickness"] >= 28 and total["medial_axis"] >= 23, total       # (what the budgets leave of the 30 each)
+
+
+# ---- the noquantum family -----------------------------------------------------------------------------------------------------
+NOQUANTUM_SEEDS = (721, 722, 723)   # (tests/test_gpu_fuzz_ops.py runs the same)
+NOQUANTUM_NCASES = 64
+_drawn_noquantum = {}
+
+
+def drawn_noquantum(seed):
+    if seed not in _drawn_noquantum:
+        _drawn_noquantum[seed] = list(fuzz_ops.cases(seed, NOQUANTUM_NCASES, fuzz_ops.NOQUANTUM_OPS))
+    return _drawn_noquantum[seed]
+
+
+def test_noquantum_generator_covers_what_it_promises(q16):  # noqa: F811
+    import noquantum_cases as nq
+    ops = fuzz_ops.NOQUANTUM_OPS
+    assert fuzz_ops.FAMILIES["noquantum"] == ops and len(ops) == 8
+    every = [c for seed in NOQUANTUM_SEEDS for c in drawn_noquantum(seed)]
+    assert len(every) == 3 * NOQUANTUM_NCASES
+    for seed in NOQUANTUM_SEEDS:
+        assert all(sum(c["op"] == op for c in drawn_noquantum(seed)) == 8 for op in ops)
+    for op in ops:
+        mine = [c for c in every if c["op"] == op]
+        exact_only = op in fuzz_ops.NOQUANTUM_EXACT_OPS
+        assert {c["data"].ndim for c in mine} == ({2, 3} if exact_only else {1, 2, 3}), op
+        assert {c["order"] for c in mine} == {"C", "F"}, op
+        assert all(c["data"].size <= fuzz_ops.CAP[op] for c in mine), op
+        assert {c["k"] for c in mine} == {0, 1, 2, 3}, op
+        assert any(c["host"] for c in mine), op
+        assert all(len(c["w_xyz"]) == c["data"].ndim for c in mine), op
+        full = {w for w in list(nq.EXACT) + list(nq.INEXACT)}
+        of = {c["w_xyz"]: [w for w in full if w[:c["data"].ndim] == c["w_xyz"]] for c in mine}
+        assert all(of.values()), op
+        if exact_only:
+            # every entry of EXACT, in 2-D and in 3-D; the library finds no quantum for any of the draws
+            assert {c["w_xyz"] for c in mine if c["data"].ndim == 3} == set(nq.EXACT), op
+            assert {c["w_xyz"] for c in mine if c["data"].ndim == 2} == {w[:2] for w in nq.EXACT}, op
+            assert all(c["a_xyz"] == ft_oracle.exact_factors(c["w_xyz"]) for c in mine), op
+            assert not any(quantum(q16, c["w_xyz"])[0] for c in mine), op
+        else:
+            exact = [c for c in mine if c["a_xyz"] is not None]
+            assert len(exact) == len(mine) // 2 and all(c["a_xyz"] == ft_oracle.exact_factors(c["w_xyz"]) for c in exact), op
+            assert {c["w_xyz"] for c in mine if c["a_xyz"] is None and c["data"].ndim == 3} == set(nq.INEXACT), op
+            assert {c["black_border"] for c in mine} == {False, True} and {c["binary"] for c in mine} == {False, True}, op
+    sx = {c["data"].shape[0] if c["order"] == "F" else c["data"].shape[-1] for c in every}
+    assert sx >= {1, 2, 63, 64, 65, 129, 257, 1030}, sorted(sx)
+    assert {c["structure"] for c in every} == set(fuzz_ops.STRUCTURES)
+    assert len({c["data"].dtype for c in every}) == 11
+    assert any(c["data"].dtype.kind == "f" and np.isnan(c["data"]).any() for c in every)
+    grown = [c for c in every if c["op"] == "expand_labels"]
+    assert {c["multiple"] for c in grown} == {0.0, 1.0, 2.5, np.inf}
+    assert all(c["distance"] == (c["multiple"] * min(c["w_xyz"]) if c["multiple"] else 0.0) for c in grown)
+    for op in ("erode", "opening", "dilate", "closing"):
+        mine = [c for c in every if c["op"] == op]
+        assert any(c["radius"] == 0.0 for c in mine) and all(c["radius"] == c["multiple"] * min(c["w_xyz"]) for c in mine), op
+    ladders = [c for c in every if c["op"] == "local_thickness"]
+    assert any(c["radii"] is None for c in ladders) and any(c["radii"] is not None for c in ladders)
+    assert all(max(c["w_xyz"]) <= 4 * min(c["w_xyz"]) for c in ladders if c["radii"] is None)
+    axes = [c for c in every if c["op"] == "medial_axis"]
+    assert len({c["gamma"] is None for c in axes}) == 2 and {c["min_angle"] for c in axes} == {0.0, 60.0, 120.0}
+    again = list(fuzz_ops.cases(NOQUANTUM_SEEDS[0], NOQUANTUM_NCASES, fuzz_ops.NOQUANTUM_OPS))
+    assert [fuzz_ops.describe(c) for c in again] == [fuzz_ops.describe(c) for c in drawn_noquantum(NOQUANTUM_SEEDS[0])]
+    assert all(np.array_equal(a["data"], b["data"], equal_nan=a["data"].dtype.kind == "f")
+               for a, b in zip(again, drawn_noquantum(NOQUANTUM_SEEDS[0])))
+
+
+def test_expand_want_forms_d_from_the_squared_sizes():
+    """with the sizes given, D is w^2 d^2 in fp64, not a d^2 in quanta: at (1, 129) a voxel 1 row away lies at 16641, within 129"""
+    lab = np.zeros((3, 3), dtype=np.uint8, order="F")
+    lab[1, 0] = 7
+    grown = fuzz_ops.expand_want(lab, 129.0, (1, 16641), (1.0, 129.0))
+    assert grown[1, 1] == 7 and grown[0, 0] == 7 and grown[0, 1] == 0 and np.count_nonzero(grown) == 4
+    assert np.count_nonzero(fuzz_ops.expand_want(lab, 1.0, (1, 16641), (1.0, 129.0))) == 3
+    # (in quanta alone the same call would compare 16641 with 129^2 as well: the two agree where a is w^2 itself)
+    assert np.array_equal(fuzz_ops.expand_want(lab, 129.0, (1, 16641)), grown)
+    tiny = fuzz_ops.expand_want(lab, 2.0 ** -8, (65536, 1), (1.0, 2.0 ** -8))
+    assert tiny[1, 1] == 7 and np.count_nonzero(tiny) == 2
+    assert np.count_nonzero(fuzz_ops.expand_want(lab, 2.0 ** -8, (65536, 1))) == 1
+
+
+_checked_noquantum = {}
+
+
+def noquantum_second_opinions(seed):
+    if seed not in _checked_noquantum:
+        _checked_noquantum[seed] = _noquantum_second_opinions(seed)
+    return _checked_noquantum[seed]
+
+
+def _ft_attains_the_brute_minimum(case, what):
+    data, nd, a, bb = case["data"], case["data"].ndim, case["a_xyz"], case["black_border"]
+    lab = data.reshape(data.shape + (1,) * (3 - nd)) if case["order"] == "F" else ft_oracle.x_first(data)
+    feats, _ = ft_oracle.feature_transform(lab, tuple(a) + (1,) * (3 - nd), bb, ndim=nd)
+    d = ft_oracle.sqdist(feats, tuple(a) + (0,) * (3 - nd))
+    best = ft_oracle.brute_min(lab, tuple(a), bb) if nd == 3 else _brute_min_nd(lab, a, bb, nd)
+    assert np.array_equal(np.where(d >= 0, d, ft_oracle.INF), best), what
+
+
+def _noquantum_second_opinions(seed):
+    import medial_oracle
+    import morph_oracle
+    checked = dict.fromkeys(fuzz_ops.NOQUANTUM_OPS, 0)
+    for case in drawn_noquantum(seed):
+        op, data, a = case["op"], case["data"], case["a_xyz"]
+        what = fuzz_ops.describe(case)
+        if a is None:                   # (sizes without exact factors: the compiled CPU transform stands alone)
+            continue
+        lab, back = _xyz(case)
+        unit = min(a)
+        binary = case["binary"] or data.dtype == np.bool_
+        r4 = None
+        if "multiple" in case and case["multiple"] != np.inf:
+            r4 = _r4(case["multiple"]) * unit
+        if op == "feature_transform":
+            if data.size <= 2000:
+                _ft_attains_the_brute_minimum(case, what)
+                checked[op] += 1
+        elif op in ("erode", "opening"):
+            if len(ball_offsets(a, r4)) * data.size > BUDGET:
+                continue
+            brute = (brute_erode if op == "erode" else brute_opening)(lab, a, r4, case["black_border"], binary)
+            assert np.array_equal(_bits(fuzz_ops.want_of(case)), _selected(data, back(brute))), what
+            checked[op] += 1
+        elif op == "local_thickness":
+            r4s = None if case["multiples"] is None else [_r4(m) for m in case["multiples"]]
+            brute = brute_thickness(lab, a, r4s, min(case["w_xyz"]), case["black_border"], binary, unit=unit)
+            if brute is None:
+                continue
+            T, radii, sizes = fuzz_ops.want_of(case)
+            assert np.array_equal(radii, brute[1]) and np.array_equal(sizes, brute[2]), (what, radii, brute[1], sizes, brute[2])
+            assert T.dtype == np.float32 and np.array_equal(_bits(T), _bits(back(brute[0]))), what
+            checked[op] += 1
+        elif op in ("dilate", "expand_labels"):
+            if int(np.count_nonzero(_fg(data))) * int(np.count_nonzero(~_fg(data))) > BUDGET:
+                continue
+            out = fuzz_ops.want_of(case)
+            dilate_properties(lab, out if case["order"] == "F" else out.T, a, r4, what)
+            if op == "expand_labels":   # the two restatements of the definition agree
+                grown = morph_oracle.expand_labels(data, case["distance"], fuzz_ops.axis_order(case, case["w_xyz"]))
+                assert np.array_equal(_bits(out), _bits(grown)), what
+            checked[op] += 1
+        elif op == "closing":
+            if len(ball_offsets(a, r4)) * data.size > BUDGET:
+                continue
+            out = fuzz_ops.want_of(case)
+            dilated = morph_oracle.dilate(data, case["radius"], fuzz_ops.axis_order(case, case["w_xyz"]))
+            grown = dilated if case["order"] == "F" else dilated.T
+            eroded = brute_erode(_fg(grown).astype(np.uint8), a, r4, False, True)
+            keep = _fg(data) | back(eroded)
+            assert np.array_equal(_fg(out), keep), what
+            assert np.array_equal(_bits(out), _selected(dilated, keep)), what
+            checked[op] += 1
+        elif data.size <= MEDIAL_SCATTER_VOXELS:
+            kw = fuzz_ops.field_kwargs(case, fuzz_ops.axis_order(case, case["w_xyz"]))
+            assert np.array_equal(medial_oracle.on_axis(data, form=medial_oracle.scatter, **kw),
+                                  medial_oracle.on_axis(data, form=medial_oracle.gather, **kw)), what
+            checked[op] += 1
+    return checked
+
+
+@pytest.mark.parametrize("seed", NOQUANTUM_SEEDS)
+def test_noquantum_oracles_against_a_second_opinion(seed):
+    checked = noquantum_second_opinions(seed)
+    # (erode, opening and local_thickness: the four cases of the eight that have exact factors)
+    assert checked["erode"] == checked["opening"] == 4 and checked["closing"] == 8, checked
+
+
+def test_noquantum_second_opinions_reach_every_operation():
+    total = dict.fromkeys(fuzz_ops.NOQUANTUM_OPS, 0)
+    for seed in NOQUANTUM_SEEDS:
+        for op, n in noquantum_second_opinions(seed).items():
+            total[op] += n
+    assert all(n >= 5 for n in total.values()), total
+    # (what the budgets leave: of the 24 cases of each operation, 12 of erode, opening and local_thickness have exact factors)
+    assert total["erode"] == total["opening"] == total["local_thickness"] == 12 and total["closing"] == total["dilate"] == 24, total
+    assert total["expand_labels"] >= 20 and total["feature_transform"] >= 8 and total["medial_axis"] >= 15, total

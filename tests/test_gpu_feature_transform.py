@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import ft_oracle
+import noquantum_cases as nq
 from synth import blocky_labels, palette_labels, voronoi_labels
 
 pytestmark = pytest.mark.gpu
@@ -303,6 +304,9 @@ def test_expand_labels(dtype, distance):
         if an != (2.3, 0.7, 1.1):  # integer sizes: each filled voxel took a nearest foreground voxel's label
             dt = ndimage.distance_transform_edt(lab == 0, sampling=an)
             assert np.array_equal(D[take], (dt[take].astype(np.float64) ** 2).round())
+        else:  # no quantum: the reference above rests on the library's own transform, so hold the result to scipy's minimum
+            assert nq.undecided(lab.T, distance, an[::-1]) == 0       # (a condition on the data: x first)
+            assert nq.check_expand(lab.T, got.T, distance, an[::-1]) == 0
     assert np.array_equal(edt.expand_labels(np.zeros_like(lab), distance=distance), np.zeros_like(lab))
     full = np.ones_like(lab)
     assert np.array_equal(edt.expand_labels(full, distance=distance), full)

@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
 """Seeded randomised runs of the label operations against their numpy oracles, bit for bit, in the manner of tools/fuzz_gpu.py.
-Two families, each round-robin over its operations:
+Three families, each round-robin over its operations:
 
-  label   connected_components, fill_holes, dust, label_stats, feature_transform and expand_labels (OPS);
-  field   erode, opening, dilate, closing, local_thickness and medial_axis (FIELD_OPS): the compositions of
-          csrc/edt_fieldops.hip.
+  label      connected_components, fill_holes, dust, label_stats, feature_transform and expand_labels (OPS);
+  field      erode, opening, dilate, closing, local_thickness and medial_axis (FIELD_OPS): the compositions of
+             csrc/edt_fieldops.hip;
+  noquantum  feature_transform, expand_labels, dilate, closing, medial_axis, erode, opening and local_thickness (NOQUANTUM_OPS)
+             at voxel sizes the library finds no quantum for: the fp64 kernels of csrc/edt_feature.hip and the fp32 column
+             kernels of the distance transform.
 
-usage: python tools/fuzz_ops.py [ncases] [seed] [label|field]
+usage: python tools/fuzz_ops.py [ncases] [seed] [label|field|noquantum]
 
 One MISMATCH line per failing case, one line of per-operation counts, a last line `N cases, M mismatches`; the exit status is
 non-zero on any mismatch.  ``cases(seed, n, ops)`` is the generator on its own (numpy only): the CPU tier draws the same inputs
 and holds the oracles against a second opinion (tests/test_fuzz_ops_cpu.py; label family: seeds 701..703, field family: seeds
-711..713).
+711..713, noquantum family: seeds 721..723).
 
 A case: 1 to 3 dimensions in C or F order; an x extent from the lengths where 64-voxel groups, 256-voxel cuts and row kernels
 change (or 1..90), the other extents 1..40, the last ones clipped to the case's cap; blocks, noise near the percolation
@@ -27,7 +30,14 @@ attains, so the `>` / `<=` ties of the selects are hit on purpose.  local_thickn
 and 1 to 4 ascending radii of the same multiples otherwise, always with its sizes; medial_axis a gamma of None, 0 or 1.5 times the
 smallest voxel size, a min_angle of 0, 60 or 120 degrees, and the radius function on every second case.  erode, opening and
 local_thickness are held against the compiled CPU transform (tests/morph_oracle.py, tests/thickness_oracle.py), dilate, closing and
-medial_axis against the pure-Python feature transform (tests/ft_oracle.py, tests/medial_oracle.py), hence their smaller cap."""
+medial_axis against the pure-Python feature transform (tests/ft_oracle.py, tests/medial_oracle.py), hence their smaller cap.
+
+A noquantum case is drawn the same way again.  feature_transform, expand_labels, dilate, closing and medial_axis take their sizes
+from the EXACT table of tests/noquantum_cases.py (squares exact in fp32, but factors beyond the 16-bit windows: the fp64 kernels
+are exact there, so the same oracles hold bit for bit with ft_oracle.exact_factors), in 2-D and 3-D only -- a 1-D cut always has
+a quantum; expand_labels' distance is 0, 1 or 2.5 times the smallest size or +inf, and D is formed from the fp64 squares of the
+sizes, as the header has it.  erode, opening and local_thickness, whose oracle is exact for any size, take theirs from EXACT and
+INEXACT in turn, in 1-D to 3-D."""
 import os
 import sys
 import time
@@ -43,7 +53,9 @@ from synth import blocky_labels, palette  # noqa: E402
 
 OPS = ("connected_components", "fill_holes", "dust", "label_stats", "feature_transform", "expand_labels")
 FIELD_OPS = ("erode", "opening", "dilate", "closing", "local_thickness", "medial_axis")
-FAMILIES = {"label": OPS, "field": FIELD_OPS}
+NOQUANTUM_OPS = ("feature_transform", "expand_labels", "dilate", "closing", "medial_axis", "erode", "opening", "local_thickness")
+NOQUANTUM_EXACT_OPS = NOQUANTUM_OPS[:5]            # (held to tests/ft_oracle.py: sizes with exact factors only, 2-D and 3-D)
+FAMILIES = {"label": OPS, "field": FIELD_OPS, "noquantum": NOQUANTUM_OPS}
 COMPONENT_FAMILY = OPS[:3]
 X_EXTENTS = (1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1030)
 STRUCTURES = ("blocky", "noise", "pinholes", "per_voxel", "chain")
@@ -133,6 +145,7 @@ def cases(seed, n, ops=OPS):
     axis in C order), connectivity, binary, k (element offset of the device buffers), host (also through the host module), and
     the operation's own parameters: per-axis ones x first (w_xyz, a_xyz)."""
     DTYPES, QUANTUM = _tables()
+    noquantum = tuple(ops) == NOQUANTUM_OPS
     rng = np.random.default_rng(seed)
     for i in range(n):
         op = ops[i % len(ops)]
@@ -142,6 +155,8 @@ def cases(seed, n, ops=OPS):
         # the last one stopped), and among the others every second one of the component family is grown past 2048 or 4096
         # voxels, so that chunk and span boundaries fall inside the volume.
         nd = 1 + (j + seed) % 3
+        if noquantum and op in NOQUANTUM_EXACT_OPS:
+            nd = 2 + (j + seed) % 2
         connectivity = 1 + (j // 3 + seed) % nd
         turn = (j // 2 + 5 * seed + 3 * ops.index(op)) if j % 2 == 0 else -1
         at_least = 0
@@ -157,7 +172,9 @@ def cases(seed, n, ops=OPS):
         order = "F" if data.flags.f_contiguous else "C"
         case = dict(index=i, op=op, data=data, order=order, structure=structure, connectivity=connectivity,
                     binary=bool(rng.integers(0, 2)), k=int(rng.integers(0, 4)), host=i % 5 == 2)
-        if op == "dust":
+        if noquantum:
+            _noquantum_parameters(case, rng, j, nd, 4 * (seed % 3) + ops.index(op))
+        elif op == "dust":
             lo = int(rng.integers(1, 12))
             case["threshold"] = lo if rng.random() < 0.5 else (lo, lo + int(rng.integers(1, 40)))
             case["invert"] = bool(rng.integers(0, 2))
@@ -174,15 +191,40 @@ def cases(seed, n, ops=OPS):
             case["distance"] = float(rng.choice([0.0, 1.0, 2.5, np.inf]))
             case["w_xyz"] = tuple(float(v) for v in rng.integers(1, 4, size=nd))
         elif op in FIELD_OPS:
-            _field_parameters(case, rng, j, nd, QUANTUM)
+            w = list(QUANTUM)[int(rng.integers(0, len(QUANTUM)))]
+            case["w_xyz"], case["a_xyz"] = w[:nd], QUANTUM[w][:nd]
+            _field_parameters(case, rng, j)
         yield case
 
 
-def _field_parameters(case, rng, j, nd, QUANTUM):
-    """what a field case draws on top of the common part"""
+def _noquantum_parameters(case, rng, j, nd, turn):
+    """what a noquantum case draws on top of the common part: sizes without a quantum, going round their tables with the
+    operation's case number -- two consecutive cases, one of each dimension or kind, share an entry, and three consecutive seeds
+    start 4 entries apart, so that they cover the seven entries in every dimension (a_xyz: the sizes' exact factors, None for
+    sizes whose squares are not exact in fp32)"""
+    import ft_oracle
+    from noquantum_cases import EXACT, INEXACT
     op = case["op"]
-    w = list(QUANTUM)[int(rng.integers(0, len(QUANTUM)))]
-    case["w_xyz"], case["a_xyz"] = w[:nd], QUANTUM[w][:nd]
+    if op in NOQUANTUM_EXACT_OPS:
+        w = list(EXACT)[(j // 2 + turn) % len(EXACT)]
+    else:
+        w = list(EXACT)[(j // 2 + turn) % len(EXACT)] if j % 2 == 0 else INEXACT[(j // 2 + case["index"]) % len(INEXACT)]
+    case["w_xyz"] = w[:nd]
+    case["a_xyz"] = ft_oracle.exact_factors(w[:nd]) if w in EXACT else None
+    if op == "feature_transform":
+        case["black_border"] = bool(rng.integers(0, 2))
+    elif op == "expand_labels":
+        case["multiple"] = float((0.0, 1.0, 2.5, np.inf)[int(rng.integers(0, 4))])
+        case["distance"] = case["multiple"] * min(case["w_xyz"]) if case["multiple"] else 0.0
+    else:
+        _field_parameters(case, rng, j, mild_ladder=True)
+
+
+def _field_parameters(case, rng, j, mild_ladder=False):
+    """what a field case draws on top of the common part and its voxel sizes; mild_ladder: local_thickness takes the default
+    ladder only where the largest size is at most 4 times the smallest (its steps are the smallest size: at (1, 2^-8, 1) a
+    ladder would have as many rungs as 256 times the extent)"""
+    op = case["op"]
     step = min(case["w_xyz"])
     if op in TAKES_FLAGS:
         case["black_border"] = bool(rng.integers(0, 2))
@@ -194,7 +236,7 @@ def _field_parameters(case, rng, j, nd, QUANTUM):
         case["radius"] = case["multiple"] * step
     elif op == "local_thickness":
         case["multiples"] = None
-        if j % 3:
+        if j % 3 or (mild_ladder and max(case["w_xyz"]) > 4 * step):
             picked = rng.permutation(len(RADIUS_MULTIPLES) - 1)[:int(rng.integers(1, 5))]
             case["multiples"] = tuple(RADIUS_MULTIPLES[1 + int(t)] for t in sorted(picked))
         case["radii"] = None if case["multiples"] is None else tuple(m * step for m in case["multiples"])
@@ -218,9 +260,10 @@ def axis_order(case, xyz):
     return tuple(xyz) if case["order"] == "F" else tuple(xyz)[::-1]
 
 
-def expand_want(data, distance, a_xyz):
+def expand_want(data, distance, a_xyz, w_xyz=None):
     """expand_reference of tests/test_gpu_feature_transform.py (the definition of include/edt_hip.h) with the inner feature
-    transform from the numpy oracle, not from the library; a_xyz: the squared voxel sizes (integers), x first"""
+    transform from the numpy oracle, not from the library; a_xyz: the squared voxel sizes in quanta (integers), x first, which
+    are the squared sizes themselves unless w_xyz gives the sizes: then D is formed from their fp64 squares, as the header does"""
     from test_gpu_feature_transform import expected
     nd = data.ndim
     order = "F" if data.flags.f_contiguous else "C"
@@ -228,7 +271,8 @@ def expand_want(data, distance, a_xyz):
         mask = np.array(data == 0, order=order).astype(np.uint8, order=order)
     f = expected(mask, False, a_xyz)                                    # component k: the coordinate along array axis k
     grids = np.stack(np.meshgrid(*[np.arange(s) for s in data.shape], indexing="ij")) if nd > 1 else np.arange(data.shape[0])[None]
-    a_axis = tuple(a_xyz) if order == "F" else tuple(a_xyz)[::-1]
+    w2_xyz = a_xyz if w_xyz is None else [np.float64(np.float32(w)) * np.float64(np.float32(w)) for w in w_xyz]
+    a_axis = tuple(w2_xyz) if order == "F" else tuple(w2_xyz)[::-1]
     D = np.zeros(data.shape)
     for k in (range(nd) if order == "F" else range(nd - 1, -1, -1)):    # terms added in ABI order x, y, z
         D = D + np.float64(a_axis[k]) * ((grids[k] - f[k]).astype(np.int64) ** 2).astype(np.float64)
@@ -295,6 +339,8 @@ def want_of(case):
         return label_stats_oracle.label_stats(data, case["dt"])
     if op == "feature_transform":
         return expected(data, case["black_border"], case["a_xyz"])
+    if "a_xyz" in case:
+        return expand_want(data, case["distance"], case["a_xyz"], case["w_xyz"])
     return expand_want(data, case["distance"], tuple(int(v * v) for v in case["w_xyz"]))
 
 
