@@ -337,6 +337,47 @@ static int feature_host(const void *labels, int dtype, int ndim, int64_t sx, int
   return rc != EDT_OK ? rc : st.down(output, kOut, obytes);
 }
 
+// ---- the tables of label_stats, label_moments and label_topology on host buffers -------------------------------------------
+// A table's output columns, the keys first (bytes per row: the label type's), then the columns of 8-byte items, then those of
+// 4-byte items (`item`: 4).  On the device (kAux): keys | 8-byte columns | n | 4-byte columns, `cap` rows each.
+struct TableColumn {
+  void *host;
+  size_t row_bytes;
+  size_t item = 8;
+};
+struct DeviceTable {
+  static constexpr int kMaxColumns = 6;
+  TableColumn cols[kMaxColumns];   // (a copy: the caller's list may be a temporary)
+  int ncols;
+  char *base = nullptr;
+  size_t off[kMaxColumns] = {}, o_n = 0, bytes = 0;
+  DeviceTable(std::initializer_list<TableColumn> c, size_t cap) : ncols((int)c.size()) {
+    if (ncols > kMaxColumns) abort();  // (a table of this file with more columns than it has room for)
+    std::copy(c.begin(), c.end(), cols);
+    size_t o = 0;
+    bool n_placed = false;
+    for (int i = 0; i < ncols; ++i) {
+      if (i == 1) o = align_up(o, 8);
+      if (i >= 1 && !n_placed && cols[i].item == 4) { o_n = o; o += 8; n_placed = true; }
+      off[i] = o;
+      o += cap * cols[i].row_bytes;
+    }
+    if (!n_placed) { o_n = o; o += 8; }
+    bytes = o;
+  }
+  bool null_column() const { return std::any_of(cols, cols + ncols, [](const TableColumn &c) { return !c.host; }); }
+  template <typename T = void> T *col(int i) const { return (T *)(base + off[i]); }
+  int64_t *n() const { return (int64_t *)(base + o_n); }
+  // n first; more than `cap` labels is not an error (the caller retries with more room) and brings nothing else back
+  int down(Staging &st, int64_t cap, int64_t *n_labels) const {
+    int rc = st.down(n_labels, kAux, sizeof(int64_t), o_n);
+    if (rc != EDT_OK || *n_labels > cap || *n_labels == 0) return rc;
+    for (int i = 0; i < ncols; ++i)
+      if ((rc = st.down(cols[i].host, kAux, (size_t)*n_labels * cols[i].row_bytes, off[i])) != EDT_OK) return rc;
+    return EDT_OK;
+  }
+};
+
 // label_stats on host buffers (kernels: edt_labelstats.hip): labels up once (and the caller's field, if it brings one; else the
 // ordinary transform runs here, with sqrt), the table pass on the device, and only the table comes back.
 static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
@@ -366,43 +407,37 @@ static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx,
   const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
   const size_t tbytes = dt ? 0 : edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
   const size_t wbytes = std::max(sbytes, tbytes);
-  // the table on the device: keys | counts | argmax | n (8-byte items) | max | bbox (4-byte items)
-  const size_t n = (size_t)cap, ksz = (size_t)dtype_size(dtype);
-  const size_t o_counts = align_up(n * ksz, 8), o_argmax = o_counts + 8 * n, o_n = o_argmax + 8 * n, o_max = o_n + 8,
-               o_bbox = o_max + 4 * n, obytes = o_bbox + 24 * n;
+  DeviceTable tab({{keys, (size_t)dtype_size(dtype)}, {counts, 8}, {argmax, 8}, {max, 4, 4}, {bbox, 24, 4}}, (size_t)cap);
   Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, fbytes}, {kWorkspace, wbytes}, {kAux, obytes}})) != EDT_OK) return rc;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kOut, fbytes}, {kWorkspace, wbytes}, {kAux, tab.bytes}})) != EDT_OK) return rc;
   if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
   rc = dt ? st.up(kOut, dt, fbytes)
           : run_device(st.p[kLabels], dtype, ndim, sx, sy, sz, wx, wy, wz, flags, st.at<float>(kOut), st.p[kWorkspace], wbytes, nullptr);
   if (rc != EDT_OK) return rc;
-  char *tab = st.at<char>(kAux);
-  rc = edt_hip_label_stats_device(st.p[kLabels], dtype, st.at<const float>(kOut), ndim, sx, sy, sz, cap, tab,
-                                  (int64_t *)(tab + o_counts), (float *)(tab + o_max), (int64_t *)(tab + o_argmax),
-                                  (int32_t *)(tab + o_bbox), (int64_t *)(tab + o_n), st.p[kWorkspace], wbytes, nullptr);
-  if (rc != EDT_OK || (rc = st.down(n_labels, kAux, sizeof(int64_t), o_n)) != EDT_OK) return rc;
-  if (*n_labels > cap) return EDT_OK;  // not an error: the caller retries with more room
-  const size_t m = (size_t)*n_labels;
-  if (m == 0) return EDT_OK;
-  if ((rc = st.down(keys, kAux, m * ksz)) != EDT_OK || (rc = st.down(counts, kAux, m * 8, o_counts)) != EDT_OK ||
-      (rc = st.down(argmax, kAux, m * 8, o_argmax)) != EDT_OK || (rc = st.down(max, kAux, m * 4, o_max)) != EDT_OK)
-    return rc;
-  return st.down(bbox, kAux, m * 24, o_bbox);
+  tab.base = st.at<char>(kAux);
+  rc = edt_hip_label_stats_device(st.p[kLabels], dtype, st.at<const float>(kOut), ndim, sx, sy, sz, cap, tab.col(0),
+                                  tab.col<int64_t>(1), tab.col<float>(3), tab.col<int64_t>(2), tab.col<int32_t>(4), tab.n(),
+                                  st.p[kWorkspace], wbytes, nullptr);
+  return rc != EDT_OK ? rc : tab.down(st, cap, n_labels);
 }
 
-// label_moments on host buffers (kernels: edt_moments.hip): labels up once, the sweep on the device, and only the table comes back.
-static int label_moments_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
-                              void *keys, int64_t *counts, int64_t *sums, double *centroid, double *central, int64_t *n_labels) {
+// label_moments and label_topology on host buffers (kernels: edt_moments.hip, edt_topology.hip): labels up once, the sweep on the
+// device, and only the table comes back.  own_check: what the call refuses after the shape (its *_check_args).  ws_query: its
+// edt_hip_*_workspace_bytes.  cols: its output columns.  call(d_labels, cap, table, d_ws, ws_bytes): its device entry point.
+template <typename Check, typename Call>
+static int label_table_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
+                            size_t (*ws_query)(int, int64_t, int64_t), std::initializer_list<TableColumn> cols, int64_t *n_labels,
+                            Check own_check, Call call) {
   int64_t cap = 0;
   size_t sbytes = 0;
   bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !keys || !counts || !sums || !centroid || !central, &empty,
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || DeviceTable(cols, 0).null_column(), &empty,
                          [&](After what) -> int {
-    if (what == After::shape) return moments_check_args(sx, sy, sz, max_labels);
+    if (what == After::shape) return own_check();
     if (what == After::voxel_sizes && !n_labels) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
     if (what == After::pointers) {  // (the volume is not empty here)
       cap = std::min(max_labels, sx * sy * sz);
-      sbytes = edt_hip_label_moments_workspace_bytes(dtype, sx * sy * sz, cap);
+      sbytes = ws_query(dtype, sx * sy * sz, cap);
     }
     return EDT_OK;
   });
@@ -411,62 +446,13 @@ static int label_moments_host(const void *labels, int dtype, int ndim, int64_t s
   ListedDevice on_listed_device;
   if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
   const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
-  // the table on the device, 8-byte items throughout but the keys: keys | counts | sums | centroid | central | n
-  const size_t n = (size_t)cap, ksz = (size_t)dtype_size(dtype);
-  const size_t o_counts = align_up(n * ksz, 8), o_sums = o_counts + 8 * n, o_centroid = o_sums + 72 * n,
-               o_central = o_centroid + 24 * n, o_n = o_central + 48 * n, obytes = o_n + 8;
+  DeviceTable tab(cols, (size_t)cap);
   Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kWorkspace, sbytes}, {kAux, obytes}})) != EDT_OK) return rc;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kWorkspace, sbytes}, {kAux, tab.bytes}})) != EDT_OK) return rc;
   if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  char *tab = st.at<char>(kAux);
-  rc = edt_hip_label_moments_device(st.p[kLabels], dtype, ndim, sx, sy, sz, cap, tab, (int64_t *)(tab + o_counts),
-                                    (int64_t *)(tab + o_sums), (double *)(tab + o_centroid), (double *)(tab + o_central),
-                                    (int64_t *)(tab + o_n), st.p[kWorkspace], sbytes, nullptr);
-  if (rc != EDT_OK || (rc = st.down(n_labels, kAux, sizeof(int64_t), o_n)) != EDT_OK) return rc;
-  if (*n_labels > cap) return EDT_OK;  // not an error: the caller retries with more room
-  const size_t m = (size_t)*n_labels;
-  if (m == 0) return EDT_OK;
-  if ((rc = st.down(keys, kAux, m * ksz)) != EDT_OK || (rc = st.down(counts, kAux, m * 8, o_counts)) != EDT_OK ||
-      (rc = st.down(sums, kAux, m * 72, o_sums)) != EDT_OK || (rc = st.down(centroid, kAux, m * 24, o_centroid)) != EDT_OK)
-    return rc;
-  return st.down(central, kAux, m * 48, o_central);
-}
-
-// label_topology on host buffers (kernels: edt_topology.hip): labels up once, the sweep on the device, and only the table comes back.
-static int label_topology_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
-                               void *keys, int64_t *closed, int64_t *interior, int64_t *n_labels) {
-  int64_t cap = 0;
-  size_t sbytes = 0;
-  bool empty;
-  int rc = host_prologue(dtype, ndim, sx, sy, sz, nullptr, !labels || !keys || !closed || !interior, &empty, [&](After what) -> int {
-    if (what == After::shape) return topology_check_args(max_labels);
-    if (what == After::voxel_sizes && !n_labels) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
-    if (what == After::pointers) {  // (the volume is not empty here)
-      cap = std::min(max_labels, sx * sy * sz);
-      sbytes = edt_hip_label_topology_workspace_bytes(dtype, sx * sy * sz, cap);
-    }
-    return EDT_OK;
-  });
-  if (rc == EDT_OK && empty && (rc = require_device()) == EDT_OK) *n_labels = 0;  // (the device form's answer to an empty volume)
-  if (rc != EDT_OK || empty) return rc;
-  ListedDevice on_listed_device;
-  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype);
-  // the table on the device, 8-byte items throughout but the keys: keys | closed | interior | n
-  const size_t n = (size_t)cap, ksz = (size_t)dtype_size(dtype);
-  const size_t o_closed = align_up(n * ksz, 8), o_interior = o_closed + 64 * n, o_n = o_interior + 64 * n, obytes = o_n + 8;
-  Staging st;
-  if ((rc = st.alloc({{kLabels, lbytes}, {kWorkspace, sbytes}, {kAux, obytes}})) != EDT_OK) return rc;
-  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
-  char *tab = st.at<char>(kAux);
-  rc = edt_hip_label_topology_device(st.p[kLabels], dtype, ndim, sx, sy, sz, cap, tab, (int64_t *)(tab + o_closed),
-                                     (int64_t *)(tab + o_interior), (int64_t *)(tab + o_n), st.p[kWorkspace], sbytes, nullptr);
-  if (rc != EDT_OK || (rc = st.down(n_labels, kAux, sizeof(int64_t), o_n)) != EDT_OK) return rc;
-  if (*n_labels > cap) return EDT_OK;  // not an error: the caller retries with more room
-  const size_t m = (size_t)*n_labels;
-  if (m == 0) return EDT_OK;
-  if ((rc = st.down(keys, kAux, m * ksz)) != EDT_OK || (rc = st.down(closed, kAux, m * 64, o_closed)) != EDT_OK) return rc;
-  return st.down(interior, kAux, m * 64, o_interior);
+  tab.base = st.at<char>(kAux);
+  rc = call(st.p[kLabels], cap, tab, st.p[kWorkspace], sbytes);
+  return rc != EDT_OK ? rc : tab.down(st, cap, n_labels);
 }
 
 // connected_components, fill_holes and dust on host buffers (kernels: edt_components.hip, edt_fillholes.hip, edt_dust.hip):
@@ -662,12 +648,25 @@ int edt_hip_label_stats(const void *labels, int dtype, int ndim, int64_t sx, int
 
 int edt_hip_label_moments(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
                           void *keys, int64_t *counts, int64_t *sums, double *centroid, double *central, int64_t *n_labels) {
-  return label_moments_host(labels, dtype, ndim, sx, sy, sz, max_labels, keys, counts, sums, centroid, central, n_labels);
+  return label_table_host(
+      labels, dtype, ndim, sx, sy, sz, max_labels, edt_hip_label_moments_workspace_bytes,
+      {{keys, (size_t)dtype_size(dtype)}, {counts, 8}, {sums, 72}, {centroid, 24}, {central, 48}}, n_labels,
+      [&] { return moments_check_args(sx, sy, sz, max_labels); },
+      [&](const void *d_labels, int64_t cap, const DeviceTable &t, void *ws, size_t ws_bytes) {
+        return edt_hip_label_moments_device(d_labels, dtype, ndim, sx, sy, sz, cap, t.col(0), t.col<int64_t>(1), t.col<int64_t>(2),
+                                            t.col<double>(3), t.col<double>(4), t.n(), ws, ws_bytes, nullptr);
+      });
 }
 
 int edt_hip_label_topology(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int64_t max_labels,
                            void *keys, int64_t *closed, int64_t *interior, int64_t *n_labels) {
-  return label_topology_host(labels, dtype, ndim, sx, sy, sz, max_labels, keys, closed, interior, n_labels);
+  return label_table_host(
+      labels, dtype, ndim, sx, sy, sz, max_labels, edt_hip_label_topology_workspace_bytes,
+      {{keys, (size_t)dtype_size(dtype)}, {closed, 64}, {interior, 64}}, n_labels, [&] { return topology_check_args(max_labels); },
+      [&](const void *d_labels, int64_t cap, const DeviceTable &t, void *ws, size_t ws_bytes) {
+        return edt_hip_label_topology_device(d_labels, dtype, ndim, sx, sy, sz, cap, t.col(0), t.col<int64_t>(1), t.col<int64_t>(2),
+                                             t.n(), ws, ws_bytes, nullptr);
+      });
 }
 
 int edt_hip_connected_components(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,

@@ -251,6 +251,32 @@ def expand_labels(data, distance=1.0, anisotropy=None, parallel=1):
 LabelStats = collections.namedtuple("LabelStats", ["labels", "counts", "max", "argmax", "bbox_lo", "bbox_hi"])
 
 
+def _label_table(who, data, code, max_labels, alloc, call):
+    """What label_stats, label_moments and label_topology do around their library call: the capacity (``max_labels``, or the
+    default rule), the call -- retried with 8x the room while a default capacity proves too small, a ``ValueError`` if an explicit
+    one does --, the columns cut to the ``n`` labels found, the keys back under ``data``'s own type and, for signed dtypes, all
+    columns in signed order.  ``alloc(cap)``: the output columns with ``cap`` rows each, the keys first.
+    ``call(cap, column pointers, n)``: the entry point; ``n`` receives the number of labels.  Returns the columns."""
+    voxels = data.size
+    cap = _lib.default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
+    while True:
+        cols = alloc(cap)
+        count = ctypes.c_int64(0)
+        _lib.check(call(cap, [_ptr(c) for c in cols], ctypes.byref(count)))
+        n = int(count.value)
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"{who}: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    cols = [c[:n] for c in cols]
+    cols[0] = cols[0].view(data.dtype)     # (signed dtypes: the bit patterns back under their own type)
+    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
+        perm = np.argsort(cols[0], kind="stable")
+        cols = [c[perm] for c in cols]
+    return cols
+
+
 def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, max_labels=None):
     """One table row per distinct non-zero label of ``data`` (contract: include/edt_hip.h, "label_stats"), as the named
     tuple ``(labels, counts, max, argmax, bbox_lo, bbox_hi)`` of numpy arrays: the label values ascending (signed dtypes
@@ -290,33 +316,14 @@ def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, 
         dt = np.asfortranarray(dt) if order == "F" else np.ascontiguousarray(dt)
     e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
     ww = tuple(w) + (1.0,) * (3 - nd)
-    voxels = data.size
-    if max_labels is not None:
-        cap = min(int(max_labels), voxels)
-    elif _lib.DTYPE_SIZE[code] <= 2:
-        cap = min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1)
-    else:
-        cap = min(voxels, 65536)
-    lib = _lib.load()
-    while True:
-        keys = np.empty(cap, dtype=buf.dtype)
-        counts, arg = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int64)
-        mx, bbox = np.empty(cap, dtype=np.float32), np.empty((cap, 6), dtype=np.int32)
-        n = ctypes.c_int64(0)
-        _lib.check(lib.edt_hip_label_stats(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
-                                           1 if black_border else 0, None if dt is None else _ptr(dt), cap, _ptr(keys),
-                                           _ptr(counts), _ptr(mx), _ptr(arg), _ptr(bbox), ctypes.byref(n)))
-        n = int(n.value)
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"label_stats: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    keys = keys[:n].view(data.dtype)       # (signed dtypes: the bit patterns back under their own type)
-    counts, mx, arg, bbox = counts[:n], mx[:n], arg[:n], bbox[:n]
-    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
-        perm = np.argsort(keys, kind="stable")
-        keys, counts, mx, arg, bbox = keys[perm], counts[perm], mx[perm], arg[perm], bbox[perm]
+    new = lambda dtype, *shape: np.empty(shape, dtype=dtype)  # noqa: E731
+    keys, counts, mx, arg, bbox = _label_table(
+        "label_stats", data, code, max_labels,
+        lambda cap: [new(buf.dtype, cap), new(np.int64, cap), new(np.float32, cap), new(np.int64, cap), new(np.int32, cap, 6)],
+        lambda cap, cols, n: _lib.load().edt_hip_label_stats(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
+                                                             1 if black_border else 0, None if dt is None else _ptr(dt), cap,
+                                                             *cols, n))
+    n = len(keys)
     lo, hi = bbox[:, 0:2 * nd:2], bbox[:, 1:2 * nd:2]
     argmax = np.stack(np.unravel_index(arg, data.shape, order=order), axis=1).astype(np.int64).reshape(n, nd)
     if order == "C":                       # x is the LAST array axis
@@ -351,32 +358,11 @@ def label_moments(data, max_labels=None):
     data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
     _moments.check_range(data.shape)
     e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    voxels = data.size
-    if max_labels is not None:
-        cap = min(int(max_labels), voxels)
-    elif _lib.DTYPE_SIZE[code] <= 2:
-        cap = min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1)
-    else:
-        cap = min(voxels, 65536)
-    lib = _lib.load()
-    while True:
-        keys = np.empty(cap, dtype=buf.dtype)
-        counts, sums = np.empty(cap, dtype=np.int64), np.empty((cap, 9), dtype=np.int64)
-        centroid, central = np.empty((cap, 3), dtype=np.float64), np.empty((cap, 6), dtype=np.float64)
-        n = ctypes.c_int64(0)
-        _lib.check(lib.edt_hip_label_moments(_ptr(buf), code, nd, e[0], e[1], e[2], cap, _ptr(keys), _ptr(counts), _ptr(sums),
-                                             _ptr(centroid), _ptr(central), ctypes.byref(n)))
-        n = int(n.value)
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"label_moments: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    keys = keys[:n].view(data.dtype)       # (signed dtypes: the bit patterns back under their own type)
-    counts, sums, centroid, central = counts[:n], sums[:n], centroid[:n], central[:n]
-    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
-        perm = np.argsort(keys, kind="stable")
-        keys, counts, sums, centroid, central = keys[perm], counts[perm], sums[perm], centroid[perm], central[perm]
+    keys, counts, sums, centroid, central = _label_table(
+        "label_moments", data, code, max_labels,
+        lambda cap: [np.empty(cap, dtype=buf.dtype), np.empty(cap, dtype=np.int64), np.empty((cap, 9), dtype=np.int64),
+                     np.empty((cap, 3), dtype=np.float64), np.empty((cap, 6), dtype=np.float64)],
+        lambda cap, cols, n: _lib.load().edt_hip_label_moments(_ptr(buf), code, nd, e[0], e[1], e[2], cap, *cols, n))
     got = _moments.assemble(np.ascontiguousarray(keys), counts, sums, centroid, central, nd, order == "C")
     return LabelMoments(*[np.ascontiguousarray(f) for f in got])
 
@@ -409,31 +395,10 @@ def label_topology(data, max_labels=None):
                              np.zeros((0,) + (2,) * nd, dtype=np.int64))
     data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
     e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    voxels = data.size
-    if max_labels is not None:
-        cap = min(int(max_labels), voxels)
-    elif _lib.DTYPE_SIZE[code] <= 2:
-        cap = min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1)
-    else:
-        cap = min(voxels, 65536)
-    lib = _lib.load()
-    while True:
-        keys = np.empty(cap, dtype=buf.dtype)
-        closed, interior = np.empty((cap, 8), dtype=np.int64), np.empty((cap, 8), dtype=np.int64)
-        n = ctypes.c_int64(0)
-        _lib.check(lib.edt_hip_label_topology(_ptr(buf), code, nd, e[0], e[1], e[2], cap, _ptr(keys), _ptr(closed), _ptr(interior),
-                                              ctypes.byref(n)))
-        n = int(n.value)
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"label_topology: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    keys = keys[:n].view(data.dtype)       # (signed dtypes: the bit patterns back under their own type)
-    closed, interior = closed[:n], interior[:n]
-    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
-        perm = np.argsort(keys, kind="stable")
-        keys, closed, interior = keys[perm], closed[perm], interior[perm]
+    keys, closed, interior = _label_table(
+        "label_topology", data, code, max_labels,
+        lambda cap: [np.empty(cap, dtype=buf.dtype), np.empty((cap, 8), dtype=np.int64), np.empty((cap, 8), dtype=np.int64)],
+        lambda cap, cols, n: _lib.load().edt_hip_label_topology(_ptr(buf), code, nd, e[0], e[1], e[2], cap, *cols, n))
     got = _topology.assemble(np.ascontiguousarray(keys), closed, interior, nd, order == "C")
     return LabelTopology(*[np.ascontiguousarray(f) for f in got])
 

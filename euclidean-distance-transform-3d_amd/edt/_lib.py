@@ -17,6 +17,16 @@ LIB_PATH = os.environ.get("EDT_HIP_LIB") or os.path.join(os.path.dirname(_HERE),
 U8, U16, U32, U64, F32, F64, BOOL = range(7)
 DTYPE_SIZE = {U8: 1, U16: 2, U32: 4, U64: 8, F32: 4, F64: 8, BOOL: 1}
 
+
+def default_max_labels(code: int, voxels: int):
+    """(first capacity, whether it is exact) of a ``label_stats`` / ``label_moments`` / ``label_topology`` call without
+    ``max_labels``: 8- and 16-bit labels cannot have more than 255 / 65535 distinct non-zero values; wider ones start at 65536
+    and are retried."""
+    if DTYPE_SIZE[code] <= 2:
+        return min(voxels, (1 << (8 * DTYPE_SIZE[code])) - 1), True
+    return min(voxels, 65536), False
+
+
 FLAG_BLACK_BORDER = 1
 FLAG_SQRT = 2
 FLAG_FORCE_GENERIC = 4

@@ -434,32 +434,41 @@ LabelStats = collections.namedtuple("LabelStats", ["labels", "counts", "max", "a
 _SIGNED_TORCH = (torch.int8, torch.int16, torch.int32, torch.int64)
 
 
-def default_max_labels(code: int, voxels: int):
-    """(first capacity, whether it is exact) of a ``label_stats`` call without ``max_labels``: 8- and 16-bit labels
-    cannot have more than 255 / 65535 distinct non-zero values; wider ones start at 65536 and are retried."""
-    if _lib.DTYPE_SIZE[code] <= 2:
-        return min(voxels, (1 << (8 * _lib.DTYPE_SIZE[code])) - 1), True
-    return min(voxels, 65536), False
+default_max_labels = _lib.default_max_labels
 
 
-def _label_stats_raw(labels, dt, nd, ext, cap):
-    """One call of edt_hip_label_stats_device: (n_labels, keys, counts, max, argmax, bbox) with ``cap`` rows each."""
-    lib = _lib.load()
-    dev = labels.device
-    code = dtype_code(labels.dtype)
-    nbytes = lib.edt_hip_label_stats_workspace_bytes(code, labels.numel(), cap)
+def _fresh_workspace(query, *query_args, device) -> torch.Tensor:
+    """The scratch of one library call, allocated for it: ``query(*query_args)`` bytes on ``device`` (:func:`_workspace` is the
+    cached source; a query that answers 0 is the library's refusal here)."""
+    nbytes = int(getattr(_lib.load(), query)(*query_args))
     if nbytes == 0:
         _lib.check(-2)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    keys = torch.empty(cap, dtype=labels.dtype, device=dev)
-    counts = torch.empty(cap, dtype=torch.int64, device=dev)
-    mx = torch.empty(cap, dtype=torch.float32, device=dev)
-    arg = torch.empty(cap, dtype=torch.int64, device=dev)
-    bbox = torch.empty((cap, 6), dtype=torch.int32, device=dev)
-    n = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.check(lib.edt_hip_label_stats_device(_vp(labels), code, _vp(dt), nd, *ext, cap, _vp(keys), _vp(counts), _vp(mx),
-                                              _vp(arg), _vp(bbox), _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
-    return int(n.item()), keys, counts, mx, arg, bbox
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _label_table(who, labels, max_labels, alloc, call):
+    """What label_stats, label_moments and label_topology do around their device call: the capacity (``max_labels``, or the
+    default rule), the call -- retried with 8x the room while a default capacity proves too small, a ``ValueError`` if an explicit
+    one does --, the columns cut to the ``n`` labels found and, for signed dtypes, brought into signed order.  ``alloc(cap)``:
+    the output columns with ``cap`` rows each, the keys first.  ``call(cap, columns, n)``: the device entry point on its
+    workspace; ``n`` is the int64 device word it writes the number of labels to.  Returns the columns."""
+    voxels = labels.numel()
+    cap = default_max_labels(dtype_code(labels.dtype), voxels)[0] if max_labels is None else min(int(max_labels), voxels)
+    while True:
+        cols = alloc(cap)
+        count = torch.empty(1, dtype=torch.int64, device=labels.device)
+        call(cap, cols, count)
+        n = int(count.item())           # the only host synchronisation
+        if n <= cap:
+            break
+        if max_labels is not None:
+            raise ValueError(f"{who}: more than max_labels = {int(max_labels)} distinct non-zero labels")
+        cap = min(voxels, 8 * cap)
+    cols = [c[:n] for c in cols]
+    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
+        perm = torch.argsort(cols[0], stable=True)
+        cols = [c[perm] for c in cols]
+    return cols
 
 
 def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> LabelStats:
@@ -474,32 +483,26 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
     labels, dt = as_device_tensor(labels), as_device_tensor(dt)
     if labels.shape != dt.shape or dt.dtype != torch.float32:
         raise ValueError("dt must be a float32 tensor of the labels' shape")
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"label_stats: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    labels, nd, code, ext = _label_op_tensor(labels, "label_stats")
     if max_labels is not None and int(max_labels) < 1:
         raise ValueError(f"label_stats: max_labels must be at least 1, got {max_labels}")
-    nd = labels.dim()
     dev = labels.device
-    code = dtype_code(labels.dtype)
-    voxels = labels.numel()
-    if voxels == 0:
-        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+    z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+    if labels.numel() == 0:
         return LabelStats(z(labels.dtype, 0), z(torch.int64, 0), z(torch.float32, 0), z(torch.int64, 0, nd),
                           z(torch.int32, 0, nd), z(torch.int32, 0, nd))
     labels, dt = labels.contiguous(), dt.contiguous()
-    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-    cap = default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
-    while True:
-        n, keys, counts, mx, arg, bbox = _label_stats_raw(labels, dt, nd, ext, cap)
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"label_stats: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    keys, counts, mx, arg, bbox = keys[:n], counts[:n], mx[:n], arg[:n], bbox[:n]
-    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
-        perm = torch.argsort(keys, stable=True)
-        keys, counts, mx, arg, bbox = keys[perm], counts[perm], mx[perm], arg[perm], bbox[perm]
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+
+    def call(cap, cols, n):
+        ws = _fresh_workspace("edt_hip_label_stats_workspace_bytes", code, labels.numel(), cap, device=dev)
+        _lib.check(_lib.load().edt_hip_label_stats_device(_vp(labels), code, _vp(dt), nd, *ext, cap, *map(_vp, cols), _vp(n),
+                                                          _vp(ws), ws.numel(), _stream_ptr()))
+
+    keys, counts, mx, arg, bbox = _label_table(
+        "label_stats", labels, max_labels,
+        lambda cap: [e(labels.dtype, cap), e(torch.int64, cap), e(torch.float32, cap), e(torch.int64, cap), e(torch.int32, cap, 6)],
+        call)
     coords = []
     for extent in ext[:nd]:            # x, y, z of the flat index
         coords.append(arg % extent)
@@ -510,26 +513,6 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
     return LabelStats(keys, counts, mx, argmax, lo, hi)
 
 
-def _label_moments_raw(labels, nd, ext, cap):
-    """One call of edt_hip_label_moments_device: (n_labels, keys, counts, sums, centroid, central) with ``cap`` rows each."""
-    lib = _lib.load()
-    dev = labels.device
-    code = dtype_code(labels.dtype)
-    nbytes = lib.edt_hip_label_moments_workspace_bytes(code, labels.numel(), cap)
-    if nbytes == 0:
-        _lib.check(-2)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    keys = torch.empty(cap, dtype=labels.dtype, device=dev)
-    counts = torch.empty(cap, dtype=torch.int64, device=dev)
-    sums = torch.empty((cap, 9), dtype=torch.int64, device=dev)
-    centroid = torch.empty((cap, 3), dtype=torch.float64, device=dev)
-    central = torch.empty((cap, 6), dtype=torch.float64, device=dev)
-    n = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.check(lib.edt_hip_label_moments_device(_vp(labels), code, nd, *ext, cap, _vp(keys), _vp(counts), _vp(sums), _vp(centroid),
-                                                _vp(central), _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
-    return int(n.item()), keys, counts, sums, centroid, central
-
-
 def label_moments(labels: torch.Tensor, max_labels=None) -> LabelMoments:
     """Device-resident :func:`edt.label_moments`: one table row per distinct non-zero label in ONE streaming sweep over
     ``labels``, nothing else is read (contract: include/edt_hip.h, "label_moments").  The named tuple
@@ -537,34 +520,27 @@ def label_moments(labels: torch.Tensor, max_labels=None) -> LabelMoments:
     ascending (signed dtypes in signed order), the voxel count, the exact raw first ``(n, ndim)`` and second ``(n, ndim, ndim)``
     moments (int64), centroid and population covariance in voxel units (float64).  The table stays on the device; the only
     host synchronisation is reading the number of labels.  ``max_labels`` and the range bound: as :func:`edt.label_moments`."""
-    labels = as_device_tensor(labels)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"label_moments: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
+    labels, nd, code, ext = _label_op_tensor(labels, "label_moments")
     if max_labels is not None and int(max_labels) < 1:
         raise ValueError(f"label_moments: max_labels must be at least 1, got {max_labels}")
-    nd = labels.dim()
     dev = labels.device
-    code = dtype_code(labels.dtype)
-    voxels = labels.numel()
-    if voxels == 0:
+    if labels.numel() == 0:
         z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
         return LabelMoments(z(labels.dtype, 0), z(torch.int64, 0), z(torch.int64, 0, nd), z(torch.int64, 0, nd, nd),
                             z(torch.float64, 0, nd), z(torch.float64, 0, nd, nd))
     _moments.check_range(labels.shape)
     labels = labels.contiguous()
-    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-    cap = default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
-    while True:
-        n, keys, counts, sums, centroid, central = _label_moments_raw(labels, nd, ext, cap)
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"label_moments: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    keys, counts, sums, centroid, central = keys[:n], counts[:n], sums[:n], centroid[:n], central[:n]
-    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
-        perm = torch.argsort(keys, stable=True)
-        keys, counts, sums, centroid, central = keys[perm], counts[perm], sums[perm], centroid[perm], central[perm]
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+
+    def call(cap, cols, n):
+        ws = _fresh_workspace("edt_hip_label_moments_workspace_bytes", code, labels.numel(), cap, device=dev)
+        _lib.check(_lib.load().edt_hip_label_moments_device(_vp(labels), code, nd, *ext, cap, *map(_vp, cols), _vp(n), _vp(ws),
+                                                            ws.numel(), _stream_ptr()))
+
+    keys, counts, sums, centroid, central = _label_table(
+        "label_moments", labels, max_labels,
+        lambda cap: [e(labels.dtype, cap), e(torch.int64, cap), e(torch.int64, cap, 9), e(torch.float64, cap, 3), e(torch.float64, cap, 6)],
+        call)
     return _moments.assemble(keys, counts, sums, centroid, central, nd, True)
 
 
@@ -613,31 +589,19 @@ def label_topology(labels: torch.Tensor, max_labels=None) -> LabelTopology:
     if max_labels is not None and int(max_labels) < 1:
         raise ValueError(f"label_topology: max_labels must be at least 1, got {max_labels}")
     dev = labels.device
-    voxels = labels.numel()
-    if voxels == 0:
+    if labels.numel() == 0:
         z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
         return LabelTopology(z(labels.dtype, 0), z(torch.int64, 0), z(torch.int64, 0, *(2,) * nd), z(torch.int64, 0, *(2,) * nd))
     labels = labels.contiguous()
-    lib = _lib.load()
-    cap = default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
-    while True:
-        ws = _workspace("edt_hip_label_topology_workspace_bytes", code, voxels, cap, device=dev)
-        keys = torch.empty(cap, dtype=labels.dtype, device=dev)
-        closed = torch.empty((cap, 8), dtype=torch.int64, device=dev)
-        interior = torch.empty((cap, 8), dtype=torch.int64, device=dev)
-        count = torch.empty(1, dtype=torch.int64, device=dev)
-        _lib.check(lib.edt_hip_label_topology_device(_vp(labels), code, nd, *ext, cap, _vp(keys), _vp(closed), _vp(interior),
-                                                     _vp(count), _vp(ws), ws.numel(), _stream_ptr()))
-        n = int(count.item())
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"label_topology: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    keys, closed, interior = keys[:n], closed[:n], interior[:n]
-    if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
-        perm = torch.argsort(keys, stable=True)
-        keys, closed, interior = keys[perm], closed[perm], interior[perm]
+    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+
+    def call(cap, cols, n):
+        ws = _workspace("edt_hip_label_topology_workspace_bytes", code, labels.numel(), cap, device=dev)
+        _lib.check(_lib.load().edt_hip_label_topology_device(_vp(labels), code, nd, *ext, cap, *map(_vp, cols), _vp(n), _vp(ws),
+                                                             ws.numel(), _stream_ptr()))
+
+    keys, closed, interior = _label_table("label_topology", labels, max_labels,
+                                          lambda cap: [e(labels.dtype, cap), e(torch.int64, cap, 8), e(torch.int64, cap, 8)], call)
     return _topology.assemble(keys, closed, interior, nd, True)
 
 

@@ -154,9 +154,21 @@ def test_range_bound(shim):
         assert bool(shim.moments_in_range(*ext)) == want, ext
 
 
-def test_kernels_of_the_unit_use_no_scratch():
-    """csrc/edt_moments.hip compiled for gfx950 (device code only): every kernel's scratch size is 0, and the sweep keeps the
-    LDS table that gives 7 workgroups per compute unit"""
+# unit -> (kernels: clear, 7 per sweep, finish_direct, compact, rank; {sweep: (LDS bytes, waves per SIMD its registers have to
+# admit -- what it has had since it was written: a register more than that occupancy's budget costs a whole wave)}; sweeps
+# whose LDS table has to admit 7 workgroups per compute unit; sweeps that have to fit 256 VGPRs)
+_UNITS = {
+    "edt_labelstats.hip": (18, {"k_ls_sweep1": (22528, 6), "k_ls_sweep2": (5120, 8)}, ("k_ls_sweep1",), ()),
+    "edt_moments.hip": (11, {"k_mm_sweep": (22528, 7)}, ("k_mm_sweep",), ()),
+    "edt_topology.hip": (11, {"k_tp_sweep": (18432, 2)}, (), ("k_tp_sweep",)),
+}
+
+
+@pytest.mark.parametrize("unit", sorted(_UNITS))
+def test_kernels_of_the_unit_use_no_scratch(unit):
+    """A unit of the per-label tables compiled for gfx950 (device code only): every kernel's scratch size is 0, every sweep
+    keeps its LDS size -- for label_stats' first sweep and the moments sweep the table that gives 7 workgroups per compute
+    unit --, no sweep of any label type loses a wave per SIMD, and the topology sweep, the tight one, stays within 256 VGPRs"""
     import re
     import shutil
     import tempfile
@@ -167,15 +179,24 @@ def test_kernels_of_the_unit_use_no_scratch():
     with tempfile.TemporaryDirectory() as d:
         res = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
                               "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S",
-                              "-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(d, "moments.s"),
-                              os.path.join(csrc, "edt_moments.hip")], capture_output=True, text=True, check=True)
+                              "-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(d, "unit.s"),
+                              os.path.join(csrc, unit)], capture_output=True, text=True, check=True)
+    kernels, lds_of, seven, tight = _UNITS[unit]
     names = re.findall(r"Function Name: (\S+)", res.stderr)
     scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", res.stderr)]
     lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", res.stderr)]
-    assert len(names) == len(scratch) == len(lds) == 11, names      # clear, 7 sweeps, finish_direct, compact, rank
-    assert scratch == [0] * 11, dict(zip(names, scratch))
-    sweeps = [b for n, b in zip(names, lds) if "k_mm_sweep" in n]
-    assert len(sweeps) == 7 and all(7 * b <= 160 * 1024 for b in sweeps), sweeps
+    vgprs = [int(v) for v in re.findall(r" VGPRs: (\d+)", res.stderr)]
+    waves = [int(v) for v in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", res.stderr)]
+    assert len(names) == len(scratch) == len(lds) == len(vgprs) == len(waves) == kernels, names
+    assert scratch == [0] * kernels, dict(zip(names, scratch))
+    for sweep, (want, occupancy) in lds_of.items():
+        got = [b for n, b in zip(names, lds) if sweep in n]
+        assert got == [want] * 7, (sweep, got)                      # one sweep per label type
+        assert all(w >= occupancy for n, w in zip(names, waves) if sweep in n), (sweep, dict(zip(names, waves)))
+        if sweep in seven:
+            assert all(7 * b <= 160 * 1024 for b in got), (sweep, got)
+        if sweep in tight:
+            assert all(v <= 256 for n, v in zip(names, vgprs) if sweep in n), dict(zip(names, vgprs))
 
 
 # ---- 3. the ABI's refusals ----------------------------------------------------------------------------------------------
