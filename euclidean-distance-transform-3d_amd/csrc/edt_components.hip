@@ -61,34 +61,7 @@ template <typename T> __device__ __forceinline__ T cc_shfl_up1(T v) {
   return v;
 }
 
-// the root above i: strictly downhill (P[j] <= j), so at most i steps
-__device__ __forceinline__ uint32_t cc_find(uint32_t *P, uint32_t i) {
-  const uint32_t from = i;
-  int steps = 0;
-  for (;;) {
-    const uint32_t p = parent_peek(&P[i]);
-    if (p >= i) break;  // a root (p == i); p > i cannot be (background is never walked)
-    i = p;
-    ++steps;
-  }
-  if (steps > 2) atomicMin(&P[from], i);  // i is an ancestor of `from`: the old parent keeps its own path to it
-  return i;
-}
-
-__device__ void cc_union(uint32_t *P, uint32_t a, uint32_t b) {
-  a = cc_find(P, a);
-  b = cc_find(P, b);
-  while (a != b) {  // a + b strictly decreases
-    if (a < b) {
-      const uint32_t t = a;
-      a = b;
-      b = t;
-    }
-    const uint32_t old = atomicMin(&P[a], b);
-    if (old == a) break;
-    a = old;
-  }
-}
+// (cc_find, cc_union: edt_forest.h)
 
 // ---- phase 1: x-runs ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -273,7 +246,7 @@ size_t components_workspace_bytes(int64_t voxels) {
   return align_up((size_t)ceil_div(std::max<int64_t>(voxels, 1), kCcChunk) * sizeof(uint32_t), 256);
 }
 
-// (contract: edt_forest.h)
+// (contracts of the three launchers: edt_forest.h)
 int launch_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary, uint32_t *P,
                   void *chunks, const char *who, hipStream_t stream) {
   const int64_t voxels64 = sx * sy * sz;
@@ -301,35 +274,45 @@ int launch_forest(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t
                          (uint32_t)sx, (uint32_t)sy, connectivity, bin);
       EDT_HIP_TRY(hipGetLastError());
     }
-    ScopedPass sp(flatten, stream);
-    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, voxels,
-                       static_cast<uint32_t *>(chunks));
-    EDT_HIP_TRY(hipGetLastError());
-    return EDT_OK;
+    return launch_forest_flatten(P, voxels64, chunks, flatten, stream);
   });
 }
 
-int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
-                      uint32_t *out, int64_t *n, void *ws, hipStream_t stream) {
-  const int rc = launch_forest(dtype, labels, sx, sy, sz, connectivity, binary, out, ws, "components", stream);
-  if (rc != EDT_OK) return rc;
-  const int64_t voxels64 = sx * sy * sz;
+int launch_forest_flatten(uint32_t *P, int64_t voxels64, void *chunks, const char *name, hipStream_t stream) {
+  ScopedPass sp(name, stream);
+  hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)ceil_div(voxels64, kCcChunk)), dim3(kCcThreads), 0, stream, P, (uint32_t)voxels64,
+                     static_cast<uint32_t *>(chunks));
+  EDT_HIP_TRY(hipGetLastError());
+  return EDT_OK;
+}
+
+int launch_forest_number(uint32_t *out, int64_t voxels64, void *chunks, int64_t *n, const char *who, hipStream_t stream) {
   const uint32_t voxels = (uint32_t)voxels64;
-  uint32_t *chunk = static_cast<uint32_t *>(ws);
+  uint32_t *chunk = static_cast<uint32_t *>(chunks);
   const uint32_t nchunks = (uint32_t)ceil_div(voxels64, kCcChunk);
+  char number[40], final[40];
+  snprintf(number, sizeof number, "%s number", who);
+  snprintf(final, sizeof final, "%s final", who);
   {
-    ScopedPass sp("components number", stream);
+    ScopedPass sp(number, stream);
     hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kCcScan), 0, stream, chunk, nchunks, n);
     EDT_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_cc_number, dim3(nchunks), dim3(kCcThreads), 0, stream, out, voxels, chunk);
     EDT_HIP_TRY(hipGetLastError());
   }
   {
-    ScopedPass sp("components final", stream);
+    ScopedPass sp(final, stream);
     hipLaunchKernelGGL(k_cc_final, dim3((unsigned)ceil_div(voxels64, kCcThreads)), dim3(kCcThreads), 0, stream, out, voxels);
     EDT_HIP_TRY(hipGetLastError());
   }
   return EDT_OK;
+}
+
+int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
+                      uint32_t *out, int64_t *n, void *ws, hipStream_t stream) {
+  const int rc = launch_forest(dtype, labels, sx, sy, sz, connectivity, binary, out, ws, "components", stream);
+  if (rc != EDT_OK) return rc;
+  return launch_forest_number(out, sx * sy * sz, ws, n, "components", stream);
 }
 
 // sx * sy * sz <= 2^31 - 1, in 64-bit arithmetic (extents are at most 2^31 - 1 each: check_shape)

@@ -701,6 +701,58 @@ int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy
       });
 }
 
+// watershed on host buffers (kernels: edt_watershed.hip): labels up once -- and the caller's field, if it brings one; else the
+// ordinary transform runs here, with sqrt, under `binary` on the mask labels != 0 --, the operation on the device, the basins
+// and their number down once.
+int edt_hip_watershed(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, const float *field, float wx,
+                      float wy, float wz, int flags, int connectivity, int binary, float min_saliency, uint32_t *out, int64_t *n) {
+  float *const w[3] = {&wx, &wy, &wz};
+  bool empty;
+  int rc = host_prologue(dtype, ndim, sx, sy, sz, field ? nullptr : w, !labels || !out, &empty, [&](After what) -> int {
+    if (what == After::shape) {
+      const int own = watershed_check_args(dtype, ndim, sx, sy, sz, connectivity, min_saliency);
+      if (own != EDT_OK) return own;
+      if (flags & ~EDT_FLAG_BLACK_BORDER) { set_error("watershed: flags other than EDT_FLAG_BLACK_BORDER"); return EDT_ERR_BAD_ARG; }
+    }
+    if (what == After::voxel_sizes && !n) { set_error("null host pointer"); return EDT_ERR_BAD_ARG; }
+    return EDT_OK;
+  });
+  if (rc == EDT_OK && empty) *n = 0;
+  if (rc != EDT_OK || empty) return rc;
+  ListedDevice on_listed_device;
+  if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
+  const int64_t voxels = sx * sy * sz;
+  const bool mask = !field && binary && dtype != EDT_BOOL;  // the transform of the mask, not of the labels
+  const int tdtype = mask ? EDT_U8 : dtype;
+  const int tflags = (flags & EDT_FLAG_BLACK_BORDER) | EDT_FLAG_SQRT | (env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0);
+  const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float), obytes = (size_t)voxels * sizeof(uint32_t);
+  const size_t sbytes = edt_hip_watershed_workspace_bytes(dtype, ndim, sx, sy, sz);
+  const size_t wbytes = std::max(sbytes, field ? 0 : edt_hip_workspace_bytes_flags(tdtype, ndim, sx, sy, sz, tflags));
+  constexpr size_t kMaskAt = 256;  // kAux: n, then the mask
+  Staging st;
+  if ((rc = st.alloc({{kLabels, lbytes}, {kSecondField, fbytes}, {kOut, obytes}, {kWorkspace, wbytes},
+                      {kAux, kMaskAt + (mask ? (size_t)voxels : 0)}})) != EDT_OK)
+    return rc;
+  st.expect(out, obytes);
+  if ((rc = st.up(kLabels, labels, lbytes)) != EDT_OK) return rc;
+  if (field) {
+    rc = st.up(kSecondField, field, fbytes);
+  } else {
+    const void *src = st.p[kLabels];
+    if (mask) {
+      rc = launch_is_foreground(dtype, st.p[kLabels], st.at<uint8_t>(kAux) + kMaskAt, voxels, nullptr);
+      src = st.at<uint8_t>(kAux) + kMaskAt;
+    }
+    if (rc == EDT_OK)
+      rc = run_device(src, tdtype, ndim, sx, sy, sz, wx, wy, wz, tflags, st.at<float>(kSecondField), st.p[kWorkspace], wbytes, nullptr);
+  }
+  if (rc != EDT_OK) return rc;
+  rc = edt_hip_watershed_device(st.p[kLabels], dtype, ndim, sx, sy, sz, st.at<const float>(kSecondField), connectivity, binary,
+                                min_saliency, st.at<uint32_t>(kOut), st.at<int64_t>(kAux), st.p[kWorkspace], wbytes, nullptr);
+  if (rc != EDT_OK || (rc = st.down(out, kOut, obytes)) != EDT_OK) return rc;
+  return st.down(n, kAux, sizeof(int64_t));
+}
+
 // erode / dilate / opening / closing, local thickness and the medial axis on host buffers (contracts: include/edt_hip.h,
 // "morphology", "local thickness", "medial axis"): staging around the one composition of each, its *_device entry point
 // (edt_fieldops.hip) -- labels up once, the call on the pooled buffers with one workspace, the outputs down once.  What the host

@@ -317,4 +317,7 @@ int launch_components(int dtype, const void *labels, int64_t sx, int64_t sy, int
 // what components_check_args refuses, then min_voxels < 0 and max_voxels < min_voxels
 int dust_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int64_t min_voxels,
                     int64_t max_voxels);
+// ---- watershed (the basins of a field by steepest ascent, as the components of a graph): edt_watershed.hip ----------
+// what components_check_args refuses, then min_saliency negative or not finite
+int watershed_check_args(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, float min_saliency);
 }  // namespace edt_amd

@@ -42,7 +42,7 @@ __all__ = [
     "label_stats", "label_moments", "LabelMoments", "label_topology", "LabelTopology",
     "connected_components", "fill_holes", "dust", "DustCounts",
     "erode", "dilate", "opening", "closing", "local_thickness", "ThicknessSizes",
-    "medial_axis",
+    "medial_axis", "watershed",
 ]
 
 
@@ -540,6 +540,68 @@ def dust(data, threshold, connectivity=None, binary=False, invert=False, return_
     _lib.check(_lib.load().edt_hip_dust(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, lo, hi,
                                         1 if invert else 0, _ptr(out), _ptr(counts)))
     return (out, DustCounts(*(int(v) for v in counts))) if return_counts else out
+
+
+def _min_saliency(min_saliency):
+    """min_saliency as the float32 the ABI takes: finite and >= 0, else ValueError."""
+    try:
+        with np.errstate(over="ignore"):
+            h = float(np.float32(min_saliency))
+    except (TypeError, ValueError):
+        h = math.nan
+    if isinstance(min_saliency, (bool, np.bool_)) or not (h >= 0.0 and math.isfinite(h)):
+        raise ValueError(f"watershed: min_saliency must be finite (as float32) and >= 0, got {min_saliency!r}")
+    return h
+
+
+def watershed(data, field=None, min_saliency=0.0, connectivity=None, anisotropy=None, black_border=False, binary=False,
+              return_N=False):
+    """Split every label of a 1-D to 3-D label array into the basins of a float32 field, on the device (contract:
+    include/edt_hip.h, "watershed").  This is the STEEPEST-ASCENT watershed -- "drop of water", hill climbing -- stated as the
+    connected components of a graph: every voxel is joined to its greatest neighbour of the same object (ties: the first in
+    memory order), a voxel without a greater one to its equal neighbours, and the basins are the components of these joins.
+    It is NOT ``skimage.segmentation.watershed``: it takes no markers, its boundaries follow the ascent rule and not a flooding
+    order, and ties go to the greatest neighbour, not the steepest slope, so anisotropy enters through the field only.  Neither
+    skimage nor cc3d is on the build machine: what is tested is the header's contract.
+
+    ``field``: a float32 array of ``data``'s shape without NaN on the foreground (``ValueError``); ``+inf`` is legal.
+    ``field=None`` computes ``edt(data, anisotropy, black_border)`` -- of ``data != 0`` under ``binary`` -- on the device
+    inside the same call; ``anisotropy`` and ``black_border`` are used for nothing else.
+    ``min_saliency``: ``h >= 0`` in the field's units.  ``h > 0`` joins two neighbouring basins whose saddle voxels reach the
+    lower of their two peaks minus ``h``, in ONE round of single-linkage merging over the basins of the ascent: it is not the
+    h-maxima hierarchy, a chain of shallow saddles merges end to end.  Half a voxel removes the over-segmentation of the
+    ascent along digital ridges; ``1e30`` gives :func:`connected_components` itself.
+    ``connectivity`` and ``binary`` as in :func:`connected_components`: two voxels are of one object iff that function
+    would connect them (``-0.0`` is background, a NaN label is alone, a bool array is always binary).
+
+    Returns a ``uint32`` array of ``data``'s shape and memory order: 0 for background, else the basin's number in ``1..N``,
+    in the order in which a scan of the array's MEMORY meets the basins; with ``return_N=True`` the pair ``(out, N)``.
+    ``label_stats(watershed(x), dt)`` is then a table per SPLIT object.  At most 2^31 - 1 voxels."""
+    data, nd = _label_op_array(data, "watershed")
+    c = _connectivity(connectivity, nd, who="watershed")
+    h = _min_saliency(min_saliency)
+    if field is not None:
+        field = np.asarray(field)
+        if field.shape != data.shape or field.dtype != np.float32:
+            raise ValueError("watershed: field must be a float32 array of the data's shape")
+    an = (1.0,) * nd if anisotropy is None else anisotropy
+    if data.size == 0:
+        out = np.zeros(data.shape, dtype=np.uint32)
+        return (out, 0) if return_N else out
+    data, order, code, buf, extents, w = _layout(data, an, nd)
+    if field is not None:
+        with np.errstate(invalid="ignore"):
+            if np.isnan(field[data != 0]).any():
+                raise ValueError("watershed: the field is NaN on a foreground voxel")
+        field = np.asfortranarray(field) if order == "F" else np.ascontiguousarray(field)
+    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
+    ww = tuple(w) + (1.0,) * (3 - nd)
+    out = np.empty(data.shape, dtype=np.uint32, order=order)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().edt_hip_watershed(_ptr(buf), code, nd, e[0], e[1], e[2], None if field is None else _ptr(field),
+                                             ww[0], ww[1], ww[2], 1 if black_border else 0, c, 1 if binary else 0, h,
+                                             _ptr(out), ctypes.byref(n)))
+    return (out, int(n.value)) if return_N else out
 
 
 def _morph_radius(radius, who, inf_allowed=False):

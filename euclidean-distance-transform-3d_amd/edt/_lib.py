@@ -131,6 +131,9 @@ SIGNATURES = {
     "edt_hip_dust_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
     "edt_hip_dust_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
     "edt_hip_dust": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i, _vp, _vp]),
+    "edt_hip_watershed_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64]),
+    "edt_hip_watershed_device": (_i, [_vp, _i, _i, _i64, _i64, _i64, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "edt_hip_watershed": (_i, [_vp, _i, _i, _i64, _i64, _i64, _vp, _f, _f, _f, _i, _i, _i, _f, _vp, _vp]),
     "edt_hip_is_foreground_device": (_i, [_vp, _i, _vp, _i64, _vp]),
     "edt_hip_morph_select_device": (_i, [_vp, _vp, _i, _vp, _d, _i, _vp, _vp, _i64, _vp]),
     "edt_hip_morphology_workspace_bytes": (_sz, [_i, _i, _i64, _i64, _i64, _i, _i]),

@@ -678,6 +678,45 @@ def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, inver
     return out, counts
 
 
+def watershed(labels: torch.Tensor, field: torch.Tensor = None, min_saliency=0.0, connectivity=None, anisotropy=None,
+              black_border=False, binary=False):
+    """:func:`edt.watershed` on a device array (semantics of a C-ordered array: the last tensor axis is fastest, and basins are
+    numbered in the tensor's memory order; contract: include/edt_hip.h, "watershed"): the STEEPEST-ASCENT watershed ("drop of
+    water", hill climbing) as the connected components of a graph.  It is not ``skimage.segmentation.watershed``: no markers,
+    boundaries by the ascent rule and not a flooding order, ties to the greatest neighbour and not the steepest slope (so
+    anisotropy enters through the field only); ``min_saliency`` is one round of single-linkage merging, not the h-maxima
+    hierarchy.  Neither skimage nor cc3d is on the build machine: what is tested is the header's contract.
+
+    ``field``: a float32 device tensor of the labels' shape; it is NOT looked at -- a NaN on a foreground voxel leaves the
+    partition unspecified (the call still terminates, with numbers in ``0..N``).  ``field=None`` calls
+    ``edt(labels, anisotropy, black_border)`` first, on ``labels != 0`` under ``binary``.
+    Returns ``(out, n)``: ``out`` an int32 tensor of the labels' shape -- 0 for background, else the basin's number in ``1..N``
+    -- and ``n`` a 0-dim int64 DEVICE tensor holding ``N``: the call only enqueues kernels on the current stream, nothing is read
+    back and nothing waits.  The scratch (4 bytes per voxel, the size of fill_holes') is cached per shape and stream.
+
+    ``label_stats(watershed(x)[0], dt)`` is then a table per SPLIT object, without leaving the device."""
+    from . import _connectivity, _min_saliency
+    labels, nd, code, ext = _label_op_tensor(labels, "watershed")
+    c = _connectivity(connectivity, nd, who="watershed")
+    h = _min_saliency(min_saliency)
+    if field is not None:
+        field = as_device_tensor(field)
+        if field.shape != labels.shape or field.dtype != torch.float32 or field.device != labels.device:
+            raise ValueError("watershed: field must be a float32 tensor of the labels' shape on their device")
+    out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    if labels.numel() == 0:
+        return out, torch.zeros((), dtype=torch.int64, device=labels.device)
+    labels = labels.contiguous()
+    if field is None:
+        field = edt(labels != 0 if binary and labels.dtype != torch.bool else labels, anisotropy, black_border)
+    field = field.contiguous()
+    n = torch.empty((), dtype=torch.int64, device=labels.device)
+    ws = _workspace("edt_hip_watershed_workspace_bytes", code, nd, *ext, device=labels.device)
+    _lib.check(_lib.load().edt_hip_watershed_device(_vp(labels), code, nd, *ext, _vp(field), c, 1 if binary else 0, h, _vp(out),
+                                                    _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
+    return out, n
+
+
 def _morph_select(code, values, field, radius, rule, out=None, mask=None, guard=None):
     """edt_hip_morph_select_device over ``field.numel()`` voxels; ``code``: the dtype code of values / guard / out"""
     _lib.check(_lib.load().edt_hip_morph_select_device(

@@ -668,6 +668,58 @@ int edt_hip_dust_device(const void *d_labels, int dtype, int ndim, int64_t sx, i
 int edt_hip_dust(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int connectivity, int binary,
                  int64_t min_voxels, int64_t max_voxels, int invert, void *out, int64_t *counts);
 
+/* ---- watershed: every label is split into the basins of a float32 field -------------------------------------------------
+ * This is the STEEPEST-ASCENT watershed ("drop of water", hill climbing), stated as the connected components of a graph: no
+ * iteration, no thread waits for another, the same bits on every run, nothing depends on who won an atomic.  It is NOT the
+ * priority-flood watershed of skimage.segmentation.watershed: it takes no markers, and its boundaries follow the ascent rule
+ * below, not a flooding order.  A voxel goes to its GREATEST neighbour, not along the steepest slope, so voxel sizes enter
+ * through the field only.  min_saliency is ONE round of single-linkage merging, not the h-maxima hierarchy: a chain of shallow
+ * saddles merges end to end.  Neither skimage nor cc3d is on the build machine: what is tested is this contract.
+ * Conventions as in the connected-components section: x fastest, idx = x + sx * (y + sy * z); adjacency by connectivity = c,
+ *   1 <= c <= ndim, as there.
+ * Inputs: labels of any label dtype; field, one float32 per voxel; min_saliency = h, finite and >= 0, in the field's units.
+ * Of one object: two neighbouring voxels are of one object iff connected_components would connect them: equal non-zero labels
+ *   (-0.0 is background, a NaN voxel is alone), or, with binary != 0 or EDT_BOOL, both non-zero.
+ * Field values: every comparison is an IEEE float32 comparison of the values as given; nothing is recomputed, squared or rounded.
+ * Phase 1, ascent.  For a foreground voxel v let M be the greatest f(u) over its neighbours u of one object with v.  If
+ *   M > f(v), v is joined to the neighbour that attains M -- on a tie the one of smallest idx.  Otherwise v is a TOP voxel and is
+ *   joined to EVERY neighbour u of one object with f(u) == f(v).  The BASINS are the connected components of these joins.  A
+ *   regional maximum, plateaus included, is one basin's summit.  A plateau that is not a maximum drains through its outlets;
+ *   if it has outlets to two summits it joins their basins.
+ * Phase 2, one round of saliency merges; skipped when h == 0, where it would change nothing.  peak(B) is the greatest f over
+ *   basin B.  For every pair of neighbouring voxels u in A, v in B of one object, A and B basins of phase 1, A and B are joined
+ *   iff  min(f(u), f(v)) >= min(peak(A), peak(B)) - h,  in float32 with one subtraction, on the phase-1 basins and their peaks.
+ *   The result is the transitive closure of those joins; nothing that is evaluated depends on a join made.
+ * Output: one uint32 per voxel -- 0 where the label is background, else the basin's number in 1..N, numbered as
+ *   connected_components numbers: in ascending order of the smallest idx among a basin's voxels.  *n receives N as int64.
+ *   With a constant field, or with h = 1e30 on a finite field, the output is that of connected_components bit for bit.
+ * Field preconditions: +inf is legal (a transform without a black border produces it) and handled by IEEE alone.  A NaN on a
+ *   foreground voxel is the caller's error: the partition is then unspecified, but the call terminates and writes numbers in
+ *   0..N -- every loop is bounded by the forest's downhill rule, whatever the values.  The entry points do not look at the field.
+ * Determinism: the same call gives the same output, bit for bit; the unions race, the result does not.
+ * Limits: sx * sy * sz <= 2^31 - 1, as for connected components. */
+
+/* Scratch of edt_hip_watershed_device: the output array serves as the parent plane; 4 bytes per voxel (the peak plane of
+ * phase 2) plus the scratch of edt_hip_components_workspace_bytes, each rounded up to 256 bytes -- what
+ * edt_hip_fill_holes_workspace_bytes gives.  0 for a bad dtype or shape, or a volume past the limit. */
+size_t edt_hip_watershed_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz);
+/* Refused before any device work, in the order of edt_hip_connected_components_device and with its codes: bad dtype, ndim
+ * outside 1..3, unused extents not 1 (EDT_ERR_BAD_ARG); connectivity outside 1..ndim (EDT_ERR_BAD_ARG); a volume past the
+ * limit (EDT_ERR_UNSUPPORTED); then min_saliency negative or not finite (EDT_ERR_BAD_ARG); NULL pointers, d_out overlapping
+ * the labels or the field, a missing, too small or misaligned scratch (d_scratch is the call's workspace: 256-byte aligned, at
+ * least the query's bytes) (EDT_ERR_BAD_ARG).  Enqueue-only on `stream`: no allocation, no synchronisation; the scratch is
+ * initialised by the call itself.  d_n: one int64 on the device.  An empty volume only sets *d_n = 0. */
+int edt_hip_watershed_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, const float *d_field,
+                             int connectivity, int binary, float min_saliency, uint32_t *d_out, int64_t *d_n, void *d_scratch,
+                             size_t scratch_bytes, void *stream);
+/* The same on host buffers (synchronous, on the cached device buffers of the host-buffer entry points; under
+ * edt_hip_set_devices on the first listed device): labels (and the field) up once, out and n down once.  field == NULL: the
+ * field is this library's own transform (with sqrt) of the labels -- of the mask labels != 0 under binary -- with the voxel
+ * sizes wx, wy, wz and flags (EDT_FLAG_BLACK_BORDER or 0), computed on the device; with a field the voxel sizes and flags are
+ * not looked at, except that any other flag is EDT_ERR_BAD_ARG, refused after min_saliency.  An empty volume sets *n = 0. */
+int edt_hip_watershed(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, const float *field, float wx,
+                      float wy, float wz, int flags, int connectivity, int binary, float min_saliency, uint32_t *out, int64_t *n);
+
 /* ---- morphology: spherical erode / dilate / opening / closing of a label volume, through the distance transform ----------
  * Conventions as elsewhere in this header: x fastest, idx = x + sx * (y + sy * z); label 0 is background, compared with the
  * type's == (so -0.0 is background and a NaN is foreground); voxel sizes as for edt_hip_edtsq_device.  The structuring element is
