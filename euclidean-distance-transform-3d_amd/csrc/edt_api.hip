@@ -1,6 +1,7 @@
-// edt_api.hip -- the C ABI (include/edt_hip.h), part 1 of 3: the plan of a call and the dispatch of its passes on
-// device-resident data (run_device), workspace carving, per-pass event timing, the device entry points that are not
-// sharded.  Part 2: edt_host.hip (host-buffer staging); part 3: edt_shard_api.hip (the phases of the Z-sharded path).
+// edt_api.hip -- the C ABI (include/edt_hip.h), part 1 of 3: the route of a call on device-resident data -- decided once, on
+// the host, by route_of --, the workspace carved from it (make_plan), the launches it names (run_device), per-pass event timing,
+// the device entry points that are not sharded.  Part 2: edt_host.hip (host-buffer staging); part 3: edt_shard_api.hip (the
+// phases of the Z-sharded path).
 // No compute happens on the host and there is no CPU fallback: every entry point needs a HIP device.
 #include <algorithm>
 #include <atomic>
@@ -63,28 +64,6 @@ void log_begin_call() {
 
 
 
-struct Plan {
-  int ndim;
-  int64_t sx, sy, sz, voxels;
-  AxisGeom gy, gz;
-  // carved pointers
-  float *bufB = nullptr;
-  int32_t *stack = nullptr;
-  uint32_t *nz_y = nullptr, *rs_y = nullptr, *zs_y = nullptr, *nz_z = nullptr, *rs_z = nullptr;
-  unsigned char *line_ws = nullptr;  // scratch of the line pipeline when pass 1 runs over rows no row kernel takes (> 4096 voxels)
-  uint16_t *codes = nullptr;  // 16-bit distance indices of pass 1 (index form): one slab of xy_slab slices, or the whole volume
-  int64_t xy_slab = 0;        // slices per slab of the slab-wise X/Y passes (0: no index form for this shape)
-  bool codes_whole = false;   // the index buffer holds every slice (volumes of several slabs: round 6) -- the 16-bit plane between
-                              // passes Y and Z then exists there too
-  int64_t code_pitch = 0;     // elements between the slices of the index buffer: sx * sy, or padded (plane_pad_elems)
-  // the tiles the 16-bit integer column kernel hands to the fp32 kernel (edt_colq16.hip): kQ16Slots counters, one per
-  // column-pass launch of a call, and one array of tile ids
-  HandOver q16;
-  // which tiles of pass Y left their results in the 16-bit plane (= codes): one bit per (x-tile, z), behind the counters
-  uint32_t *q16_map = nullptr;
-  int q16_map_words = 0;  // words per x-tile
-  size_t bytes = 0;
-};
 
 AxisGeom make_geom_y(int64_t sx, int64_t sy, int64_t sz) {
   AxisGeom g;
@@ -99,10 +78,6 @@ AxisGeom make_geom_z(int64_t sx, int64_t sy, int64_t sz) {
   return g;
 }
 
-// What a call needs besides the bit planes: the second fp32 volume + hull stacks of the size-agnostic
-// column pass (only when an axis is too long for the in-place LDS kernels, or the caller forces the
-// generic kernels), and one slab of 16-bit distance indices for the index form of pass 1.
-static bool plan_needs_pingpong(int ndim, int64_t sx, int64_t sy, int64_t sz, int flags);
 
 // Index form of pass 1 (edt_rowwave.hip C16 -> edt_colwave_kernel.h XF): pass 1 hands the first column pass 2 bytes
 // per voxel instead of 4.  The indices live in the workspace, never more than kCodeSlabVoxels of them: passes X and
@@ -114,12 +89,9 @@ constexpr int64_t kCodeSlabVoxels = (int64_t)1 << 27;
 // 1024^3, against 288 GB of HBM): pass Y then leaves its results in the 16-bit plane there as well and pass Z reads 2 bytes per
 // voxel instead of 4 (round 4 measured it at cfg4 and did not keep it for the workspace; round 6 does).  Passes X and Y still run
 // slab by slab, so that a slab's indices are read back while they are warm.  EDT_HIP_WHOLE_INDEX_BYTES overrides the limit (0: off).
-static int64_t whole_index_limit() {
-  static const int64_t v = [] {
-    const char *e = std::getenv("EDT_HIP_WHOLE_INDEX_BYTES");
-    return e ? (int64_t)std::strtoll(e, nullptr, 0) : (int64_t)8 << 30;
-  }();
-  return v;
+static int64_t whole_index_limit() {  // (read per route, like the pad below: the route table of the CPU tier sets it per case)
+  const char *e = std::getenv("EDT_HIP_WHOLE_INDEX_BYTES");
+  return e ? (int64_t)std::strtoll(e, nullptr, 0) : (int64_t)8 << 30;
 }
 // The pitch of the index buffer = of the 16-bit plane between passes Y and Z (round 6).  Pass Z walks columns whose rows are one
 // slice apart: 2 * sx * sy bytes in the plane it reads, 4 * sx * sy in the caller's array it writes.  Where the plane's slice is a
@@ -141,86 +113,12 @@ static int64_t plane_pad_elems(int64_t sx, int64_t sy) {
   return 0;
 }
 constexpr int kQ16Slots = 256;  // counters of the 16-bit integer column kernel's hand-over lists (one per launch)
-constexpr int EDT_FLAG_NO_INDEX_FORM = 0x8000;  // internal: plan without the index buffer
-static int64_t plan_code_slab(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
-  if (ndim < 2 || sx % 4 != 0 || sx * sy > kCodeSlabVoxels || (flags & (EDT_FLAG_NO_INDEX_FORM | EDT_FLAG_SMALL_WORKSPACE))) return 0;
-  if ((flags & EDT_FLAG_FORCE_GENERIC) || env_force_generic() || (g_debug_mode & (kDbgFp32PassX | kDbgTiledColumns | kDbgTiledRows))) return 0;
-  if (!row_pass_wave_supported(dtype, sx, sy, sz) || !column_pass_wave_supported(make_geom_y(sx, sy, sz))) return 0;
-  int64_t slab = kCodeSlabVoxels / (sx * sy);
-  if (slab >= sz) return sz;
-  // (several slabs: whole words of the per-slice map of the 16-bit plane per slab)
-  if (slab >= 32) slab &= ~(int64_t)31;
-  return slab;
-}
-
-static Plan make_plan(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, void *ws, int flags) {
-  Plan p;
-  p.ndim = ndim; p.sx = sx; p.sy = sy; p.sz = sz; p.voxels = sx * sy * sz;
-  p.gy = make_geom_y(sx, sy, sz);
-  p.gz = make_geom_z(sx, sy, sz);
-  Carver c(ws);
-  if (ndim >= 2) {
-    if (plan_needs_pingpong(ndim, sx, sy, sz, flags)) {
-      p.bufB = c.take<float>((size_t)p.voxels);
-      p.stack = c.take<int32_t>((size_t)p.voxels);
-    }
-    const size_t wy = (size_t)(p.gy.sx * p.gy.nbands * p.gy.nouter);
-    p.nz_y = c.take<uint32_t>(wy);
-    p.rs_y = c.take<uint32_t>(wy);
-  }
-  if (ndim >= 3 && !(flags & EDT_FLAG_BATCH_2D)) {
-    // the z-packed planes are built AFTER the y pass: its run-start plane is dead by then and lends its
-    // storage to the z run starts (four planes in all: 1/8 byte per voxel each, 0.5 GiB for 1024^3)
-    const size_t wy = (size_t)(p.gy.sx * p.gy.nbands * p.gy.nouter);
-    const size_t wz = (size_t)(p.gz.sx * p.gz.nbands * p.gz.nouter);
-    p.nz_z = c.take<uint32_t>(wz);
-    if (wz <= wy) p.rs_z = p.rs_y;
-    else p.rs_z = c.take<uint32_t>(wz);
-    p.zs_y = c.take<uint32_t>(wy);
-  }
-  if (ndim >= 2) {
-    p.xy_slab = plan_code_slab(dtype, ndim, sx, sy, sz, flags);
-    p.codes_whole = p.xy_slab >= sz || (p.xy_slab > 0 && p.xy_slab % 32 == 0 && ndim == 3 && !(flags & EDT_FLAG_BATCH_2D) &&
-                                        sx * sy * sz * (int64_t)sizeof(uint16_t) <= whole_index_limit());
-    // (a padded pitch only where the plane exists -- a whole-volume buffer of a 3-D call; a single slice needs none)
-    p.code_pitch = sx * sy + ((p.codes_whole && ndim == 3 && sz > 1 && !(flags & EDT_FLAG_BATCH_2D)) ? plane_pad_elems(sx, sy) : 0);
-    if (p.xy_slab > 0) p.codes = c.take<uint16_t>((size_t)((p.codes_whole ? sz : p.xy_slab) * p.code_pitch));
-  }
-  if (ndim >= 2 && !(flags & EDT_FLAG_FORCE_GENERIC) && !env_force_generic()) {
-    // (ids in the fp32 kernel's geometry: 16-column tiles for axes of more than 512 rows)
-    // (pass Y runs over all sz slices at once whenever the index form is not taken at run time: sized for that)
-    p.q16_map_words = (int)ceil_div(sz, 32);
-    p.q16.slots = kQ16Slots;
-    // (one region, two rules: the counters are zeroed on the stream before the first launch that may hand a tile over,
-    // HandOver::zero; the map behind them never is -- every tile of a pass that writes the plane sets or clears its own bit)
-    p.q16.counts = c.take<uint32_t>(kQ16Slots + (size_t)(ceil_div(sx, 32) * p.q16_map_words));
-    p.q16_map = p.q16.counts ? p.q16.counts + kQ16Slots : nullptr;
-    p.q16.capacity = std::max(HandOver::ids_of(sx, sz), HandOver::ids_of(sx, sy));
-    p.q16.ids = c.take<uint32_t>((size_t)p.q16.capacity);
-  }
-  if (ndim == 1) (void)c.take<unsigned char>(line_workspace_bytes(sx));  // block scan + table of the 1-D pipeline
-  // rows too long for the row kernels (more than 4096 voxels; more than 2048 where the wave kernel does not apply): pass 1
-  // runs as the line pipeline over the stack of rows and needs its scratch
-  if (ndim >= 2 && !row_pass_tiled_supported(sx) && !row_pass_wave_supported(dtype, sx, sy, sz) &&
-      !(flags & EDT_FLAG_FORCE_GENERIC) && !env_force_generic())
-    p.line_ws = c.take<unsigned char>(rows_line_workspace_bytes(sx, sy * sz));
-  p.bytes = align_up(c.off, 256) + 256;
-  return p;
-}
 
 bool env_force_generic() {
   const char *e = std::getenv("EDT_HIP_FORCE_GENERIC");  // test hook: every call takes the fallback kernels
   return e && e[0] == '1';
 }
 
-static bool force_generic_1d(int flags) { return (flags & EDT_FLAG_FORCE_GENERIC) || env_force_generic(); }
-
-static bool plan_needs_pingpong(int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
-  if (ndim < 2) return false;
-  if ((flags & EDT_FLAG_FORCE_GENERIC) || env_force_generic()) return true;
-  if (!column_inplace_supported(make_geom_y(sx, sy, sz))) return true;
-  return ndim == 3 && !(flags & EDT_FLAG_BATCH_2D) && !column_inplace_supported(make_geom_z(sx, sy, sz));
-}
 
 int check_shape(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz) {
   if (dtype_size(dtype) == 0) { set_error("unknown dtype code"); return EDT_ERR_BAD_ARG; }
@@ -305,51 +203,254 @@ bool label_op_begin(const char *who, int own_rc, void *d_result, size_t result_w
   return true;
 }
 
-// ---- the pass pipeline on device-resident data -----------------------------------------
-int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
-                      float wx, float wy, float wz, int flags, float *d_out, void *d_ws,
-                      size_t ws_bytes, hipStream_t stream) {
+
+// ---- the route of a call -----------------------------------------------------------------
+// Everything a transform decides before its first launch: which kernels run and what lives in which region of the workspace.
+// route_of fills it from the call's inputs, the thread's debug mode and the environment hooks, and touches no device; the
+// workspace is carved from it (make_plan), run_device executes it, the size and support queries read it, and
+// edt_hip_transform_route shows the exported part (include/edt_hip.h documents its fields; DESIGN.md "The route of a call").
+struct Route {
+  edt_hip_route r = {};
+  bool empty = false;         // a volume without voxels: nothing to do
+  int dtype = 0, ndim = 0;
+  int64_t sx = 0, sy = 0, sz = 0;
+  bool zpass = false;         // a 3-D volume that is not a stack of 2-D images: pass Z exists
+  bool handover = false;      // the workspace holds the counters, map and id array of the integer column kernel
+  bool signed_ok = false;     // EDT_FLAG_SIGNED is served (edt_hip_signed_supported)
+  int bb = 0, last_epi = 0;   // the border rule; the epilogue of the call's last pass
+  bool last_sqrt = false;
+  Quantum Q;                  // the quantum of the voxel sizes, where a column pass may use it
+};
+
+// the carved pointers of a route
+struct Plan {
+  int64_t voxels;
+  AxisGeom gy, gz;
+  float *bufB = nullptr;
+  int32_t *stack = nullptr;
+  uint32_t *nz_y = nullptr, *rs_y = nullptr, *zs_y = nullptr, *nz_z = nullptr, *rs_z = nullptr;
+  unsigned char *line_ws = nullptr;  // scratch of the line pipeline when pass 1 runs over rows no row kernel takes (> 4096 voxels)
+  uint16_t *codes = nullptr;  // 16-bit distance indices of pass 1 (index form): one slab of route.slab slices, or the whole volume
+                              // (codes_whole: volumes of several slabs, round 6) -- the 16-bit plane between passes Y and Z then
+                              // exists there too
+  // the tiles the 16-bit integer column kernel hands to the fp32 kernel (edt_colq16.hip): kQ16Slots counters, one per
+  // column-pass launch of a call, and one array of tile ids
+  HandOver q16;
+  // which tiles of pass Y left their results in the 16-bit plane (= codes): one bit per (x-tile, z), behind the counters
+  uint32_t *q16_map = nullptr;
+  int q16_map_words = 0;  // words per x-tile
+  size_t bytes = 0;
+};
+
+// What a call needs besides the bit planes: the second fp32 volume + hull stacks of the size-agnostic column pass (only when an
+// axis is too long for the in-place LDS kernels, or the caller forces the generic kernels), and the 16-bit distance indices of
+// the index form of pass 1.
+static Plan make_plan(const Route &R, void *ws) {
+  const edt_hip_route &r = R.r;
+  const int64_t sx = R.sx, sy = R.sy, sz = R.sz;
+  Plan p;
+  p.voxels = sx * sy * sz;
+  p.gy = make_geom_y(sx, sy, sz);
+  p.gz = make_geom_z(sx, sy, sz);
+  const size_t wy = (size_t)(p.gy.sx * p.gy.nbands * p.gy.nouter), wz = (size_t)(p.gz.sx * p.gz.nbands * p.gz.nouter);
+  Carver c(ws);
+  if (r.second_volume) {
+    p.bufB = c.take<float>((size_t)p.voxels);
+    p.stack = c.take<int32_t>((size_t)p.voxels);
+  }
+  if (R.ndim >= 2) {
+    p.nz_y = c.take<uint32_t>(wy);
+    p.rs_y = c.take<uint32_t>(wy);
+  }
+  if (R.zpass) {
+    // the z-packed planes are built AFTER the y pass: its run-start plane is dead by then and lends its
+    // storage to the z run starts (four planes in all: 1/8 byte per voxel each, 0.5 GiB for 1024^3)
+    p.nz_z = c.take<uint32_t>(wz);
+    if (wz <= wy) p.rs_z = p.rs_y;
+    else p.rs_z = c.take<uint32_t>(wz);
+    p.zs_y = c.take<uint32_t>(wy);
+  }
+  if (r.slab > 0) p.codes = c.take<uint16_t>((size_t)((r.codes_whole ? sz : r.slab) * r.code_pitch));
+  if (R.handover) {
+    // (ids in the fp32 kernel's geometry: 16-column tiles for axes of more than 512 rows)
+    // (pass Y runs over all sz slices at once whenever the index form is not taken: sized for that)
+    p.q16_map_words = (int)ceil_div(sz, 32);
+    p.q16.slots = kQ16Slots;
+    // (one region, two rules: the counters are zeroed on the stream before the first launch that may hand a tile over,
+    // HandOver::zero; the map behind them never is -- every tile of a pass that writes the plane sets or clears its own bit)
+    p.q16.counts = c.take<uint32_t>(kQ16Slots + (size_t)(ceil_div(sx, 32) * p.q16_map_words));
+    p.q16_map = p.q16.counts ? p.q16.counts + kQ16Slots : nullptr;
+    p.q16.capacity = std::max(HandOver::ids_of(sx, sz), HandOver::ids_of(sx, sy));
+    p.q16.ids = c.take<uint32_t>((size_t)p.q16.capacity);
+  }
+  if (R.ndim == 1) (void)c.take<unsigned char>(line_workspace_bytes(sx));  // block scan + table of the 1-D pipeline
+  // rows too long for the row kernels (more than 4096 voxels; more than 2048 where the wave kernel does not apply): pass 1
+  // runs as the line pipeline over the stack of rows and needs its scratch
+  if (R.ndim >= 2 && r.x_kernel == EDT_ROUTE_X_LINE) p.line_ws = c.take<unsigned char>(rows_line_workspace_bytes(sx, sy * sz));
+  p.bytes = align_up(c.off, 256) + 256;
+  return p;
+}
+
+// The one place that decides.  Returns what the call refuses with before its first launch, in the order the refusals always
+// had: shape, voxel sizes (their signs dropped: wy, wz), [an empty volume: EDT_OK], the data pointers (null_data), the workspace,
+// EDT_FLAG_SIGNED, EDT_FLAG_BATCH_2D.  ws_bytes: the workspace the caller brought (0: none).  out_misalignment: d_out's address
+// modulo 16 -- all column_pass_q16_aligned needs: the workspace is 256-aligned (check_workspace_alignment; internal callers
+// hand in carved regions) and every region of the carve is, and where the index form exists sx % 4 == 0, so a slab's part of
+// the field (z0 * sx * sy floats: a multiple of 16 bytes) and of the index buffer (z0 * code_pitch indices: sx * sy and the pad
+// are multiples of 4 elements, 8 bytes) keeps the alignment of its base.  What is filled when a refusal comes stays filled:
+// the size and support queries read it.
+static int route_of(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float &wx, float &wy, float &wz, int flags,
+                    bool null_data, size_t ws_bytes, uint32_t out_misalignment, Route &R) {
+  R = Route();
   int rc = check_shape(dtype, ndim, sx, sy, sz);
   if (rc != EDT_OK) return rc;
   if ((rc = check_voxel_sizes(ndim, wx, wy, wz)) != EDT_OK) return rc;
-  if (sx == 0 || sy == 0 || sz == 0) return EDT_OK;
-  if (!d_labels || !d_out) { set_error("null device pointer"); return EDT_ERR_BAD_ARG; }
-  Plan p = make_plan(dtype, ndim, sx, sy, sz, d_ws, flags);
+  if (sx == 0 || sy == 0 || sz == 0) { R.empty = true; return EDT_OK; }
+  if (null_data) { set_error("null device pointer"); return EDT_ERR_BAD_ARG; }
+  edt_hip_route &r = R.r;
+  R.dtype = dtype; R.ndim = ndim; R.sx = sx; R.sy = sy; R.sz = sz;
+  const int mode = g_debug_mode;
+  const bool generic = (flags & EDT_FLAG_FORCE_GENERIC) != 0 || env_force_generic();
+  // a stack of 2-D images is a volume without a z pass
+  R.zpass = ndim == 3 && !(flags & EDT_FLAG_BATCH_2D);
+  R.bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
+  R.last_sqrt = (flags & EDT_FLAG_SQRT) != 0;
+  R.last_epi = last_pass_epi(R.bb, R.last_sqrt ? 1 : 0);
+  const AxisGeom gy = make_geom_y(sx, sy, sz), gz = make_geom_z(sx, sy, sz);
+
+  // The kernels the shape allows.  Pass 1 on the row kernels: the register kernel up to 4096 voxels per row, the
+  // workgroup-phased one up to 2048 (debug bit 32: never the former); longer rows: the line pipeline; forced generic: a thread
+  // per row.  Column passes are in place when an LDS-tiled kernel applies, otherwise they ping-pong between two volumes.
+  const bool row_kernels = ndim >= 2 && row_pass_on_row_kernels(dtype, sx, sy, sz, generic);
+  const bool register_x = row_kernels && row_pass_wave_supported(dtype, sx, sy, sz) && !(mode & kDbgTiledRows);
+  const bool tiled_y = ndim >= 2 && !generic && column_inplace_supported(gy);
+  const bool tiled_z = R.zpass && !generic && column_inplace_supported(gz);
+  r.x_kernel = register_x ? EDT_ROUTE_X_REGISTER : row_kernels ? EDT_ROUTE_X_PHASED : generic ? EDT_ROUTE_X_SERIAL : EDT_ROUTE_X_LINE;
+  r.planes_from_labels = ndim >= 2 && !row_kernels;
+  r.second_volume = ndim >= 2 && (!tiled_y || (R.zpass && !tiled_z));
+  R.handover = ndim >= 2 && !generic;
+  // The one-transform form of sdf / sdfsq needs pass X on the register kernel (the only pass-X kernel that takes zero_label)
+  // and in-place column passes (their kernels never look at label values: run-start bits and field values only).
+  R.signed_ok = register_x && tiled_y && (!R.zpass || tiled_z) && !(flags & EDT_FLAG_BINARY_YZ);
+
+  // The index buffer (see kCodeSlabVoxels): the register kernel of pass X and the wave column kernel, rows of whole 8-byte
+  // granules.  Several slabs: whole words of the per-slice map of the 16-bit plane per slab.  A padded pitch only where the
+  // plane exists -- a whole-volume buffer of a 3-D call; a single slice needs none.
+  const auto index_buffer = [&](bool wanted) {
+    r.slab = 0;
+    if (wanted && register_x && sx % 4 == 0 && sx * sy <= kCodeSlabVoxels && column_pass_wave_supported(gy) &&
+        !(mode & (kDbgFp32PassX | kDbgTiledColumns))) {
+      r.slab = std::min(kCodeSlabVoxels / (sx * sy), sz);
+      if (r.slab < sz && r.slab >= 32) r.slab &= ~(int64_t)31;
+    }
+    r.codes_whole = r.slab >= sz || (r.slab > 0 && r.slab % 32 == 0 && R.zpass && sx * sy * sz * (int64_t)sizeof(uint16_t) <= whole_index_limit());
+    r.code_pitch = ndim >= 2 ? sx * sy + ((r.codes_whole && R.zpass && sz > 1) ? plane_pad_elems(sx, sy) : 0) : 0;
+    r.workspace_bytes = make_plan(R, nullptr).bytes;
+  };
+  index_buffer(!(flags & EDT_FLAG_SMALL_WORKSPACE));
   // (a workspace sized while the index form of pass 1 was switched off still serves: fp32 form)
-  if (d_ws && ws_bytes < p.bytes && p.codes != nullptr) p = make_plan(dtype, ndim, sx, sy, sz, d_ws, flags | EDT_FLAG_NO_INDEX_FORM);
+  if (ws_bytes != 0 && ws_bytes < r.workspace_bytes && r.slab > 0) {
+    index_buffer(false);
+    r.index_fallback = 1;
+  }
   // (1-D: the parallel line pipeline needs its block-scan scratch; a call without any -- the ABI of round 1 -- is
   // served by the thread-per-row kernel instead of being refused)
-  const bool line_without_ws = ndim == 1 && (!d_ws || ws_bytes < p.bytes);
-  if (!line_without_ws && (!d_ws || ws_bytes < p.bytes)) {
-    set_error("workspace too small: need " + std::to_string(p.bytes) +
+  if (ws_bytes < r.workspace_bytes && ndim != 1) {
+    set_error("workspace too small: need " + std::to_string(r.workspace_bytes) +
               " bytes (edt_hip_workspace_bytes_flags with the flags of this call)");
     return EDT_ERR_BAD_ARG;
   }
-  const int bb = (flags & EDT_FLAG_BLACK_BORDER) ? 1 : 0;
-  const int want_sqrt = (flags & EDT_FLAG_SQRT) ? 1 : 0;
   // The SIGNED transform (EDT_FLAG_SIGNED; sdf / sdfsq of src/edt.pyx:121-202 = edt(x) - edt(x == 0)) as ONE transform: the
   // two fields have disjoint supports, and a voxel's value depends on nothing but the voxels of its own label runs -- so
   // measuring label 0 like every other label gives edt(x) on the foreground and edt(x == 0) on the background at once, bit
   // for bit; the background's sign follows in one streaming kernel.  Pass X's register kernel takes the flag (zero_label).
-  const int signed_tf = (flags & EDT_FLAG_SIGNED) ? 1 : 0;
-  if (signed_tf && !signed_transform_supported(dtype, ndim, sx, sy, sz, flags)) {
+  const bool signed_tf = (flags & EDT_FLAG_SIGNED) != 0;
+  if (signed_tf && !R.signed_ok) {
     set_error("EDT_FLAG_SIGNED: shape not served by the one-transform form (edt_hip_signed_supported)");
     return EDT_ERR_UNSUPPORTED;
   }
-  const int last_epi = last_pass_epi(bb, want_sqrt);
-  // a stack of 2-D images is a volume without a z pass
   if ((flags & EDT_FLAG_BATCH_2D) && ndim != 3) { set_error("EDT_FLAG_BATCH_2D needs ndim = 3 (sz = image count)"); return EDT_ERR_BAD_ARG; }
-  const bool zpass = ndim == 3 && !(flags & EDT_FLAG_BATCH_2D);
+  r.slabs = 1;
+  if (ndim == 1) {  // (pass X is the call's last pass; one thread for the whole line only where forced, or without scratch)
+    if (ws_bytes < r.workspace_bytes) r.x_kernel = EDT_ROUTE_X_SERIAL;
+    return EDT_OK;
+  }
   // the reference's binary route for multi-valued labels: labels split runs in pass 1 only (edt_generic.hip:
   // k_planes_one_run).  Boolean input gives the same values either way and keeps the ordinary planes.
-  const bool binary_yz = (flags & EDT_FLAG_BINARY_YZ) != 0 && dtype != EDT_BOOL;
+  r.binary_yz = (flags & EDT_FLAG_BINARY_YZ) != 0 && dtype != EDT_BOOL;
+  // Start in the buffer that makes the last pass land in d_out.
+  r.first_buffer = ((tiled_y ? 0 : 1) + ((R.zpass && !tiled_z) ? 1 : 0)) % 2;
+  // Index form of pass 1: pass 1 stores 16-bit distance indices, the first column pass turns them into F while it fills its
+  // tile -- 2 B less written and 2 B less read per voxel.  Bit-identical only where every multiple k * wx of the row is exact
+  // in fp32 (row_codes_exact); other voxel sizes keep the fp32 form.
+  r.index_form = r.slab > 0 && row_codes_exact(wx, sx);
+  if (r.index_form) r.slabs = ceil_div(sz, r.slab);
+
+  // The 16-bit integer form of the column passes (edt_colq16.hip): voxel sizes that share a quantum.  Every column pass is
+  // then two launches: the integer kernel over all tiles, and the fp32 kernel over the list of tiles it refused -- unless the
+  // host proves that list empty (q16_no_refusals): in the index form for pass Y, behind such a pass Y for pass Z.  The field a
+  // pass works on: pass Y on the first buffer, an in-place pass Z on d_out.  Its counter: one per launch, pass Y's slabs first.
+  if (R.handover) {
+    const float w3[3] = {wx, wy, wz};
+    R.Q = q16_quantum(w3, R.zpass ? 3 : 2);
+  }
+  static uint32_t planned;  // (the counters of the plan: column_pass_q16_applies asks whether they exist)
+  HandOver h;
+  h.counts = &planned;
+  h.slots = kQ16Slots;
+  h.slot = (int)std::min<int64_t>(r.slabs - 1, kQ16Slots);
+  const bool out_aligned = out_misalignment % 16 == 0;
+  const bool y_integer = tiled_y && (r.first_buffer == 1 || out_aligned) && column_pass_q16_applies(R.Q, gy, h);
+  r.y_pass = !tiled_y ? EDT_ROUTE_COL_SERIAL : !y_integer ? EDT_ROUTE_COL_FP32
+             : (r.index_form && q16_no_refusals(R.Q, 1, sx, sy, sy, R.bb)) ? EDT_ROUTE_COL_INTEGER_ALONE : EDT_ROUTE_COL_INTEGER_LIST;
+  h.slot = y_integer ? (int)r.slabs : 0;
+  const bool z_integer = tiled_z && out_aligned && column_pass_q16_applies(R.Q, gz, h);
+  r.z_pass = !R.zpass ? EDT_ROUTE_COL_NONE : !tiled_z ? EDT_ROUTE_COL_SERIAL : !z_integer ? EDT_ROUTE_COL_FP32
+             : (r.y_pass == EDT_ROUTE_COL_INTEGER_ALONE && q16_no_refusals(R.Q, 2, sx, sy, sz, R.bb)) ? EDT_ROUTE_COL_INTEGER_ALONE
+                                                                                                     : EDT_ROUTE_COL_INTEGER_LIST;
+  const bool integer_only = r.y_pass == EDT_ROUTE_COL_INTEGER_ALONE && r.z_pass == EDT_ROUTE_COL_INTEGER_ALONE;
+  const bool keep_planes = (mode & kDbgKeepPlanes) != 0;
+  // The 16-bit plane between passes Y and Z: where both run on the integer kernel and the indices of pass X cover the whole
+  // volume, the tiles of pass Y that qualify write their results over their indices -- 2 bytes per voxel out of pass Y and
+  // into pass Z instead of 4 -- and pass Z reads every row from wherever pass Y left it.  (debug bit 0x10000000: fp32 between
+  // the passes.)  plane_inf_ok: may a tile of nothing but +inf stay there for pass Z?
+  r.plane16 = r.index_form && r.codes_whole && y_integer && z_integer && !(mode & kDbgFp32Plane);
+  r.plane_inf_ok = r.plane16 && q16_value_limit(R.Q.q, R.Q.a[2], sz, R.bb) != 0u;
+  // The signed transform's sign as the EPILOGUE of pass Z (round 6): where both column passes provably run on the integer kernel
+  // alone -- it never reads the foreground plane -- pass X keeps the TRUE label != 0 bits there (zero_label = 2), the transposer
+  // carries them to the z axis, and the last pass negates the voxels whose bit is clear (kEpiSign): no pass of its own over
+  // labels and field (1.2 GB at 512^3).  Anywhere else: all-ones planes and k_negate_background.  (debug bit 0x400: never.)
+  r.sign = !signed_tf ? 0 : (integer_only && !keep_planes) ? 1 : 2;
+  r.zero_label = !signed_tf ? 0 : r.sign == 1 ? 2 : 1;
+  // ... and then nobody reads a foreground plane (the integer kernel knows background as N = 0): pass X does not write one, the
+  // transposer carries the run starts alone -- 48 MiB less per 512^3 step (debug bit 0x400 keeps the planes)
+  r.skip_nz = integer_only && !signed_tf && !r.binary_yz && !keep_planes;
+  // ... and then the storage of the y foreground plane is nobody's: it takes the ROW FLAGS.  Pass X does not store the indices of
+  // a row without a run start -- its indices follow from x alone -- and says so in two words per (z, band of 32 rows), [z][band]
+  // [plain, plain_fg], the first 2 * bands * sz words of nz_y (which has sx words per (z, band): sx >= 4 here); pass Y puts the
+  // indices back while it fills its tile (edt_colq16.hip: q16_plain_quad).  Written by pass X, both words of every group, so the
+  // region needs no clearing.  Only where nothing else reads the indices: the integer kernel alone (the fp32 kernel reads them
+  // too and knows nothing of the flags), unsigned and not binary_yz (skip_nz), one slab of indices, rows of one wave
+  // (sx <= 1024).  Everything else hands both kernels nullptr and stores every row.  (debug bit 0x800000: every row is stored.)
+  r.row_flags = r.skip_nz && r.slabs == 1 && sx <= 1024 && !(mode & kDbgStoreEveryRow);
+  return EDT_OK;
+}
+
+// ---- the pass pipeline on device-resident data: the launches the route names, in order -----------------------------------
+int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                      float wx, float wy, float wz, int flags, float *d_out, void *d_ws,
+                      size_t ws_bytes, hipStream_t stream) {
+  Route R;
+  int rc = route_of(dtype, ndim, sx, sy, sz, wx, wy, wz, flags, !d_labels || !d_out, d_ws ? ws_bytes : 0,
+                    (uint32_t)(reinterpret_cast<uintptr_t>(d_out) % 16), R);
+  if (rc != EDT_OK || R.empty) return rc;
+  const edt_hip_route &r = R.r;
+  Plan p = make_plan(R, d_ws);
   // lower bounds of the non-zero values passes Y and Z read (AxisGeom::fmin): pass X leaves fl32(T[k]^2) >= fl32(wx^2),
   // pass Y's results are at least the smaller of that and fl32(wy^2) (every candidate is its row's own value or carries
   // a c_d >= w2y; the border terms are >= w2y).  Not for the fused sqrt of a 2-D call (pass Z does not exist then).
-  const float fmin_y = edt_hip_field_floor(wx, wx);
-  const float fmin_z = edt_hip_field_floor(wx, wy);
-  p.gy.fmin = fmin_y;
-  p.gz.fmin = fmin_z;
+  p.gy.fmin = edt_hip_field_floor(wx, wx);
+  p.gz.fmin = edt_hip_field_floor(wx, wy);
 
   // the pass log is process-wide and only touched (under its mutex) while profiling is switched on
   if (g_log.enabled.load(std::memory_order_relaxed)) {
@@ -357,173 +458,125 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
     log_begin_call();
   }
 
-  // The 16-bit integer form of the column passes (edt_colq16.hip): voxel sizes that share a quantum.  Every column pass
-  // is then two launches: the integer kernel over all tiles, and the fp32 kernel over the list of tiles it refused
-  // (run_column_pass, edt_colpass.hip).
-  Quantum Q;
-  if (ndim >= 2 && p.q16.counts != nullptr) {
-    const float ws3[3] = {wx, wy, wz};
-    Q = q16_quantum(ws3, zpass ? 3 : 2);
-  }
-  // a column pass of this call over the field at F, in place
-  auto column = [&](float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w, int epi) {
-    ColumnPass cp = column_pass(F, nz, rs, g, w, bb, epi, stream);
+  // a column pass of this call over the field at F, in place: run_column_pass (edt_colpass.hip) is handed what the route
+  // decided -- the quantum only where the integer kernel is to run, `sure` only where it is to run alone -- and a pass that
+  // did anything else is an internal error
+  const auto column = [&](float *F, const uint32_t *nz, const uint32_t *rs, const AxisGeom &g, float w, int epi) {
+    ColumnPass cp = column_pass(F, nz, rs, g, w, R.bb, epi, stream);
     cp.map = p.q16_map;
     cp.map_words = p.q16_map_words;
     return cp;
   };
+  const auto run_column = [&](const ColumnPass &cp, int axis, int kind, Fp32Leg leg) -> int {
+    TileList served;
+    const int rc = run_column_pass(cp, kind >= EDT_ROUTE_COL_INTEGER_LIST ? R.Q : Quantum(), axis, p.q16, leg,
+                                   kind == EDT_ROUTE_COL_INTEGER_ALONE, &served);
+    if (rc != EDT_OK) return rc;
+    if ((served.count != nullptr) == (kind >= EDT_ROUTE_COL_INTEGER_LIST) && served.none == (kind == EDT_ROUTE_COL_INTEGER_ALONE)) return EDT_OK;
+    set_error(axis == 1 ? "internal: pass Y left its route" : "internal: pass Z left its route");
+    return EDT_ERR_HIP;
+  };
 
   // pass X of this call: the whole volume into the field at `out` (the index form below works slab by slab)
-  RowPass rp = row_pass(dtype, d_labels, sx, sy, sz, wx, bb, stream);
+  RowPass rp = row_pass(dtype, d_labels, sx, sy, sz, wx, R.bb, stream);
 
-  if (ndim == 1) {  // (pass X is the call's last pass; one thread for the whole line only where forced, or without scratch)
-    rp.out = d_out; rp.last = true; rp.last_sqrt = want_sqrt != 0;
-    return run_row_pass(rp, false, (force_generic_1d(flags) || line_without_ws) ? nullptr : d_ws, true);
+  if (r.y_pass == EDT_ROUTE_COL_NONE) {  // (a line: pass X is the call's last pass)
+    rp.out = d_out; rp.last = true; rp.last_sqrt = R.last_sqrt;
+    return run_row_pass(rp, false, r.x_kernel == EDT_ROUTE_X_LINE ? d_ws : nullptr, true);
   }
 
-  // Column passes are in place when the LDS-tiled kernel applies, otherwise they ping-pong
-  // between two volumes.  Start in the buffer that makes the last pass land in d_out.
-  const bool force_generic = (flags & EDT_FLAG_FORCE_GENERIC) != 0 || env_force_generic();
-  const bool tiled_y = !force_generic && column_inplace_supported(p.gy);
-  const bool tiled_z = !force_generic && column_inplace_supported(p.gz);
-  const int swaps = (tiled_y ? 0 : 1) + ((zpass && !tiled_z) ? 1 : 0);
-  float *cur = (swaps % 2 == 0) ? d_out : p.bufB;
-  float *other = (cur == d_out) ? p.bufB : d_out;
-  // (pass 1 on the row kernels: the wave kernel up to 4096 voxels per row, the workgroup-phased one up to 2048)
-  const bool tiled_x = row_pass_on_row_kernels(dtype, sx, sy, sz, force_generic);
-  // Index form of pass 1 (see plan_code_slab): pass 1 stores 16-bit distance indices, the first column pass turns
-  // them into F while it fills its tile -- 2 B less written and 2 B less read per voxel.  Bit-identical only where
-  // every multiple k * wx of the row is exact in fp32 (row_codes_exact); other voxel sizes keep the fp32 form.
-  const bool index_form = p.codes != nullptr && tiled_x && tiled_y && row_codes_exact(wx, sx);
-  // The 16-bit plane between passes Y and Z: where both run on the integer kernel and the indices of pass X cover the whole
-  // volume (one slab), the tiles of pass Y that qualify write their results over their indices -- 2 bytes per voxel out
-  // of pass Y and into pass Z instead of 4 -- and pass Z reads every row from wherever pass Y left it.  (debug bit
-  // 0x10000000: fp32 between the passes.)
-  bool plane16 = index_form && zpass && p.codes_whole && !(g_debug_mode & kDbgFp32Plane) &&
-                 column_pass_q16_applies(Q, p.gy, p.q16) && column_pass_q16_applies(Q, p.gz, p.q16);
-  bool y_sure = true;  // every tile of pass Y was served by the integer kernel, provably (q16_no_refusals)
-  // The signed transform's sign as the EPILOGUE of pass Z (round 6): where both column passes provably run on the integer kernel
-  // alone -- it never reads the foreground plane -- pass X keeps the TRUE label != 0 bits there (zero_label = 2), the transposer
-  // carries them to the z axis, and the last pass negates the voxels whose bit is clear (kEpiSign): no pass of its own over
-  // labels and field (1.2 GB at 512^3).  Anywhere else: all-ones planes and k_negate_background.  (debug bit 0x400: never.)
-  // q16_only: both column passes of the call provably run on the integer kernel alone (what run_column_pass will decide, decided
-  // here for the whole call; a pass that left that kernel after all is an internal error below)
-  const bool q16_only = zpass && index_form && tiled_z && column_pass_q16_applies(Q, p.gy, p.q16) && column_pass_q16_applies(Q, p.gz, p.q16) &&
-                        q16_no_refusals(Q, 1, sx, sy, sy, bb) && q16_no_refusals(Q, 2, sx, sy, sz, bb) &&
-                        column_pass_q16_aligned(cur, p.codes, p.codes) && ceil_div(sz, p.xy_slab > 0 ? p.xy_slab : sz) + 1 <= kQ16Slots;
-  const bool fuse_sign = signed_tf && q16_only && !(g_debug_mode & kDbgKeepPlanes);
-  const int zero_label = fuse_sign ? 2 : signed_tf;
-  // ... and then nobody reads a foreground plane (the integer kernel knows background as N = 0): pass X does not write one, the
-  // transposer carries the run starts alone -- 48 MiB less per 512^3 step (debug bit 0x400 keeps the planes)
-  const bool skip_nz = q16_only && !signed_tf && !binary_yz && !(g_debug_mode & kDbgKeepPlanes);
-  uint32_t *const nzy = skip_nz ? nullptr : p.nz_y, *const nzz = skip_nz ? nullptr : p.nz_z;
-  // ... and then the storage of the y foreground plane is nobody's: it takes the ROW FLAGS.  Pass X does not store the indices of
-  // a row without a run start -- its indices follow from x alone -- and says so in two words per (z, band of 32 rows), [z][band]
-  // [plain, plain_fg], the first 2 * bands * sz words of nz_y (which has sx words per (z, band): sx >= 4 here); pass Y puts the
-  // indices back while it fills its tile (edt_colq16.hip: q16_plain_quad).  Written by pass X, both words of every group, so the
-  // region needs no clearing.  Only where nothing else reads the indices: the integer kernel alone (q16_only: the fp32 kernel
-  // reads them too and knows nothing of the flags), unsigned and not binary_yz (skip_nz), one slab of indices, rows of one wave
-  // (sx <= 1024).  Everything else hands both kernels nullptr and stores every row.  (debug bit 0x800000: every row is stored.)
-  uint32_t *const rowflags = (skip_nz && p.xy_slab >= sz && sx <= 1024 && !(g_debug_mode & kDbgStoreEveryRow)) ? p.nz_y : nullptr;
-  if (index_form) {
+  float *cur = r.first_buffer ? p.bufB : d_out;
+  float *other = r.first_buffer ? d_out : p.bufB;
+  const bool row_kernels = !r.planes_from_labels;
+  const int y_epi = R.zpass ? 0 : R.last_epi;
+  uint32_t *const nzy = r.skip_nz ? nullptr : p.nz_y, *const nzz = r.skip_nz ? nullptr : p.nz_z;
+  uint32_t *const rowflags = r.row_flags ? p.nz_y : nullptr;
+  if (r.index_form) {
     const int64_t sxy = sx * sy, wpl = p.gy.sx * p.gy.nbands;  // voxels / bit words per slice
     const size_t lsz = dtype_size(dtype);
-    const bool one = p.xy_slab >= sz;
+    const bool one = r.slabs == 1;
     ScopedPass whole(one ? nullptr : "xy_pass", stream);
-    for (int64_t z0 = 0; z0 < sz; z0 += p.xy_slab) {
-      const int64_t zc = std::min<int64_t>(p.xy_slab, sz - z0);
+    for (int64_t z0 = 0; z0 < sz; z0 += r.slab) {
+      const int64_t zc = std::min<int64_t>(r.slab, sz - z0);
       const char *lab = static_cast<const char *>(d_labels) + (size_t)(z0 * sxy) * lsz;
       // (one slab of indices taken in turn, or -- codes_whole -- every slab's own part of a whole-volume buffer: the 16-bit plane)
-      uint16_t *slab_codes = p.codes + ((p.codes_whole && !one) ? z0 * p.code_pitch : 0);
+      uint16_t *slab_codes = p.codes + ((r.codes_whole && !one) ? z0 * r.code_pitch : 0);
       {
         // (slice 0 of a later slab compares against the slice below it through the halo pointer of the sharded path)
         ScopedPass t(one ? "x_pass" : nullptr, stream);
         RowPass slab = rp;
         slab.labels = lab; slab.halo = z0 > 0 ? lab - (size_t)sxy * lsz : nullptr; slab.sz = zc;
-        slab.nz_y = nzy ? nzy + z0 * wpl : nullptr; slab.ys_y = p.rs_y + z0 * wpl; slab.zs_y = zpass ? p.zs_y + z0 * wpl : nullptr;
-        slab.codes = slab_codes; slab.codes_pitch = p.code_pitch; slab.zero_label = zero_label;
+        slab.nz_y = nzy ? nzy + z0 * wpl : nullptr; slab.ys_y = p.rs_y + z0 * wpl; slab.zs_y = R.zpass ? p.zs_y + z0 * wpl : nullptr;
+        slab.codes = slab_codes; slab.codes_pitch = r.code_pitch; slab.zero_label = r.zero_label;
         slab.rowflags = rowflags;
         if ((rc = launch_row_pass_wave(slab)) != EDT_OK) return rc;
-        if (binary_yz) {
+        if (r.binary_yz) {
           AxisGeom gb = p.gy;
           gb.nouter = zc;
-          rc = launch_planes_one_run(p.nz_y + z0 * wpl, p.rs_y + z0 * wpl, zpass ? p.zs_y + z0 * wpl : nullptr, gb, z0, stream);
+          rc = launch_planes_one_run(p.nz_y + z0 * wpl, p.rs_y + z0 * wpl, R.zpass ? p.zs_y + z0 * wpl : nullptr, gb, z0, stream);
           if (rc != EDT_OK) return rc;
         }
       }
       {
         ScopedPass t(one ? "y_pass" : nullptr, stream);
-        ColumnPass cp = column(cur + z0 * sxy, p.nz_y + z0 * wpl, p.rs_y + z0 * wpl, p.gy, wy, zpass ? 0 : last_epi);
+        ColumnPass cp = column(cur + z0 * sxy, p.nz_y + z0 * wpl, p.rs_y + z0 * wpl, p.gy, wy, y_epi);
         cp.g.nouter = zc;
         cp.codes = slab_codes;
-        cp.codes_outer = p.code_pitch;  // (the index buffer's own pitch: the outer stride of codes -- and of the plane written over them)
+        cp.codes_outer = r.code_pitch;  // (the index buffer's own pitch: the outer stride of codes -- and of the plane written over them)
         cp.wx = wx;
         cp.rowflags = rowflags;
-        cp.plane = plane16 ? slab_codes : nullptr;
+        cp.plane = r.plane16 ? slab_codes : nullptr;
         // (the slab's first word in every x-tile's row of the plane's map: pass Y of the slabs after the first)
-        if (p.codes_whole && !one) cp.map += z0 / 32;
-        // (pass Y into the plane: may a tile of nothing but +inf stay there for pass Z?)
-        cp.plane_inf_ok = (plane16 && q16_value_limit(Q.q, Q.a[2], sz, bb) != 0u) ? 1 : 0;
-        TileList served;
-        rc = run_column_pass(cp, Q, 1, p.q16, Fp32Leg::wave, true, &served);
-        if (rc != EDT_OK) return rc;
-        if (served.count == nullptr) plane16 = false;  // (nothing wrote the plane or said where the rows are: pass Z reads fp32 values)
-        y_sure = y_sure && served.none;
-        if (q16_only && !served.none) { set_error("internal: pass Y left the integer kernel"); return EDT_ERR_HIP; }
+        if (r.codes_whole && !one) cp.map += z0 / 32;
+        cp.plane_inf_ok = r.plane_inf_ok;
+        if ((rc = run_column(cp, 1, r.y_pass, Fp32Leg::wave)) != EDT_OK) return rc;
       }
     }
   } else {
-    // (the signed form -- signed_transform_supported: the register kernel of pass X serves this shape -- measures label 0 too)
-    rp.out = cur; rp.nz_y = p.nz_y; rp.ys_y = p.rs_y; rp.zs_y = (zpass && tiled_x) ? p.zs_y : nullptr; rp.zero_label = signed_tf;
-    if ((rc = run_row_pass(rp, tiled_x, p.line_ws, true)) != EDT_OK) return rc;
-    if (binary_yz) rc = launch_planes_one_run(p.nz_y, p.rs_y, rp.zs_y, p.gy, 0, stream);
+    // (the signed form -- the register kernel of pass X serves this shape -- measures label 0 too)
+    rp.out = cur; rp.nz_y = p.nz_y; rp.ys_y = p.rs_y; rp.zs_y = (R.zpass && row_kernels) ? p.zs_y : nullptr; rp.zero_label = r.zero_label;
+    if ((rc = run_row_pass(rp, row_kernels, p.line_ws, true)) != EDT_OK) return rc;
+    if (r.binary_yz) rc = launch_planes_one_run(p.nz_y, p.rs_y, rp.zs_y, p.gy, 0, stream);
     if (rc != EDT_OK) return rc;
-  }
-  if (!index_form) {
     ScopedPass t("y_pass", stream);
-    const int epi = zpass ? 0 : last_epi;
-    if (tiled_y) {
-      // (fp32 values of pass X: (k * wx)^2 need not be on the quantum grid for large k -- the list stays)
-      rc = run_column_pass(column(cur, p.nz_y, p.rs_y, p.gy, wy, epi), Q, 1, p.q16, Fp32Leg::inplace);
-      y_sure = false;
-    } else {
-      rc = launch_column_pass_serial(cur, other, p.nz_y, p.rs_y, p.stack, p.gy, wy, bb, epi, stream);
+    if (r.y_pass == EDT_ROUTE_COL_SERIAL) {
+      rc = launch_column_pass_serial(cur, other, p.nz_y, p.rs_y, p.stack, p.gy, wy, R.bb, y_epi, stream);
       std::swap(cur, other);
+    } else {
+      // (fp32 values of pass X: (k * wx)^2 need not be on the quantum grid for large k -- the list stays)
+      rc = run_column(column(cur, p.nz_y, p.rs_y, p.gy, wy, y_epi), 1, r.y_pass, Fp32Leg::inplace);
     }
     if (rc != EDT_OK) return rc;
   }
-  if (zpass) {
+  if (R.zpass) {
     // z-packed planes (after the y pass: rs_z may live in the y pass's run-start plane)
     ScopedPass t("z_bits", stream);
-    if (tiled_x) rc = launch_bits_transpose_yz(nzy, p.zs_y, nzz, p.rs_z, sx, sy, sz, stream);
+    if (row_kernels) rc = launch_bits_transpose_yz(nzy, p.zs_y, nzz, p.rs_z, sx, sy, sz, stream);
     else {
       rc = launch_axis_bits(dtype, d_labels, nullptr, p.nz_z, p.rs_z, p.gz, stream);
-      if (rc == EDT_OK && binary_yz) rc = launch_planes_one_run(p.nz_z, p.rs_z, nullptr, p.gz, 0, stream);
+      if (rc == EDT_OK && r.binary_yz) rc = launch_planes_one_run(p.nz_z, p.rs_z, nullptr, p.gz, 0, stream);
     }
     if (rc != EDT_OK) return rc;
   }
-  if (zpass) {
+  if (R.zpass) {
     ScopedPass t("z_pass", stream);
-    if (tiled_z) {
-      ColumnPass cp = column(cur, p.nz_z, p.rs_z, p.gz, wz, last_epi | (fuse_sign ? kEpiSign : 0));
-      if (plane16) {  // (the index buffer's own pitch: the row stride of the plane pass Z reads)
+    if (r.z_pass == EDT_ROUTE_COL_SERIAL) {
+      rc = launch_column_pass_serial(cur, other, p.nz_z, p.rs_z, p.stack, p.gz, wz, R.bb, R.last_epi, stream);
+      std::swap(cur, other);
+    } else {
+      ColumnPass cp = column(cur, p.nz_z, p.rs_z, p.gz, wz, R.last_epi | (r.sign == 1 ? kEpiSign : 0));
+      if (r.plane16) {  // (the index buffer's own pitch: the row stride of the plane pass Z reads)
         cp.plane = p.codes;
-        cp.plane_stride = p.code_pitch;
+        cp.plane_stride = r.code_pitch;
         cp.plane_outer = sx;
       }
-      cp.signbits = fuse_sign ? p.nz_z : nullptr;
-      TileList served;
-      rc = run_column_pass(cp, Q, 2, p.q16, Fp32Leg::inplace, index_form && y_sure, &served);
-      if (rc == EDT_OK && q16_only && !served.none) { set_error("internal: pass Z left the integer kernel"); return EDT_ERR_HIP; }
-    } else {
-      rc = launch_column_pass_serial(cur, other, p.nz_z, p.rs_z, p.stack, p.gz, wz, bb, last_epi,
-                                     stream);
-      std::swap(cur, other);
+      cp.signbits = r.sign == 1 ? p.nz_z : nullptr;
+      rc = run_column(cp, 2, r.z_pass, Fp32Leg::inplace);
     }
     if (rc != EDT_OK) return rc;
   }
   if (cur != d_out) { set_error("internal: result buffer mismatch"); return EDT_ERR_HIP; }
-  if (signed_tf && !fuse_sign) {
+  if (r.sign == 2) {
     ScopedPass t("sign", stream);
     rc = launch_negate_background(dtype, d_labels, d_out, p.voxels, stream);
     if (rc != EDT_OK) return rc;
@@ -531,15 +584,16 @@ int run_device(const void *d_labels, int dtype, int ndim, int64_t sx, int64_t sy
   return EDT_OK;
 }
 
-// The one-transform form of sdf / sdfsq needs pass X on the register kernel (the only pass-X kernel that takes zero_label)
-// and in-place column passes (their kernels never look at label values: run-start bits and field values only).
+// the route of the call with a workspace of whatever size it asks for (the size and support queries; voxel sizes play no part in either)
+static Route route_for_query(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
+  Route R;
+  float wx = 1.0f, wy = 1.0f, wz = 1.0f;
+  (void)route_of(dtype, ndim, sx, sy, sz, wx, wy, wz, flags, false, SIZE_MAX, 0, R);
+  return R;
+}
+
 bool signed_transform_supported(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
-  if (ndim < 2 || ndim > 3 || dtype_size(dtype) == 0 || sx < 1 || sy < 1 || sz < 1) return false;
-  if ((flags & (EDT_FLAG_FORCE_GENERIC | EDT_FLAG_BINARY_YZ)) || env_force_generic() || (g_debug_mode & kDbgTiledRows)) return false;
-  if (!row_pass_wave_supported(dtype, sx, sy, sz)) return false;
-  if (!column_inplace_supported(make_geom_y(sx, sy, sz))) return false;
-  const bool zpass = ndim == 3 && !(flags & EDT_FLAG_BATCH_2D);
-  return !zpass || column_inplace_supported(make_geom_z(sx, sy, sz));
+  return route_for_query(dtype, ndim, sx, sy, sz, flags).signed_ok;
 }
 
 const char *last_error_cstr() { return g_last_error.c_str(); }
@@ -566,14 +620,20 @@ int edt_hip_index_form_exact(float wx, int64_t sx) { return (sx >= 1 && row_code
 const char *edt_hip_version(void) { return "edt_hip 0.1 (gfx950)"; }
 
 size_t edt_hip_workspace_bytes_flags(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
-  if (check_shape(dtype, ndim, sx, sy, sz) != EDT_OK) return 0;
-  if (sx == 0 || sy == 0 || sz == 0) return 256;
-  return make_plan(dtype, ndim, sx, sy, sz, nullptr, flags).bytes;
+  const Route R = route_for_query(dtype, ndim, sx, sy, sz, flags);
+  return R.empty ? 256 : (size_t)R.r.workspace_bytes;  // (0: a shape every call refuses)
 }
 
 int edt_hip_signed_supported(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, int flags) {
-  if (check_shape(dtype, ndim, sx, sy, sz) != EDT_OK) return 0;
   return signed_transform_supported(dtype, ndim, sx, sy, sz, flags) ? 1 : 0;
+}
+
+int edt_hip_transform_route(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz, int flags,
+                            size_t workspace_bytes, uint32_t out_misalignment, edt_hip_route *route) {
+  Route R;
+  const int rc = route_of(dtype, ndim, sx, sy, sz, wx, wy, wz, flags, false, workspace_bytes, out_misalignment, R);
+  *route = rc == EDT_OK ? R.r : edt_hip_route{};
+  return rc;
 }
 
 size_t edt_hip_workspace_bytes(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz) {

@@ -206,7 +206,6 @@ static int host_prologue(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz
 // labels up, the transform on the current device, the field down
 static int run_on_current_device(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy,
                                  float wz, int flags, float *output) {
-  if (env_force_generic()) flags |= EDT_FLAG_FORCE_GENERIC;
   const size_t lbytes = (size_t)(sx * sy * sz) * dtype_size(dtype), obytes = (size_t)(sx * sy * sz) * sizeof(float);
   const size_t wbytes = edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
   Staging st;
@@ -264,7 +263,6 @@ static int sdf_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t
   if (rc != EDT_OK || empty) return rc;
   ListedDevice on_listed_device;
   if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
-  if (env_force_generic()) flags |= EDT_FLAG_FORCE_GENERIC;
   const int64_t voxels = sx * sy * sz;
   const size_t lbytes = (size_t)voxels * dtype_size(dtype), obytes = (size_t)voxels * sizeof(float);
   const size_t wbytes = std::max(edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags),
@@ -403,7 +401,7 @@ static int label_stats_host(const void *labels, int dtype, int ndim, int64_t sx,
   ListedDevice on_listed_device;
   if (on_listed_device.rc != EDT_OK) return on_listed_device.rc;
   const int64_t voxels = sx * sy * sz;
-  const int flags = (black_border ? EDT_FLAG_BLACK_BORDER : 0) | EDT_FLAG_SQRT | (env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0);
+  const int flags = (black_border ? EDT_FLAG_BLACK_BORDER : 0) | EDT_FLAG_SQRT;
   const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float);
   const size_t tbytes = dt ? 0 : edt_hip_workspace_bytes_flags(dtype, ndim, sx, sy, sz, flags);
   const size_t wbytes = std::max(sbytes, tbytes);
@@ -724,7 +722,7 @@ int edt_hip_watershed(const void *labels, int dtype, int ndim, int64_t sx, int64
   const int64_t voxels = sx * sy * sz;
   const bool mask = !field && binary && dtype != EDT_BOOL;  // the transform of the mask, not of the labels
   const int tdtype = mask ? EDT_U8 : dtype;
-  const int tflags = (flags & EDT_FLAG_BLACK_BORDER) | EDT_FLAG_SQRT | (env_force_generic() ? EDT_FLAG_FORCE_GENERIC : 0);
+  const int tflags = (flags & EDT_FLAG_BLACK_BORDER) | EDT_FLAG_SQRT;
   const size_t lbytes = (size_t)voxels * dtype_size(dtype), fbytes = (size_t)voxels * sizeof(float), obytes = (size_t)voxels * sizeof(uint32_t);
   const size_t sbytes = edt_hip_watershed_workspace_bytes(dtype, ndim, sx, sy, sz);
   const size_t wbytes = std::max(sbytes, field ? 0 : edt_hip_workspace_bytes_flags(tdtype, ndim, sx, sy, sz, tflags));

@@ -246,6 +246,53 @@ int edt_hip_get_debug_mode(void);
  * and holds this answer against what the tiles do (tests/test_q16_logic.py).  No counterpart in the reference. */
 int edt_hip_q16_no_refusals(int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz, int ndim, int black_border,
                             int *pass_y, int *pass_z);
+/* Diagnostics (pure host arithmetic, no device needed): the ROUTE of an edt_hip_edtsq_device call -- everything the library
+ * decides before its first launch: which kernels run, in which order, and what lives in which part of the workspace.  The
+ * call itself asks the same function and then only executes the answer (csrc/edt_api.hip: route_of, run_device; DESIGN.md,
+ * "The route of a call").  Inputs besides the call's own: the calling thread's debug mode, EDT_HIP_FORCE_GENERIC,
+ * EDT_HIP_WHOLE_INDEX_BYTES and EDT_HIP_PLANE_PAD_BYTES in the environment, the bytes of the workspace the caller brings
+ * (SIZE_MAX: whatever the route asks for; 0: none) and d_output's address modulo 16 (out_misalignment: the integer column
+ * kernel loads 16-byte granules of the field).  Returns EDT_OK and the route, or what the call would refuse with before it
+ * launches anything -- same code, same edt_hip_last_error() -- and a route of zeros; an empty volume is EDT_OK and zeros. */
+enum {
+  EDT_ROUTE_X_REGISTER = 0, /* rows in registers, one to four waves per row (csrc/edt_rowwave.hip)            */
+  EDT_ROUTE_X_PHASED = 1,   /* the workgroup-phased row kernel (csrc/edt_rows.hip)                            */
+  EDT_ROUTE_X_LINE = 2,     /* the line pipeline, a thread per voxel: rows no row kernel takes, 1-D lines     */
+  EDT_ROUTE_X_SERIAL = 3    /* a thread per row: forced generic, and a 1-D line without a workspace           */
+};
+enum {
+  EDT_ROUTE_COL_NONE = 0,         /* the call has no such pass                                                  */
+  EDT_ROUTE_COL_SERIAL = 1,       /* the size-agnostic kernel, from one volume into the other (ping-pong)       */
+  EDT_ROUTE_COL_FP32 = 2,         /* in place, an fp32 kernel over every tile                                   */
+  EDT_ROUTE_COL_INTEGER_LIST = 3, /* in place, the 16-bit integer kernel, then an fp32 kernel over its list     */
+  EDT_ROUTE_COL_INTEGER_ALONE = 4 /* the integer kernel alone: the host has proven that it refuses no tile      */
+};
+typedef struct edt_hip_route {
+  int32_t x_kernel;           /* EDT_ROUTE_X_*: the kernel of pass X                                                          */
+  int32_t planes_from_labels; /* 1: the run bit planes of y and z are built from the labels by passes of their own (y_bits,
+                                 z_bits); 0: the row kernel emits them and z_bits is their transposition (1-D: no planes)     */
+  int32_t index_form;         /* 1: pass X hands pass Y 16-bit distance indices, slab by slab, instead of fp32 values         */
+  int32_t codes_whole;        /* 1: the index buffer holds every slice of the volume, 0: one slab (or does not exist)         */
+  int32_t y_pass, z_pass;     /* EDT_ROUTE_COL_*                                                                              */
+  int32_t plane16;            /* 1: pass Y leaves its results in the index buffer as 16-bit values, pass Z reads them there   */
+  int32_t plane_inf_ok;       /* 1: ... and a tile of nothing but +inf may stay in that plane (pass Z carries +inf)           */
+  int32_t skip_nz;            /* 1: nobody reads a foreground plane; pass X writes none, z_bits moves the run starts only     */
+  int32_t row_flags;          /* 1: ... and its storage holds the row flags: pass X stores no indices of rows without a run start */
+  int32_t zero_label;         /* what label 0 is to pass X: 0 background; 1 a label like any other, all-ones foreground
+                                 planes; 2 a label like any other, true foreground planes (for the sign epilogue)            */
+  int32_t sign;               /* EDT_FLAG_SIGNED: 0 not asked for, 1 the epilogue of pass Z, 2 a pass of its own ("sign")     */
+  int32_t binary_yz;          /* 1: one run per column in y and z (EDT_FLAG_BINARY_YZ on a label type that is not bool)       */
+  int32_t first_buffer;       /* where pass X writes: 0 d_output, 1 the second volume (an odd number of ping-pong passes)     */
+  int32_t second_volume;      /* 1: the workspace holds a second fp32 volume and the hull stacks of the serial column kernel  */
+  int32_t index_fallback;     /* 1: the workspace brought is too small for the index buffer and large enough without it: the
+                                 route is the one of EDT_FLAG_SMALL_WORKSPACE (slab = 0)                                      */
+  int64_t slab;               /* slices per slab of the index buffer (0: there is none)                                       */
+  int64_t slabs;              /* launches of pass X and of pass Y each: slabs of the index form, else 1                       */
+  int64_t code_pitch;         /* elements between the slices of the index buffer and of the 16-bit plane (0: 1-D)            */
+  uint64_t workspace_bytes;   /* what this route needs = edt_hip_workspace_bytes_flags, or less under index_fallback          */
+} edt_hip_route;
+int edt_hip_transform_route(int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz, int flags,
+                            size_t workspace_bytes, uint32_t out_misalignment, edt_hip_route *route);
 int edt_hip_get_pass_times(float *ms, int capacity);
 const char *edt_hip_get_pass_name(int index);
 

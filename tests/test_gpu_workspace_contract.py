@@ -345,6 +345,37 @@ def test_residue_pass_log_tells_the_signed_routes_apart(oracle_port):
     assert names["signed, fused"] == names["integer only"] == ["x_pass", "y_pass", "z_bits", "z_pass"], names
 
 
+def names_of_the_route(route):
+    """the pass log a call must leave, from the library's host query (edt_hip_transform_route) alone"""
+    import test_transform_routes_cpu as table
+    name, kind, w, bb, flags, mode, fn = route
+    a = table.answers(lib(), [table.case(U8, 3, EXT, w, flags | (FLAG_BB if bb else 0), mode=mode)])[0]
+    assert a[0] == 0, (name, a)
+    r = dict(zip(table.FIELDS, a[2:]))
+    assert r["slabs"] == 1, (name, r)                       # (several slabs would be one "xy_pass")
+    names = ["x_pass"] + (["y_bits"] if r["planes_from_labels"] else []) + ["y_pass"]
+    names += ["z_bits", "z_pass"] if r["z_pass"] else []
+    return names + (["sign"] if r["sign"] == 2 else [])
+
+
+@pytest.mark.parametrize("r", range(len(ROUTES)), ids=ROUTE_IDS)
+def test_residue_pass_log_is_the_one_the_route_names(oracle_port, r):
+    """what ran is what the host said would run -- and a column pass that left its route would have failed the call"""
+    from edt import device
+    route = ROUTES[r]
+    ws, out = transform_buffer(), transform_out()
+    want_names = names_of_the_route(route)
+    device.set_profiling(True)
+    try:
+        run_route(route, 1, ws, out)
+        sync()
+        names = [n for n, _ in device.pass_times()]
+    finally:
+        device.set_profiling(False)
+    assert names == want_names, (route[0], names, want_names)
+    equal_bits(out, f32_bits(route_want(oracle_port, route, 1)), (route[0], "profiled against its route"))
+
+
 @pytest.mark.parametrize("b", range(len(ROUTES)), ids=ROUTE_IDS)
 def test_residue_every_route_after_every_route(oracle_port, b):
     """route A on volume 0, then route B on volume 1, on one buffer that nobody clears: B's result is the oracle's"""

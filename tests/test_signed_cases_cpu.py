@@ -1,7 +1,7 @@
 """CPU tier: the case table of tests/test_gpu_signed.py (tests/signed_cases.py) against the library's host proof.
 
 Whether the signed transform's sign is the epilogue of the last integer pass or a pass of its own is decided on the host
-(csrc/edt_api.hip: fuse_sign): rows of whole 16-byte granules, both column axes on the integer kernel, and the proof that
+(csrc/edt_api.hip: route_of, the route's `sign`): rows of whole 16-byte granules, both column axes on the integer kernel, and the proof that
 neither column pass can refuse a tile (edt_hip_q16_no_refusals: host arithmetic, no device).  The table states the route of
 every row by hand; here every row is held against the proof before a GPU is involved, so that a row the GPU tier expects to be
 fused can be, and the row that is there because its VALUES defeat the proof does."""
@@ -13,7 +13,13 @@ import numpy as np
 import pytest
 
 import signed_cases as sc
+import test_transform_routes_cpu as routes
 from test_gpu_plain_rows import CASES as PLAIN_CASES
+
+
+def _lib_loaded():
+    from edt import _lib
+    return _lib.load()
 
 
 def library_proof(shape_xyz, w, bb):
@@ -44,6 +50,12 @@ def test_every_row_against_the_host_proof(case):
         # a row of a fused family that the proof turned: it is the proof that says so
         assert proof != (1, 1, 1), (case, proof)
     assert (case.q is None) == (proof[0] == 0), (case, proof)
+    # ... and the route of the call itself (edt_hip_transform_route): the sign is the epilogue of pass Z exactly where the table says
+    ext = list(case.shape) + [1] * (3 - len(case.shape))
+    ws = [float(v) for v in case.an] + [1.0] * (3 - len(case.an))
+    code = {"uint8": 0, "uint16": 1, "uint32": 2, "uint64": 3, "float32": 4, "bool": 6}[np.dtype(case.dtype).name]
+    a = routes.answers(_lib_loaded(), [routes.case(code, len(case.shape), ext, ws, routes.SIGNED | (routes.BB if case.bb else 0))])[0]
+    assert a[0] == 0 and (a[2 + routes.FIELDS.index("sign")] == 1) == case.fused, (case, a)
 
 
 def test_fused_rows_agree_with_the_table_of_plain_rows():
