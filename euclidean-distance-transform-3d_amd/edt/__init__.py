@@ -21,15 +21,16 @@ from __future__ import annotations
 
 import collections
 import ctypes
-import math
 import multiprocessing
 
 import numpy as np
 
 from . import _lib, _moments, _topology
+from ._args import (  # noqa: F401  (the argument rules shared with edt.device; re-exported)
+    _DTYPE_CODE, _NEIGHBOUR_COUNTS, _NP_OF_CODE, DustCounts, LabelMoments, LabelStats, LabelTopology, ThicknessSizes, _check_max_labels,
+    _check_ndim, _connectivity, _dust_bounds, _empty_table, _label_table, _ladder_room, _medial_gamma, _medial_ratio, _min_saliency,
+    _morph_flags, _morph_radius, _thickness_radii, _xyz)
 from ._lib import EdtHipError  # noqa: F401  (re-export)
-from ._moments import LabelMoments
-from ._topology import LabelTopology
 
 # a host that cannot run any transform fails HERE, with the reason (no built library; no GPU device node) -- _lib.probe_at_import
 _lib.probe_at_import()
@@ -60,16 +61,6 @@ def reshape(arr, shape, order=None):
         order = "F" if arr.flags.f_contiguous else ("C" if arr.flags.c_contiguous else None)
     return arr.reshape(shape) if order is None else arr.reshape(shape, order=order)
 
-_DTYPE_CODE = {
-    np.dtype(np.uint8): _lib.U8, np.dtype(np.int8): _lib.U8,
-    np.dtype(np.uint16): _lib.U16, np.dtype(np.int16): _lib.U16,
-    np.dtype(np.uint32): _lib.U32, np.dtype(np.int32): _lib.U32,
-    np.dtype(np.uint64): _lib.U64, np.dtype(np.int64): _lib.U64,
-    np.dtype(np.float32): _lib.F32, np.dtype(np.float64): _lib.F64,
-    np.dtype(bool): _lib.BOOL,
-}
-_UNSIGNED = {_lib.U8: np.uint8, _lib.U16: np.uint16, _lib.U32: np.uint32, _lib.U64: np.uint64}
-
 
 def _label_code(data: np.ndarray) -> int:
     try:
@@ -82,16 +73,37 @@ def _label_code(data: np.ndarray) -> int:
 
 def _as_label_buffer(data: np.ndarray, code: int) -> np.ndarray:
     """Contiguous buffer the kernels can read: signed -> unsigned view, bool -> bytes."""
-    if code in _UNSIGNED:
-        want = np.dtype(_UNSIGNED[code])
-        return data.view(want) if data.dtype != want else data
-    if code == _lib.BOOL:
-        return data.view(np.uint8)
-    return data
+    want = _NP_OF_CODE[code]
+    return data.view(want) if data.dtype != want else data
 
 
 def _ptr(arr: np.ndarray) -> ctypes.c_void_p:
     return ctypes.c_void_p(arr.ctypes.data)
+
+
+class _Call(collections.namedtuple("_Call", ["data", "order", "code", "buf", "nd", "e", "w"])):
+    """One call as the C ABI sees it (:func:`_layout` makes it): the contiguous array and its memory order, the dtype code,
+    the buffer the kernels read, the number of dimensions, and the x-fastest extents and voxel sizes, both padded to three."""
+    __slots__ = ()
+
+    @property
+    def head(self):
+        """how every entry point of the library begins: labels, dtype, ndim, extents"""
+        return (_ptr(self.buf), self.code, self.nd, *self.e)
+
+    def new(self, dtype=None):
+        """an uninitialised result of the data's shape and memory order"""
+        return np.empty(self.data.shape, dtype=self.data.dtype if dtype is None else dtype, order=self.order)
+
+
+def _array(data, who, dtype=True):
+    """Step one of a call, before its own arguments are looked at: an array of 1 to 3 dimensions and (``dtype``) of a label
+    dtype.  Step two, :func:`_layout`, comes after them and after the empty case."""
+    data = np.asarray(data)
+    _check_ndim(who, data.ndim)
+    if dtype:
+        _label_code(data)
+    return data, data.ndim
 
 
 # ----------------------------------------------------------------------------------------
@@ -172,24 +184,14 @@ def binary_edtsq(data, anisotropy=None, black_border=False, parallel=1):
     data = np.asarray(data)
     if data.ndim not in (2, 3):
         raise TypeError("binary_edtsq: 2-D or 3-D arrays")
-    an = (1.0,) * data.ndim if anisotropy is None else anisotropy
-    return _run(data, an, black_border, None, False, ndim=data.ndim, binary=True)
+    return _run(data, anisotropy, black_border, None, False, ndim=data.ndim, binary=True)
 
 
 def binary_edt(data, anisotropy=None, black_border=False, parallel=1):
     data = np.asarray(data)
     if data.ndim not in (2, 3):
         raise TypeError("binary_edt: 2-D or 3-D arrays")
-    an = (1.0,) * data.ndim if anisotropy is None else anisotropy
-    return _run(data, an, black_border, None, True, ndim=data.ndim, binary=True)
-
-
-def _ft_args(data, anisotropy, name):
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"{name}: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    an = (1.0,) * data.ndim if anisotropy is None else anisotropy
-    return data, an
+    return _run(data, anisotropy, black_border, None, True, ndim=data.ndim, binary=True)
 
 
 def _planes_to_axes(planes, shape, order):
@@ -210,20 +212,16 @@ def feature_transform(data, anisotropy=None, black_border=False, parallel=1, ret
     ``return_distances=True`` also returns ``edt(data, anisotropy, black_border)``.  The tie rule runs its passes in
     the order of the array's memory axes, fastest first: axis 0 first for an F-contiguous array (also for one that is
     C-contiguous as well, e.g. with unit axes, as in every entry point of this module), the last axis first otherwise."""
-    data, an = _ft_args(data, anisotropy, "feature_transform")
-    nd = data.ndim
+    data, nd = _array(data, "feature_transform", dtype=False)
     if data.size == 0:
         feats = np.zeros((nd,) + data.shape, dtype=np.int32)
         return (feats, np.zeros(data.shape, dtype=np.float32)) if return_distances else feats
-    data, order, code, buf, extents, w = _layout(data, an, nd)
-    e = tuple(extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
+    c = _layout(data, anisotropy)
     planes = np.empty(nd * data.size, dtype=np.int32)
-    _lib.check(_lib.load().edt_hip_feature_transform(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
-                                                     1 if black_border else 0, _ptr(planes)))
-    feats = _planes_to_axes(planes, data.shape, order)
+    _lib.check(_lib.load().edt_hip_feature_transform(*c.head, *c.w, 1 if black_border else 0, _ptr(planes)))
+    feats = _planes_to_axes(planes, data.shape, c.order)
     if return_distances:
-        return feats, edt(data, anisotropy=an, black_border=black_border, parallel=parallel)
+        return feats, edt(c.data, anisotropy=anisotropy, black_border=black_border, parallel=parallel)
     return feats
 
 
@@ -232,49 +230,40 @@ def expand_labels(data, distance=1.0, anisotropy=None, parallel=1):
     label of its feature in the feature transform of ``data == 0`` if that voxel lies within ``distance``
     (skimage.segmentation.expand_labels with anisotropy; contract: include/edt_hip.h).  Same shape, dtype and memory
     order as ``data``."""
-    data, an = _ft_args(data, anisotropy, "expand_labels")
+    data, nd = _array(data, "expand_labels", dtype=False)
     distance = float(distance)
     if not distance >= 0.0:
         raise ValueError(f"expand_labels: distance must be >= 0, got {distance}")
     if data.size == 0:
         return data.copy()
-    nd = data.ndim
-    data, order, code, buf, extents, w = _layout(data, an, nd)
-    e = tuple(extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
-    out = np.empty(data.shape, dtype=data.dtype, order=order)
-    _lib.check(_lib.load().edt_hip_expand_labels(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
-                                                 distance, _ptr(out)))
+    c = _layout(data, anisotropy)
+    out = c.new()
+    _lib.check(_lib.load().edt_hip_expand_labels(*c.head, *c.w, distance, _ptr(out)))
     return out
 
 
-LabelStats = collections.namedtuple("LabelStats", ["labels", "counts", "max", "argmax", "bbox_lo", "bbox_hi"])
-
-
-def _label_table(who, data, code, max_labels, alloc, call):
-    """What label_stats, label_moments and label_topology do around their library call: the capacity (``max_labels``, or the
-    default rule), the call -- retried with 8x the room while a default capacity proves too small, a ``ValueError`` if an explicit
-    one does --, the columns cut to the ``n`` labels found, the keys back under ``data``'s own type and, for signed dtypes, all
-    columns in signed order.  ``alloc(cap)``: the output columns with ``cap`` rows each, the keys first.
-    ``call(cap, column pointers, n)``: the entry point; ``n`` receives the number of labels.  Returns the columns."""
-    voxels = data.size
-    cap = _lib.default_max_labels(code, voxels)[0] if max_labels is None else min(int(max_labels), voxels)
-    while True:
-        cols = alloc(cap)
+def _table(who, c, max_labels, columns, call):
+    """The numpy side of :func:`edt._args._label_table`: ``columns``, the (dtype, row shape) of every output column behind the
+    keys, allocated per attempt; ``call(cap, column pointers, n)``, the entry point, ``n`` receiving the number of labels.
+    Returns the columns cut to the labels found, the keys back under the data's own type and, for signed dtypes, all columns
+    in signed order."""
+    def attempt(cap):
+        cols = [np.empty((cap,) + shape, dtype=dtype) for dtype, shape in [(c.buf.dtype, ())] + columns]
         count = ctypes.c_int64(0)
-        _lib.check(call(cap, [_ptr(c) for c in cols], ctypes.byref(count)))
-        n = int(count.value)
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"{who}: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    cols = [c[:n] for c in cols]
-    cols[0] = cols[0].view(data.dtype)     # (signed dtypes: the bit patterns back under their own type)
-    if data.dtype.kind == "i":             # the ABI orders bit patterns: negative keys come last there
+        _lib.check(call(cap, [_ptr(col) for col in cols], ctypes.byref(count)))
+        return int(count.value), cols
+
+    cols = _label_table(who, c.code, c.data.size, max_labels, attempt)
+    cols[0] = cols[0].view(c.data.dtype)   # (signed dtypes: the bit patterns back under their own type)
+    if c.data.dtype.kind == "i":           # the ABI orders bit patterns: negative keys come last there
         perm = np.argsort(cols[0], kind="stable")
-        cols = [c[perm] for c in cols]
+        cols = [col[perm] for col in cols]
     return cols
+
+
+def _no_rows(cls, data, nd):
+    _label_code(data)
+    return _empty_table(cls, nd, lambda name, shape: np.zeros(shape, dtype=data.dtype if name is None else name))
 
 
 def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, max_labels=None):
@@ -295,37 +284,24 @@ def label_stats(data, dt=None, anisotropy=None, black_border=False, parallel=1, 
 
     ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x the room while it proves
     too small; an explicit ``max_labels`` that proves too small raises ``ValueError``."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"label_stats: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    nd = data.ndim
+    data, nd = _array(data, "label_stats", dtype=False)
     if dt is not None:
         dt = np.asarray(dt)
         if dt.shape != data.shape or dt.dtype != np.float32:
             raise ValueError("dt must be a float32 array of the data's shape")
-    if max_labels is not None and int(max_labels) < 1:
-        raise ValueError(f"label_stats: max_labels must be at least 1, got {max_labels}")
-    an = (1.0,) * nd if anisotropy is None else anisotropy
+    _check_max_labels("label_stats", max_labels)
     if data.size == 0:
-        _label_code(data)
-        return LabelStats(np.zeros(0, dtype=data.dtype), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32),
-                          np.zeros((0, nd), dtype=np.int64), np.zeros((0, nd), dtype=np.int32),
-                          np.zeros((0, nd), dtype=np.int32))
-    data, order, code, buf, extents, w = _layout(data, an, nd)
+        return _no_rows(LabelStats, data, nd)
+    c = _layout(data, anisotropy)
     if dt is not None:
-        dt = np.asfortranarray(dt) if order == "F" else np.ascontiguousarray(dt)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
-    new = lambda dtype, *shape: np.empty(shape, dtype=dtype)  # noqa: E731
-    keys, counts, mx, arg, bbox = _label_table(
-        "label_stats", data, code, max_labels,
-        lambda cap: [new(buf.dtype, cap), new(np.int64, cap), new(np.float32, cap), new(np.int64, cap), new(np.int32, cap, 6)],
-        lambda cap, cols, n: _lib.load().edt_hip_label_stats(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
-                                                             1 if black_border else 0, None if dt is None else _ptr(dt), cap,
-                                                             *cols, n))
-    n = len(keys)
+        dt = np.asfortranarray(dt) if c.order == "F" else np.ascontiguousarray(dt)
+    keys, counts, mx, arg, bbox = _table(
+        "label_stats", c, max_labels, [(np.int64, ()), (np.float32, ()), (np.int64, ()), (np.int32, (6,))],
+        lambda cap, cols, n: _lib.load().edt_hip_label_stats(*c.head, *c.w, 1 if black_border else 0,
+                                                             None if dt is None else _ptr(dt), cap, *cols, n))
+    n, order = len(keys), c.order
     lo, hi = bbox[:, 0:2 * nd:2], bbox[:, 1:2 * nd:2]
-    argmax = np.stack(np.unravel_index(arg, data.shape, order=order), axis=1).astype(np.int64).reshape(n, nd)
+    argmax = np.stack(np.unravel_index(arg, c.data.shape, order=order), axis=1).astype(np.int64).reshape(n, nd)
     if order == "C":                       # x is the LAST array axis
         lo, hi = lo[:, ::-1], hi[:, ::-1]
     return LabelStats(np.ascontiguousarray(keys), counts, mx, argmax, np.ascontiguousarray(lo), np.ascontiguousarray(hi))
@@ -344,26 +320,16 @@ def label_moments(data, max_labels=None):
     ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x the room while it proves too
     small; an explicit ``max_labels`` that proves too small raises ``ValueError``.  So does a volume with
     ``voxels * (largest extent - 1)**2 >= 2**63`` (lines of millions of voxels): its sums would leave int64."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"label_moments: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    nd = data.ndim
-    if max_labels is not None and int(max_labels) < 1:
-        raise ValueError(f"label_moments: max_labels must be at least 1, got {max_labels}")
+    data, nd = _array(data, "label_moments", dtype=False)
+    _check_max_labels("label_moments", max_labels)
     if data.size == 0:
-        _label_code(data)
-        return LabelMoments(np.zeros(0, dtype=data.dtype), np.zeros(0, dtype=np.int64), np.zeros((0, nd), dtype=np.int64),
-                            np.zeros((0, nd, nd), dtype=np.int64), np.zeros((0, nd), dtype=np.float64),
-                            np.zeros((0, nd, nd), dtype=np.float64))
-    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
+        return _no_rows(LabelMoments, data, nd)
+    c = _layout(data)
     _moments.check_range(data.shape)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    keys, counts, sums, centroid, central = _label_table(
-        "label_moments", data, code, max_labels,
-        lambda cap: [np.empty(cap, dtype=buf.dtype), np.empty(cap, dtype=np.int64), np.empty((cap, 9), dtype=np.int64),
-                     np.empty((cap, 3), dtype=np.float64), np.empty((cap, 6), dtype=np.float64)],
-        lambda cap, cols, n: _lib.load().edt_hip_label_moments(_ptr(buf), code, nd, e[0], e[1], e[2], cap, *cols, n))
-    got = _moments.assemble(np.ascontiguousarray(keys), counts, sums, centroid, central, nd, order == "C")
+    keys, counts, sums, centroid, central = _table(
+        "label_moments", c, max_labels, [(np.int64, ()), (np.int64, (9,)), (np.float64, (3,)), (np.float64, (6,))],
+        lambda cap, cols, n: _lib.load().edt_hip_label_moments(*c.head, cap, *cols, n))
+    got = _moments.assemble(np.ascontiguousarray(keys), counts, sums, centroid, central, nd, c.order == "C")
     return LabelMoments(*[np.ascontiguousarray(f) for f in got])
 
 
@@ -383,60 +349,15 @@ def label_topology(data, max_labels=None):
 
     ``max_labels=None``: exact for 8/16-bit labels, else room for 65536 labels, retried with 8x the room while it proves too
     small; an explicit ``max_labels`` that proves too small raises ``ValueError``."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"label_topology: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    nd = data.ndim
-    if max_labels is not None and int(max_labels) < 1:
-        raise ValueError(f"label_topology: max_labels must be at least 1, got {max_labels}")
+    data, nd = _array(data, "label_topology", dtype=False)
+    _check_max_labels("label_topology", max_labels)
     if data.size == 0:
-        _label_code(data)
-        return LabelTopology(np.zeros(0, dtype=data.dtype), np.zeros(0, dtype=np.int64), np.zeros((0,) + (2,) * nd, dtype=np.int64),
-                             np.zeros((0,) + (2,) * nd, dtype=np.int64))
-    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    keys, closed, interior = _label_table(
-        "label_topology", data, code, max_labels,
-        lambda cap: [np.empty(cap, dtype=buf.dtype), np.empty((cap, 8), dtype=np.int64), np.empty((cap, 8), dtype=np.int64)],
-        lambda cap, cols, n: _lib.load().edt_hip_label_topology(_ptr(buf), code, nd, e[0], e[1], e[2], cap, *cols, n))
-    got = _topology.assemble(np.ascontiguousarray(keys), closed, interior, nd, order == "C")
+        return _no_rows(LabelTopology, data, nd)
+    c = _layout(data)
+    keys, closed, interior = _table("label_topology", c, max_labels, [(np.int64, (8,)), (np.int64, (8,))],
+                                    lambda cap, cols, n: _lib.load().edt_hip_label_topology(*c.head, cap, *cols, n))
+    got = _topology.assemble(np.ascontiguousarray(keys), closed, interior, nd, c.order == "C")
     return LabelTopology(*[np.ascontiguousarray(f) for f in got])
-
-
-_NEIGHBOUR_COUNTS = {2: {4: 1, 8: 2}, 3: {6: 1, 18: 2, 26: 3}}   # cc3d's spelling of the connectivity
-
-
-def _connectivity(connectivity, ndim, default=None, who="connected_components"):
-    """The ABI's connectivity (1..ndim) of a call: None is `default` (itself None: full); 1..ndim as in skimage; cc3d's
-    neighbour counts 4 / 8 (2-D) and 6 / 18 / 26 (3-D).  Anything else is a ValueError."""
-    if connectivity is None:
-        return ndim if default is None else default
-    if isinstance(connectivity, (int, np.integer)) and not isinstance(connectivity, (bool, np.bool_)):
-        c = int(connectivity)
-        if 1 <= c <= ndim:
-            return c
-        if c in _NEIGHBOUR_COUNTS.get(ndim, {}):
-            return _NEIGHBOUR_COUNTS[ndim][c]
-    raise ValueError(f"{who}: connectivity of a {ndim}-D array is None, 1..{ndim}"
-                     + (f" or one of {sorted(_NEIGHBOUR_COUNTS[ndim])}" if ndim in _NEIGHBOUR_COUNTS else "")
-                     + f", got {connectivity!r}")
-
-
-def _label_op_array(data, who):
-    """What every label operation asks of its input before anything else: an array of 1 to 3 dimensions and a label dtype."""
-    data = np.asarray(data)
-    if data.ndim < 1 or data.ndim > 3:
-        raise TypeError(f"{who}: 1-D, 2-D or 3-D arrays, got {data.ndim}-D")
-    _label_code(data)
-    return data, data.ndim
-
-
-def _label_op_layout(data):
-    """... and once its own arguments and the empty case are through: ``(data, order, dtype code, label buffer, x-fastest
-    extents padded to three)``."""
-    nd = data.ndim
-    data, order, code, buf, extents, _ = _layout(data, (1.0,) * nd, nd)
-    return data, order, code, buf, tuple(int(v) for v in extents) + (1,) * (3 - nd)
 
 
 def connected_components(data, connectivity=None, binary=False, return_N=False):
@@ -454,16 +375,15 @@ def connected_components(data, connectivity=None, binary=False, return_N=False):
     array's MEMORY meets them: for a C-contiguous array and ``binary`` that is scipy's numbering, for an F-contiguous one
     (also one that is C-contiguous as well, e.g. with unit axes, as in every entry point of this module) cc3d's.  At most
     2^31 - 1 voxels."""
-    data, nd = _label_op_array(data, "connected_components")
-    c = _connectivity(connectivity, nd)
+    data, nd = _array(data, "connected_components")
+    conn = _connectivity(connectivity, nd)
     if data.size == 0:
         out = np.zeros(data.shape, dtype=np.uint32)
         return (out, 0) if return_N else out
-    data, order, code, buf, e = _label_op_layout(data)
-    out = np.empty(data.shape, dtype=np.uint32, order=order)
+    c = _layout(data)
+    out = c.new(np.uint32)
     n = ctypes.c_int64(0)
-    _lib.check(_lib.load().edt_hip_connected_components(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0,
-                                                        _ptr(out), ctypes.byref(n)))
+    _lib.check(_lib.load().edt_hip_connected_components(*c.head, conn, 1 if binary else 0, _ptr(out), ctypes.byref(n)))
     return (out, int(n.value)) if return_N else out
 
 
@@ -481,36 +401,16 @@ def fill_holes(data, connectivity=None, binary=False, return_fill_count=False):
 
     Returns an array of ``data``'s dtype, shape and memory order; with ``return_fill_count=True`` the pair
     ``(out, n)``, ``n`` the number of voxels that were filled.  At most 2^31 - 1 voxels."""
-    data, nd = _label_op_array(data, "fill_holes")
-    c = _connectivity(connectivity, nd, default=1, who="fill_holes")
+    data, nd = _array(data, "fill_holes")
+    conn = _connectivity(connectivity, nd, default=1, who="fill_holes")
     if data.size == 0:
         out = data.copy()
         return (out, 0) if return_fill_count else out
-    data, order, code, buf, e = _label_op_layout(data)
-    out = np.empty(data.shape, dtype=data.dtype, order=order)
+    c = _layout(data)
+    out = c.new()
     n = ctypes.c_int64(0)
-    _lib.check(_lib.load().edt_hip_fill_holes(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, _ptr(out),
-                                              ctypes.byref(n)))
+    _lib.check(_lib.load().edt_hip_fill_holes(*c.head, conn, 1 if binary else 0, _ptr(out), ctypes.byref(n)))
     return (out, int(n.value)) if return_fill_count else out
-
-
-DustCounts = collections.namedtuple("DustCounts", ["components", "kept", "removed_voxels"])
-_NO_UPPER_BOUND = (1 << 63) - 1          # INT64_MAX: the ABI's "no upper bound"
-
-
-def _dust_bounds(threshold):
-    """(min_voxels, max_voxels) of the ABI from `threshold`: an integer t (sizes below t are removed) or a pair (lo, hi)
-    (lo <= size < hi is kept).  Anything else, a negative value or hi < lo is a ValueError."""
-    def integer(v):
-        return (isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-                and 0 <= int(v) <= _NO_UPPER_BOUND)
-
-    if integer(threshold):
-        return int(threshold), _NO_UPPER_BOUND
-    if (isinstance(threshold, (tuple, list)) and len(threshold) == 2 and integer(threshold[0]) and integer(threshold[1])
-            and int(threshold[0]) <= int(threshold[1])):
-        return int(threshold[0]), int(threshold[1])
-    raise ValueError(f"dust: threshold is a non-negative integer or a pair (lo, hi) of them with lo <= hi, got {threshold!r}")
 
 
 def dust(data, threshold, connectivity=None, binary=False, invert=False, return_counts=False):
@@ -528,30 +428,17 @@ def dust(data, threshold, connectivity=None, binary=False, invert=False, return_
     Returns an array of ``data``'s dtype, shape and memory order: the voxels of kept components and the background bit for
     bit, the voxels of removed components zero.  With ``return_counts=True`` the pair
     ``(out, DustCounts(components, kept, removed_voxels))`` of Python ints.  At most 2^31 - 1 voxels."""
-    data, nd = _label_op_array(data, "dust")
+    data, nd = _array(data, "dust")
     lo, hi = _dust_bounds(threshold)
-    c = _connectivity(connectivity, nd, who="dust")
+    conn = _connectivity(connectivity, nd, who="dust")
     if data.size == 0:
         out = data.copy()
         return (out, DustCounts(0, 0, 0)) if return_counts else out
-    data, order, code, buf, e = _label_op_layout(data)
-    out = np.empty(data.shape, dtype=data.dtype, order=order)
+    c = _layout(data)
+    out = c.new()
     counts = np.zeros(3, dtype=np.int64)
-    _lib.check(_lib.load().edt_hip_dust(_ptr(buf), code, nd, e[0], e[1], e[2], c, 1 if binary else 0, lo, hi,
-                                        1 if invert else 0, _ptr(out), _ptr(counts)))
+    _lib.check(_lib.load().edt_hip_dust(*c.head, conn, 1 if binary else 0, lo, hi, 1 if invert else 0, _ptr(out), _ptr(counts)))
     return (out, DustCounts(*(int(v) for v in counts))) if return_counts else out
-
-
-def _min_saliency(min_saliency):
-    """min_saliency as the float32 the ABI takes: finite and >= 0, else ValueError."""
-    try:
-        with np.errstate(over="ignore"):
-            h = float(np.float32(min_saliency))
-    except (TypeError, ValueError):
-        h = math.nan
-    if isinstance(min_saliency, (bool, np.bool_)) or not (h >= 0.0 and math.isfinite(h)):
-        raise ValueError(f"watershed: min_saliency must be finite (as float32) and >= 0, got {min_saliency!r}")
-    return h
 
 
 def watershed(data, field=None, min_saliency=0.0, connectivity=None, anisotropy=None, black_border=False, binary=False,
@@ -577,60 +464,38 @@ def watershed(data, field=None, min_saliency=0.0, connectivity=None, anisotropy=
     Returns a ``uint32`` array of ``data``'s shape and memory order: 0 for background, else the basin's number in ``1..N``,
     in the order in which a scan of the array's MEMORY meets the basins; with ``return_N=True`` the pair ``(out, N)``.
     ``label_stats(watershed(x), dt)`` is then a table per SPLIT object.  At most 2^31 - 1 voxels."""
-    data, nd = _label_op_array(data, "watershed")
-    c = _connectivity(connectivity, nd, who="watershed")
+    data, nd = _array(data, "watershed")
+    conn = _connectivity(connectivity, nd, who="watershed")
     h = _min_saliency(min_saliency)
     if field is not None:
         field = np.asarray(field)
         if field.shape != data.shape or field.dtype != np.float32:
             raise ValueError("watershed: field must be a float32 array of the data's shape")
-    an = (1.0,) * nd if anisotropy is None else anisotropy
     if data.size == 0:
         out = np.zeros(data.shape, dtype=np.uint32)
         return (out, 0) if return_N else out
-    data, order, code, buf, extents, w = _layout(data, an, nd)
+    c = _layout(data, anisotropy)
     if field is not None:
         with np.errstate(invalid="ignore"):
-            if np.isnan(field[data != 0]).any():
+            if np.isnan(field[c.data != 0]).any():
                 raise ValueError("watershed: the field is NaN on a foreground voxel")
-        field = np.asfortranarray(field) if order == "F" else np.ascontiguousarray(field)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
-    out = np.empty(data.shape, dtype=np.uint32, order=order)
+        field = np.asfortranarray(field) if c.order == "F" else np.ascontiguousarray(field)
+    out = c.new(np.uint32)
     n = ctypes.c_int64(0)
-    _lib.check(_lib.load().edt_hip_watershed(_ptr(buf), code, nd, e[0], e[1], e[2], None if field is None else _ptr(field),
-                                             ww[0], ww[1], ww[2], 1 if black_border else 0, c, 1 if binary else 0, h,
-                                             _ptr(out), ctypes.byref(n)))
+    _lib.check(_lib.load().edt_hip_watershed(*c.head, None if field is None else _ptr(field), *c.w, 1 if black_border else 0,
+                                             conn, 1 if binary else 0, h, _ptr(out), ctypes.byref(n)))
     return (out, int(n.value)) if return_N else out
 
 
-def _morph_radius(radius, who, inf_allowed=False):
-    """The radius of a morphology call as a float: >= 0 with a finite square (``inf_allowed``: or +inf itself), else ValueError."""
-    r = float(radius)
-    if not r >= 0.0 or not (np.isfinite(r * r) or (inf_allowed and r == np.inf)):
-        raise ValueError(f"{who}: radius must be >= 0 and its square finite" + (" (+inf allowed)" if inf_allowed else "")
-                         + f", got {radius!r}")
-    return r
-
-
 def _morphology(who, op, data, radius, anisotropy, flags):
-    data, an = _ft_args(data, anisotropy, who)
-    _label_code(data)
+    data, nd = _array(data, who)
     r = _morph_radius(radius, who, inf_allowed=op == _lib.MORPH_DILATE)
     if data.size == 0:
         return data.copy()
-    nd = data.ndim
-    data, order, code, buf, extents, w = _layout(data, an, nd)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
-    out = np.empty(data.shape, dtype=data.dtype, order=order)
-    _lib.check(_lib.load().edt_hip_morphology(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2], op, r, flags,
-                                              _ptr(out)))
+    c = _layout(data, anisotropy)
+    out = c.new()
+    _lib.check(_lib.load().edt_hip_morphology(*c.head, *c.w, op, r, flags, _ptr(out)))
     return out
-
-
-def _morph_flags(black_border, binary):
-    return (_lib.FLAG_BLACK_BORDER if black_border else 0) | (_lib.FLAG_MORPH_BINARY if binary else 0)
 
 
 def erode(data, radius=1.0, anisotropy=None, black_border=False, binary=False, parallel=1):
@@ -664,29 +529,6 @@ def closing(data, radius=1.0, anisotropy=None, parallel=1):
     return _morphology("closing", _lib.MORPH_CLOSE, data, radius, anisotropy, 0)
 
 
-ThicknessSizes = collections.namedtuple("ThicknessSizes", ["radii", "voxels"])
-
-
-def _thickness_radii(radii, who="local_thickness"):
-    """The radii of a local_thickness call as a float64 array: at least one, each > 0 with a finite square (``_morph_radius``),
-    strictly ascending; anything else is a ValueError."""
-    try:
-        r = np.array([_morph_radius(v, who) for v in np.asarray(radii, dtype=np.float64).reshape(-1)], dtype=np.float64)
-    except TypeError:
-        raise ValueError(f"{who}: radii must be numbers, got {radii!r}") from None
-    if r.size < 1 or not (r > 0.0).all() or not (np.diff(r) > 0.0).all():
-        raise ValueError(f"{who}: radii must be at least one, > 0 and strictly ascending, got {radii!r}")
-    return r
-
-
-def _ladder_room(extents, w):
-    """``(step, room)`` of the default ladder r_j = j * step: step is the smallest |voxel size|, and no ladder is longer than
-    ``room``, because S <= sum_i (w_i (n_i + 1))^2 and the ladder ends where r_j^2 reaches the largest finite S."""
-    step = min(abs(float(v)) for v in w)
-    bound = sum((abs(float(v)) * (int(n) + 1)) ** 2 for v, n in zip(w, extents))
-    return step, int(np.sqrt(bound) / step) + 2
-
-
 def local_thickness(data, radii=None, anisotropy=None, black_border=False, binary=False, return_sizes=False, parallel=1):
     """Local thickness of every label of a 1-D to 3-D label array at once (porespy's ``local_thickness``, ImageJ's "Local
     Thickness", quantised to a ladder of radii; contract: include/edt_hip.h, "local thickness"): for every voxel the largest
@@ -702,58 +544,24 @@ def local_thickness(data, radii=None, anisotropy=None, black_border=False, binar
     Returns float32 of ``data``'s shape and memory order; with ``return_sizes=True`` the pair ``(thickness,
     ThicknessSizes(radii, voxels))``: the radii actually used (float64) and the voxel count of each radius' opening (int64),
     the granulometry curve.  One trip over PCIe each way; per radius one binary transform and one streaming kernel."""
-    data, an = _ft_args(data, anisotropy, "local_thickness")
-    _label_code(data)
+    data, nd = _array(data, "local_thickness")
     r = None if radii is None else _thickness_radii(radii)
     if data.size == 0:
         out = np.zeros(data.shape, dtype=np.float32)
         used = np.zeros(0, dtype=np.float64) if r is None else r
         return (out, ThicknessSizes(used, np.zeros(used.size, dtype=np.int64))) if return_sizes else out
-    nd = data.ndim
-    data, order, code, buf, extents, w = _layout(data, an, nd)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
-    step, room = (0.0, r.size) if r is not None else _ladder_room(extents, w)
-    out = np.empty(data.shape, dtype=np.float32, order=order)
+    c = _layout(data, anisotropy)
+    step, room = (0.0, r.size) if r is not None else _ladder_room(c.e[:nd], c.w[:nd])
+    out = c.new(np.float32)
     sizes = np.zeros(room, dtype=np.int64)
     n = ctypes.c_int64(0)
-    _lib.check(_lib.load().edt_hip_local_thickness(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
-                                                   _morph_flags(black_border, binary), None if r is None else _ptr(r), room, step,
-                                                   _ptr(out), _ptr(sizes), ctypes.byref(n)))
+    _lib.check(_lib.load().edt_hip_local_thickness(*c.head, *c.w, _morph_flags(black_border, binary), None if r is None else _ptr(r),
+                                                   room, step, _ptr(out), _ptr(sizes), ctypes.byref(n)))
     if not return_sizes:
         return out
     k = int(n.value)
     used = r if r is not None else np.arange(1, k + 1, dtype=np.float64) * step
     return out, ThicknessSizes(used, sizes[:k].copy())
-
-
-def _medial_ratio(min_angle, who="medial_axis"):
-    """The angle pruning of a medial_axis call, ``min_angle`` in degrees in [0, 180), as the ``ratio`` of the C ABI:
-    ``tan(radians(a) / 2) ** 2`` (0 switches it off); anything else is a ValueError.  Both Python layers convert here."""
-    try:
-        a = float(min_angle)
-    except TypeError:
-        raise ValueError(f"{who}: min_angle must be a number, got {min_angle!r}") from None
-    if not (0.0 <= a < 180.0):
-        raise ValueError(f"{who}: min_angle must be in [0, 180) degrees, got {min_angle!r}")
-    ratio = math.tan(math.radians(a) / 2.0) ** 2
-    if not np.isfinite(ratio):
-        raise ValueError(f"{who}: min_angle {min_angle!r} is too close to 180 degrees")
-    return ratio
-
-
-def _medial_gamma(gamma, w, who="medial_axis"):
-    """The constant pruning of a medial_axis call as a float: ``None`` is the largest |voxel size| (the paper's "features more
-    than one voxel apart"); otherwise finite, >= 0 and with a finite square, else ValueError."""
-    if gamma is None:
-        return max(abs(float(v)) for v in w)
-    try:
-        g = float(gamma)
-    except TypeError:
-        raise ValueError(f"{who}: gamma must be a number, got {gamma!r}") from None
-    if not g >= 0.0 or not np.isfinite(g * g):
-        raise ValueError(f"{who}: gamma must be finite and >= 0 with a finite square, got {gamma!r}")
-    return g
 
 
 def medial_axis(data, gamma=None, min_angle=0.0, anisotropy=None, black_border=False, binary=False, return_distance=False,
@@ -774,21 +582,16 @@ def medial_axis(data, gamma=None, min_angle=0.0, anisotropy=None, black_border=F
     Returns an array of ``data``'s shape, dtype and memory order: the label on the axis, 0 elsewhere.  With
     ``return_distance=True`` the pair ``(axis, distance)``: ``distance`` is float32, ``edt(data)`` (of the mask under binary) on
     the axis and 0 elsewhere -- the radius function.  One trip over PCIe each way."""
-    data, an = _ft_args(data, anisotropy, "medial_axis")
-    _label_code(data)
+    data, nd = _array(data, "medial_axis")
     ratio = _medial_ratio(min_angle)
     if data.size == 0:
         _medial_gamma(gamma, (1.0,))
         return (data.copy(), np.zeros(data.shape, dtype=np.float32)) if return_distance else data.copy()
-    nd = data.ndim
-    data, order, code, buf, extents, w = _layout(data, an, nd)
-    g = _medial_gamma(gamma, w)
-    e = tuple(int(v) for v in extents) + (1,) * (3 - nd)
-    ww = tuple(w) + (1.0,) * (3 - nd)
-    out = np.empty(data.shape, dtype=data.dtype, order=order)
-    dist = np.empty(data.shape, dtype=np.float32, order=order) if return_distance else None
-    _lib.check(_lib.load().edt_hip_medial_axis(_ptr(buf), code, nd, e[0], e[1], e[2], ww[0], ww[1], ww[2],
-                                               _morph_flags(black_border, binary), g, ratio, _ptr(out),
+    c = _layout(data, anisotropy)
+    g = _medial_gamma(gamma, c.w[:nd])
+    out = c.new()
+    dist = c.new(np.float32) if return_distance else None
+    _lib.check(_lib.load().edt_hip_medial_axis(*c.head, *c.w, _morph_flags(black_border, binary), g, ratio, _ptr(out),
                                                None if dist is None else _ptr(dist)))
     return (out, dist) if return_distance else out
 
@@ -852,26 +655,23 @@ def _transform(data, anisotropy, black_border, parallel, voxel_graph, take_sqrt,
         raise TypeError(
             "Voxel connectivity graph is only supported for 2D and 3D. Got {}.".format(dims))
 
-    if dims == 1:
-        anisotropy = (1.0 if anisotropy is None else anisotropy,)
-    elif dims == 2:
-        anisotropy = (1.0, 1.0) if anisotropy is None else anisotropy
-    elif dims == 3:
-        anisotropy = (1.0, 1.0, 1.0) if anisotropy is None else anisotropy
-    else:
+    if dims < 1 or dims > 3:
         raise TypeError(
             "Multi-Label EDT library only supports up to 3 dimensions got {}.".format(dims))
     return _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim=dims, signed=signed)
 
 
-def _layout(data, anisotropy, ndim):
-    """The buffer the kernels read and how it maps onto the C ABI (x the fastest axis of memory): returns
-    (data, order, dtype code, label buffer, x-fastest extents, x-fastest voxel sizes); validates the voxel sizes."""
+def _layout(data, anisotropy=None):
+    """Step two of a call: the buffer the kernels read and how it maps onto the C ABI (x the fastest axis of memory), as a
+    :class:`_Call`; validates the voxel sizes (``None``: 1.0 along every axis)."""
+    ndim = data.ndim
     if not data.flags.c_contiguous and not data.flags.f_contiguous:
         data = np.ascontiguousarray(data)
     order = "F" if data.flags.f_contiguous else "C"
     code = _label_code(data)
     buf = _as_label_buffer(data, code)
+    if anisotropy is None:
+        return _Call(data, order, code, buf, ndim, *_xyz(data.shape, None, ndim, order == "C"))
 
     if np.ndim(anisotropy) == 0:
         anisotropy = (anisotropy,) * ndim if ndim == 1 else anisotropy
@@ -885,14 +685,7 @@ def _layout(data, anisotropy, ndim):
     fastest = 0 if order == "F" else ndim - 1
     if not all(np.isfinite(a) and a != 0.0 for a in weights) or weights[fastest] < 0.0:
         raise ValueError(f"anisotropy must be finite and non-zero (and positive along the fastest axis), got {weights}")
-
-    # x is the fastest axis of the buffer the kernels see.
-    if order == "F":
-        extents, w = tuple(data.shape), weights
-    else:
-        extents, w = tuple(data.shape[::-1]), weights[::-1]
-
-    return data, order, code, buf, extents, w
+    return _Call(data, order, code, buf, ndim, *_xyz(data.shape, weights, ndim, order == "C"))   # x: the fastest axis of the buffer
 
 
 def _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim, signed=False, binary=False):
@@ -900,7 +693,8 @@ def _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim, signed=Fa
         raise TypeError(f"expected a {ndim}-D array, got {data.ndim}-D")
     if data.size == 0:
         return np.zeros(shape=data.shape, dtype=np.float32)
-    data, order, code, buf, extents, w = _layout(data, anisotropy, ndim)
+    c = _layout(data, anisotropy)
+    data, order, labels, e, w = c.data, c.order, _ptr(c.buf), c.e, c.w
 
     lib = _lib.load()
     out = np.empty(data.size, dtype=np.float32)
@@ -916,39 +710,22 @@ def _run(data, anisotropy, black_border, voxel_graph, take_sqrt, ndim, signed=Fa
         graph = np.ascontiguousarray(graph) if order == "C" else np.asfortranarray(graph)
         # only the low 6 bits are meaningful (src/edt.pyx:748-752)
         graph = graph.view(np.uint8) if graph.dtype.itemsize == 1 else graph.astype(np.uint8, order="K")
-        if ndim == 2:
-            rc = lib.edt_hip_edt2dsq_voxel_graph(_ptr(buf), code, _ptr(graph), extents[0], extents[1],
-                                                 w[0], w[1], bb, _ptr(out))
-        else:
-            rc = lib.edt_hip_edt3dsq_voxel_graph(_ptr(buf), code, _ptr(graph), extents[0], extents[1],
-                                                 extents[2], w[0], w[1], w[2], bb, _ptr(out))
-        _lib.check(rc)
+        fn = lib.edt_hip_edt2dsq_voxel_graph if ndim == 2 else lib.edt_hip_edt3dsq_voxel_graph
+        _lib.check(fn(labels, c.code, _ptr(graph), *e[:ndim], *w[:ndim], bb, _ptr(out)))
         if take_sqrt:
             np.sqrt(out, out)
-        return out.reshape(data.shape, order=order)
-
-    if signed:  # sdf / sdfsq: edt(x) - edt(x == 0), everything but the two copies on the device
-        e = tuple(extents) + (1,) * (3 - ndim)
-        ww = tuple(w) + (1.0,) * (3 - ndim)
-        _lib.check(lib.edt_hip_sdf(_ptr(buf), code, ndim, e[0], e[1], e[2], ww[0], ww[1], ww[2], bb,
-                                   0 if take_sqrt else 1, _ptr(out)))
+    elif signed:  # sdf / sdfsq: edt(x) - edt(x == 0), everything but the two copies on the device
+        _lib.check(lib.edt_hip_sdf(*c.head, *w, bb, 0 if take_sqrt else 1, _ptr(out)))
     elif binary:
-        e = tuple(extents) + (1,) * (3 - ndim)
-        ww = tuple(w) + (1.0,) * (3 - ndim)
-        _lib.check(lib.edt_hip_binary_edtsq(_ptr(buf), code, ndim, e[0], e[1], e[2], ww[0], ww[1], ww[2], bb,
-                                            1 if take_sqrt else 0, _ptr(out)))
+        _lib.check(lib.edt_hip_binary_edtsq(*c.head, *w, bb, 1 if take_sqrt else 0, _ptr(out)))
     elif ndim == 1:
-        rc = lib.edt_hip_squared_edt_1d_multi_seg(_ptr(buf), code, _ptr(out), data.size, 1, w[0], bb)
-        _lib.check(rc)
+        _lib.check(lib.edt_hip_squared_edt_1d_multi_seg(labels, c.code, _ptr(out), data.size, 1, w[0], bb))
         if take_sqrt:
             np.sqrt(out, out)
-    elif ndim == 2:
-        fn = lib.edt_hip_edt2d if take_sqrt else lib.edt_hip_edt2dsq
-        _lib.check(fn(_ptr(buf), code, extents[0], extents[1], w[0], w[1], bb, 1, _ptr(out)))
     else:
-        fn = lib.edt_hip_edt3d if take_sqrt else lib.edt_hip_edt3dsq
-        _lib.check(fn(_ptr(buf), code, extents[0], extents[1], extents[2], w[0], w[1], w[2], bb, 1,
-                      _ptr(out)))
+        fn = ((lib.edt_hip_edt2d if take_sqrt else lib.edt_hip_edt2dsq) if ndim == 2 else
+              (lib.edt_hip_edt3d if take_sqrt else lib.edt_hip_edt3dsq))
+        _lib.check(fn(labels, c.code, *e[:ndim], *w[:ndim], bb, 1, _ptr(out)))
     return out.reshape(data.shape, order=order)
 
 

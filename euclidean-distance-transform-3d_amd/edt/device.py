@@ -11,16 +11,18 @@ before they reach the kernels (reference: src/edt.pyx:651-656).
 """
 from __future__ import annotations
 
-import collections
 import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib, _moments, _topology
-from ._moments import LabelMoments
-from ._topology import LabelTopology
+from ._args import (  # noqa: F401  (LabelStats: re-exported, the class of edt.label_stats)
+    _NP_OF_CODE, LabelMoments, LabelStats, LabelTopology, ThicknessSizes, _check_max_labels, _check_ndim, _connectivity, _dust_bounds,
+    _empty_table, _label_table, _ladder_room, _medial_gamma, _medial_ratio, _min_saliency, _morph_flags, _morph_radius, _thickness_radii,
+    _xyz)
 
+# torch's dtypes: the code of include/edt_hip.h a label dtype has (edt._args has numpy's)
 _TORCH_CODE = {
     torch.uint8: _lib.U8, torch.int8: _lib.U8,
     torch.int16: _lib.U16, torch.int32: _lib.U32, torch.int64: _lib.U64,
@@ -136,24 +138,38 @@ def _plan_for(ext, code, device) -> Plan:
     return _plans[key]
 
 
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _input(labels, anisotropy=None, who=None, code=True):
+    """What every entry point asks of its input: ``(contiguous tensor, dtype code, nd, x-fastest extents, x-fastest voxel
+    sizes)``, extents and sizes padded to three.  Refused, in this order: what is no device array; a tensor not of 1 to 3
+    dimensions (``who``: the operation in the text; None: the reference's text); an ``anisotropy`` -- None, a number, or one size
+    per tensor axis -- of another length than the tensor has axes; a dtype without a code (``code=False``: not looked at, the
+    caller does after its own arguments and the empty case)."""
+    labels = as_device_tensor(labels)
+    nd = labels.dim()
+    if who is not None:
+        _check_ndim(who, nd, "tensors")
+    elif nd < 1 or nd > 3:
+        raise TypeError("Multi-Label EDT library only supports up to 3 dimensions got {}.".format(nd))
+    if anisotropy is not None:
+        anisotropy = (float(anisotropy),) if np.ndim(anisotropy) == 0 else tuple(float(a) for a in anisotropy)
+    ext, w = _xyz(labels.shape, anisotropy, nd)
+    return labels.contiguous(), dtype_code(labels.dtype) if code else None, nd, ext, w
+
+
 def _transform(labels, anisotropy, black_border, sqrt, force_generic=False, binary=False, signed=False):
     """signed: the signed transform where the shape is served (one transform), None returned where it is not"""
     labels = as_device_tensor(labels)
     if labels.numel() == 0:
         return torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(
-            "Multi-Label EDT library only supports up to 3 dimensions got {}.".format(labels.dim()))
-    labels = labels.contiguous()
-    nd = labels.dim()
-    an = (1.0,) * nd if anisotropy is None else (
-        (float(anisotropy),) if np.ndim(anisotropy) == 0 else tuple(float(a) for a in anisotropy))
-    ext = tuple(labels.shape[::-1])
-    w = an[::-1]
-    plan = _plan_for(ext, dtype_code(labels.dtype), labels.device)
+    labels, code, nd, ext, w = _input(labels, anisotropy)
+    plan = _plan_for(ext[:nd], code, labels.device)
     if signed and not plan.signed_supported():
         return None
-    return plan.run(labels, w, black_border, sqrt, force_generic=force_generic, binary=binary, signed=signed)
+    return plan.run(labels, w[:nd], black_border, sqrt, force_generic=force_generic, binary=binary, signed=signed)
 
 
 def binary_edtsq(labels: torch.Tensor, anisotropy=None, black_border=False) -> torch.Tensor:
@@ -174,63 +190,38 @@ def edt(labels: torch.Tensor, anisotropy=None, black_border=False) -> torch.Tens
     return _transform(labels, anisotropy, black_border, sqrt=True)
 
 
-def _ft_tensor(labels, anisotropy, name):
-    labels = as_device_tensor(labels)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"{name}: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
-    labels = labels.contiguous()
-    nd = labels.dim()
-    an = (1.0,) * nd if anisotropy is None else (
-        (float(anisotropy),) if np.ndim(anisotropy) == 0 else tuple(float(a) for a in anisotropy))
-    if len(an) != nd:
-        raise ValueError(f"anisotropy must have {nd} entries, got {len(an)}")
-    ext = tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-    w = tuple(float(np.float32(a)) for a in an[::-1]) + (1.0,) * (3 - nd)
-    return labels, nd, ext, w
-
-
 def feature_transform(labels: torch.Tensor, anisotropy=None, black_border=False, force_generic=False) -> torch.Tensor:
     """Feature transform of a device tensor (semantics: :func:`edt.feature_transform` on a C-ordered array; anisotropy
     in tensor axis order).  Returns int32 of shape ``(labels.dim(),) + labels.shape`` on the same device: component k is
     the coordinate along tensor axis k.  The kernels write the components in ABI order (x, y, z: tensor axes last to
     first) and the result is a reordered COPY of them: at its peak the call holds twice the output (4 bytes per voxel
     and component each) besides the workspace, which is freed before the copy."""
-    labels, nd, ext, w = _ft_tensor(labels, anisotropy, "feature_transform")
+    labels, _, nd, ext, w = _input(labels, anisotropy, "feature_transform", code=False)
     if labels.numel() == 0:
         return torch.zeros((nd,) + tuple(labels.shape), dtype=torch.int32, device=labels.device)
-    lib = _lib.load()
     code = dtype_code(labels.dtype)
     flags = (_lib.FLAG_BLACK_BORDER if black_border else 0) | (_lib.FLAG_FORCE_GENERIC if force_generic else 0)
-    nbytes = lib.edt_hip_feature_workspace_bytes(code, nd, *ext, flags)
-    if nbytes == 0:
-        _lib.check(-2)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)
+    ws = _workspace("edt_hip_feature_workspace_bytes", code, nd, *ext, flags, device=labels.device, keep=False)
     planes = torch.empty((nd,) + tuple(labels.shape), dtype=torch.int32, device=labels.device)  # x, y, z planes
-    _lib.check(lib.edt_hip_feature_transform_device(
-        ctypes.c_void_p(labels.data_ptr()), code, nd, *ext, *w, flags, ctypes.c_void_p(planes.data_ptr()),
-        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr()))
+    _lib.check(_lib.load().edt_hip_feature_transform_device(_vp(labels), code, nd, *ext, *w, flags, _vp(planes), _vp(ws), ws.numel(),
+                                                            _stream_ptr()))
     del ws
     return planes.flip(0)  # tensor axis k = plane nd-1-k
 
 
 def expand_labels(labels: torch.Tensor, distance=1.0, anisotropy=None) -> torch.Tensor:
     """:func:`edt.expand_labels` on a device tensor (anisotropy in tensor axis order); same shape and dtype."""
-    labels, nd, ext, w = _ft_tensor(labels, anisotropy, "expand_labels")
+    labels, _, nd, ext, w = _input(labels, anisotropy, "expand_labels", code=False)
     distance = float(distance)
     if not distance >= 0.0:
         raise ValueError(f"expand_labels: distance must be >= 0, got {distance}")
     if labels.numel() == 0:
         return labels.clone()
-    lib = _lib.load()
     code = dtype_code(labels.dtype)
-    nbytes = lib.edt_hip_expand_labels_workspace_bytes(code, nd, *ext)
-    if nbytes == 0:
-        _lib.check(-2)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)
+    ws = _workspace("edt_hip_expand_labels_workspace_bytes", code, nd, *ext, device=labels.device, keep=False)
     out = torch.empty_like(labels)
-    _lib.check(lib.edt_hip_expand_labels_device(
-        ctypes.c_void_p(labels.data_ptr()), code, nd, *ext, *w, distance, ctypes.c_void_p(out.data_ptr()),
-        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr()))
+    _lib.check(_lib.load().edt_hip_expand_labels_device(_vp(labels), code, nd, *ext, *w, distance, _vp(out), _vp(ws), ws.numel(),
+                                                        _stream_ptr()))
     return out
 
 
@@ -240,13 +231,11 @@ def _stack2d(images, anisotropy, black_border, sqrt):
         raise TypeError("a stack of 2-D images is a 3-D tensor (count, height, width)")
     if images.numel() == 0:
         return torch.zeros(images.shape, dtype=torch.float32, device=images.device)
-    images = images.contiguous()
     an = (1.0, 1.0) if anisotropy is None else tuple(float(a) for a in anisotropy)
     if len(an) != 2:
         raise ValueError("anisotropy of a 2-D image has 2 entries")
-    ext = tuple(images.shape[::-1])            # (width, height, count): x fastest
-    plan = _plan_for(ext, dtype_code(images.dtype), images.device)
-    return plan.run(images, (an[1], an[0], 1.0), black_border, sqrt, batch2d=True)
+    images, code, _, ext, _ = _input(images)   # (width, height, count): x fastest
+    return _plan_for(ext, code, images.device).run(images, (an[1], an[0], 1.0), black_border, sqrt, batch2d=True)
 
 
 def edtsq_stack(images: torch.Tensor, anisotropy=None, black_border=False) -> torch.Tensor:
@@ -301,25 +290,15 @@ def edtsq_voxel_graph(labels: torch.Tensor, voxel_graph: torch.Tensor, anisotrop
     labels, voxel_graph = as_device_tensor(labels), as_device_tensor(voxel_graph)
     if labels.dim() not in (2, 3) or voxel_graph.shape != labels.shape or voxel_graph.dtype != torch.uint8:
         raise TypeError("voxel_graph needs a 2-D or 3-D volume and a uint8 graph of the same shape")
-    lib = _lib.load()
-    labels, voxel_graph = labels.contiguous(), voxel_graph.contiguous()
-    ndim = labels.dim()
-    an = (1.0,) * ndim if anisotropy is None else tuple(float(a) for a in anisotropy)
     # a C-ordered tensor (z, y, x) is the x-fastest volume with extents and weights reversed
-    ext = tuple(labels.shape[::-1]) + (1,) * (3 - ndim)
-    w = an[::-1] + (1.0,) * (3 - ndim)
+    labels, code, ndim, ext, w = _input(labels, anisotropy)
+    voxel_graph = voxel_graph.contiguous()
     out = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
-    nbytes = lib.edt_hip_voxel_graph_workspace_bytes(ndim, ext[0], ext[1], ext[2])
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=labels.device)
-    _lib.check(lib.edt_hip_edtsq_voxel_graph_device(
-        ctypes.c_void_p(labels.data_ptr()), dtype_code(labels.dtype), ctypes.c_void_p(voxel_graph.data_ptr()),
-        ndim, ext[0], ext[1], ext[2], w[0], w[1], w[2], _lib.FLAG_BLACK_BORDER if black_border else 0,
-        ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr()))
+    ws = _workspace("edt_hip_voxel_graph_workspace_bytes", ndim, *ext, device=labels.device, keep=False)
+    _lib.check(_lib.load().edt_hip_edtsq_voxel_graph_device(
+        _vp(labels), code, _vp(voxel_graph), ndim, *ext, *w, _lib.FLAG_BLACK_BORDER if black_border else 0, _vp(out), _vp(ws),
+        ws.numel(), _stream_ptr()))
     return out
-
-
-_NP_OF_CODE = {_lib.U8: np.uint8, _lib.BOOL: np.uint8, _lib.U16: np.uint16, _lib.U32: np.uint32,
-               _lib.U64: np.uint64, _lib.F32: np.float32, _lib.F64: np.float64}
 
 
 def _key_buffer(code: int, key) -> np.ndarray:
@@ -365,7 +344,7 @@ def runs(labels: torch.Tensor):
         z = torch.zeros(0, dtype=torch.int64, device=dev)
         return z, z.clone(), labels.reshape(-1)
     code = dtype_code(labels.dtype)
-    ws = torch.empty(int(lib.edt_hip_runs_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    ws = _workspace("edt_hip_runs_workspace_bytes", n, device=dev, keep=False)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     lp, cp, wp = ctypes.c_void_p(labels.data_ptr()), ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(ws.data_ptr())
     _lib.check(lib.edt_hip_extract_runs_device(lp, code, n, None, 0, cp, wp, ws.numel(), _stream_ptr()))
@@ -429,46 +408,36 @@ def each(labels: torch.Tensor, dt: torch.Tensor, in_place: bool = False):
     return _DeviceLabelImages(labels, dt, bool(in_place))
 
 
-LabelStats = collections.namedtuple("LabelStats", ["labels", "counts", "max", "argmax", "bbox_lo", "bbox_hi"])
-
 _SIGNED_TORCH = (torch.int8, torch.int16, torch.int32, torch.int64)
 
 
 default_max_labels = _lib.default_max_labels
 
 
-def _fresh_workspace(query, *query_args, device) -> torch.Tensor:
-    """The scratch of one library call, allocated for it: ``query(*query_args)`` bytes on ``device`` (:func:`_workspace` is the
-    cached source; a query that answers 0 is the library's refusal here)."""
-    nbytes = int(getattr(_lib.load(), query)(*query_args))
-    if nbytes == 0:
-        _lib.check(-2)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+def _table(who, labels, code, max_labels, columns, query, call, keep):
+    """The device side of :func:`edt._args._label_table`: ``columns``, the (dtype, row shape) of every output column behind the
+    keys, allocated per attempt together with the int64 device word for the number of labels and the workspace of ``query``
+    (``keep``: as :func:`_workspace`); ``call(cap, tail)``, the device entry point, ``tail`` being its arguments from the columns
+    on.  Returns the columns cut to the labels found and, for signed dtypes, brought into signed order."""
+    dev = labels.device
 
+    def attempt(cap):
+        cols = [torch.empty((cap,) + shape, dtype=dtype, device=dev) for dtype, shape in [(labels.dtype, ())] + columns]
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = _workspace(query, code, labels.numel(), cap, device=dev, keep=keep)
+        _lib.check(call(cap, [*map(_vp, cols), _vp(count), _vp(ws), ws.numel(), _stream_ptr()]))
+        return int(count.item()), cols  # the only host synchronisation
 
-def _label_table(who, labels, max_labels, alloc, call):
-    """What label_stats, label_moments and label_topology do around their device call: the capacity (``max_labels``, or the
-    default rule), the call -- retried with 8x the room while a default capacity proves too small, a ``ValueError`` if an explicit
-    one does --, the columns cut to the ``n`` labels found and, for signed dtypes, brought into signed order.  ``alloc(cap)``:
-    the output columns with ``cap`` rows each, the keys first.  ``call(cap, columns, n)``: the device entry point on its
-    workspace; ``n`` is the int64 device word it writes the number of labels to.  Returns the columns."""
-    voxels = labels.numel()
-    cap = default_max_labels(dtype_code(labels.dtype), voxels)[0] if max_labels is None else min(int(max_labels), voxels)
-    while True:
-        cols = alloc(cap)
-        count = torch.empty(1, dtype=torch.int64, device=labels.device)
-        call(cap, cols, count)
-        n = int(count.item())           # the only host synchronisation
-        if n <= cap:
-            break
-        if max_labels is not None:
-            raise ValueError(f"{who}: more than max_labels = {int(max_labels)} distinct non-zero labels")
-        cap = min(voxels, 8 * cap)
-    cols = [c[:n] for c in cols]
+    cols = _label_table(who, code, labels.numel(), max_labels, attempt)
     if labels.dtype in _SIGNED_TORCH:   # the ABI orders bit patterns: negative keys come last there
         perm = torch.argsort(cols[0], stable=True)
         cols = [c[perm] for c in cols]
     return cols
+
+
+def _no_rows(cls, labels, nd):
+    return _empty_table(cls, nd, lambda name, shape: torch.zeros(shape, dtype=labels.dtype if name is None else getattr(torch, name),
+                                                                 device=labels.device))
 
 
 def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> LabelStats:
@@ -483,26 +452,15 @@ def label_stats(labels: torch.Tensor, dt: torch.Tensor, max_labels=None) -> Labe
     labels, dt = as_device_tensor(labels), as_device_tensor(dt)
     if labels.shape != dt.shape or dt.dtype != torch.float32:
         raise ValueError("dt must be a float32 tensor of the labels' shape")
-    labels, nd, code, ext = _label_op_tensor(labels, "label_stats")
-    if max_labels is not None and int(max_labels) < 1:
-        raise ValueError(f"label_stats: max_labels must be at least 1, got {max_labels}")
-    dev = labels.device
-    z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
+    labels, code, nd, ext, _ = _input(labels, None, "label_stats")
+    _check_max_labels("label_stats", max_labels)
     if labels.numel() == 0:
-        return LabelStats(z(labels.dtype, 0), z(torch.int64, 0), z(torch.float32, 0), z(torch.int64, 0, nd),
-                          z(torch.int32, 0, nd), z(torch.int32, 0, nd))
-    labels, dt = labels.contiguous(), dt.contiguous()
-    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-
-    def call(cap, cols, n):
-        ws = _fresh_workspace("edt_hip_label_stats_workspace_bytes", code, labels.numel(), cap, device=dev)
-        _lib.check(_lib.load().edt_hip_label_stats_device(_vp(labels), code, _vp(dt), nd, *ext, cap, *map(_vp, cols), _vp(n),
-                                                          _vp(ws), ws.numel(), _stream_ptr()))
-
-    keys, counts, mx, arg, bbox = _label_table(
-        "label_stats", labels, max_labels,
-        lambda cap: [e(labels.dtype, cap), e(torch.int64, cap), e(torch.float32, cap), e(torch.int64, cap), e(torch.int32, cap, 6)],
-        call)
+        return _no_rows(LabelStats, labels, nd)
+    dt = dt.contiguous()
+    keys, counts, mx, arg, bbox = _table(
+        "label_stats", labels, code, max_labels, [(torch.int64, ()), (torch.float32, ()), (torch.int64, ()), (torch.int32, (6,))],
+        "edt_hip_label_stats_workspace_bytes",
+        lambda cap, tail: _lib.load().edt_hip_label_stats_device(_vp(labels), code, _vp(dt), nd, *ext, cap, *tail), keep=False)
     coords = []
     for extent in ext[:nd]:            # x, y, z of the flat index
         coords.append(arg % extent)
@@ -520,42 +478,39 @@ def label_moments(labels: torch.Tensor, max_labels=None) -> LabelMoments:
     ascending (signed dtypes in signed order), the voxel count, the exact raw first ``(n, ndim)`` and second ``(n, ndim, ndim)``
     moments (int64), centroid and population covariance in voxel units (float64).  The table stays on the device; the only
     host synchronisation is reading the number of labels.  ``max_labels`` and the range bound: as :func:`edt.label_moments`."""
-    labels, nd, code, ext = _label_op_tensor(labels, "label_moments")
-    if max_labels is not None and int(max_labels) < 1:
-        raise ValueError(f"label_moments: max_labels must be at least 1, got {max_labels}")
-    dev = labels.device
+    labels, code, nd, ext, _ = _input(labels, None, "label_moments")
+    _check_max_labels("label_moments", max_labels)
     if labels.numel() == 0:
-        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
-        return LabelMoments(z(labels.dtype, 0), z(torch.int64, 0), z(torch.int64, 0, nd), z(torch.int64, 0, nd, nd),
-                            z(torch.float64, 0, nd), z(torch.float64, 0, nd, nd))
+        return _no_rows(LabelMoments, labels, nd)
     _moments.check_range(labels.shape)
-    labels = labels.contiguous()
-    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-
-    def call(cap, cols, n):
-        ws = _fresh_workspace("edt_hip_label_moments_workspace_bytes", code, labels.numel(), cap, device=dev)
-        _lib.check(_lib.load().edt_hip_label_moments_device(_vp(labels), code, nd, *ext, cap, *map(_vp, cols), _vp(n), _vp(ws),
-                                                            ws.numel(), _stream_ptr()))
-
-    keys, counts, sums, centroid, central = _label_table(
-        "label_moments", labels, max_labels,
-        lambda cap: [e(labels.dtype, cap), e(torch.int64, cap), e(torch.int64, cap, 9), e(torch.float64, cap, 3), e(torch.float64, cap, 6)],
-        call)
+    keys, counts, sums, centroid, central = _table(
+        "label_moments", labels, code, max_labels, [(torch.int64, ()), (torch.int64, (9,)), (torch.float64, (3,)), (torch.float64, (6,))],
+        "edt_hip_label_moments_workspace_bytes",
+        lambda cap, tail: _lib.load().edt_hip_label_moments_device(_vp(labels), code, nd, *ext, cap, *tail), keep=False)
     return _moments.assemble(keys, counts, sums, centroid, central, nd, True)
 
 
 _workspaces: dict = {}         # query name -> {(bytes, device, stream): scratch}
 
 
-def _workspace(query, *query_args, device) -> torch.Tensor:
-    """The scratch of one library call: ``query(*query_args)`` bytes on ``device``.  One buffer per query name, byte count, device
-    and current stream (a workspace is only ever used on the stream it was allocated for; calls that need the same bytes share
-    it, whatever their shape or dtype: every call initialises what it reads).  At most 9 are kept per query name, and the one
-    cached longest ago makes room for a new one."""
+def _workspace(query, *query_args, device, keep) -> torch.Tensor:
+    """The scratch of one library call: ``query(*query_args)`` bytes on ``device``; a query that answers 0 is a ``ValueError``.
+
+    ``keep=True``: one buffer per query name, byte count, device and current stream (a workspace is only ever used on the stream
+    it was allocated for; calls that need the same bytes share it, whatever their shape or dtype: every call initialises what it
+    reads).  At most 9 are kept per query name, and the one cached longest ago makes room for a new one.
+    ``keep=False``: allocated for this call and freed with it.
+
+    Who keeps: connected_components, fill_holes, dust (on fill_holes' query), watershed, label_topology, erode / opening / closing,
+    local_thickness and medial_axis.  Who does not: feature_transform (which frees it before it reorders its planes),
+    expand_labels (and so dilate), edtsq_voxel_graph, runs, label_stats and label_moments.  The transforms have their scratch in
+    a :class:`Plan`."""
     nbytes = int(getattr(_lib.load(), query)(*query_args))
     if nbytes == 0:
         raise ValueError(f"{query}{query_args} is 0: this dtype, shape (at most 2^31 - 1 voxels for the label operations) or "
                          "flags is not served")
+    if not keep:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
     cache = _workspaces.setdefault(query, {})
     key = (nbytes, str(device), torch.cuda.current_stream(device).cuda_stream)
     if key not in cache:
@@ -565,19 +520,6 @@ def _workspace(query, *query_args, device) -> torch.Tensor:
     return cache[key]
 
 
-def _label_op_tensor(labels, who):
-    """What every label operation asks of its input: ``(labels, nd, dtype code, x-fastest extents padded to three)``."""
-    labels = as_device_tensor(labels)
-    if labels.dim() < 1 or labels.dim() > 3:
-        raise TypeError(f"{who}: 1-D, 2-D or 3-D tensors, got {labels.dim()}-D")
-    nd = labels.dim()
-    return labels, nd, dtype_code(labels.dtype), tuple(int(e) for e in labels.shape[::-1]) + (1,) * (3 - nd)
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def label_topology(labels: torch.Tensor, max_labels=None) -> LabelTopology:
     """Device-resident :func:`edt.label_topology`: one table row per distinct non-zero label in ONE sweep over ``labels``,
     nothing else is read (contract: include/edt_hip.h, "label_topology").  The named tuple ``(labels, counts, closed, interior)``
@@ -585,23 +527,13 @@ def label_topology(labels: torch.Tensor, max_labels=None) -> LabelTopology:
     tables of shape ``(n,) + (2,) * ndim`` per tensor axis.  ``euler``, ``intrinsic_volumes`` and ``surface_area`` of the result
     bring the table to the host.  The table stays on the device; the only host synchronisation is reading the number of labels.
     The scratch is cached per size and stream.  ``max_labels``: as :func:`edt.label_topology`."""
-    labels, nd, code, ext = _label_op_tensor(labels, "label_topology")
-    if max_labels is not None and int(max_labels) < 1:
-        raise ValueError(f"label_topology: max_labels must be at least 1, got {max_labels}")
-    dev = labels.device
+    labels, code, nd, ext, _ = _input(labels, None, "label_topology")
+    _check_max_labels("label_topology", max_labels)
     if labels.numel() == 0:
-        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)  # noqa: E731
-        return LabelTopology(z(labels.dtype, 0), z(torch.int64, 0), z(torch.int64, 0, *(2,) * nd), z(torch.int64, 0, *(2,) * nd))
-    labels = labels.contiguous()
-    e = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-
-    def call(cap, cols, n):
-        ws = _workspace("edt_hip_label_topology_workspace_bytes", code, labels.numel(), cap, device=dev)
-        _lib.check(_lib.load().edt_hip_label_topology_device(_vp(labels), code, nd, *ext, cap, *map(_vp, cols), _vp(n), _vp(ws),
-                                                             ws.numel(), _stream_ptr()))
-
-    keys, closed, interior = _label_table("label_topology", labels, max_labels,
-                                          lambda cap: [e(labels.dtype, cap), e(torch.int64, cap, 8), e(torch.int64, cap, 8)], call)
+        return _no_rows(LabelTopology, labels, nd)
+    keys, closed, interior = _table(
+        "label_topology", labels, code, max_labels, [(torch.int64, (8,)), (torch.int64, (8,))], "edt_hip_label_topology_workspace_bytes",
+        lambda cap, tail: _lib.load().edt_hip_label_topology_device(_vp(labels), code, nd, *ext, cap, *tail), keep=True)
     return _topology.assemble(keys, closed, interior, nd, True)
 
 
@@ -615,15 +547,13 @@ def connected_components(labels: torch.Tensor, connectivity=None, binary=False):
 
     The result composes without leaving the device: ``label_stats(out, dt)`` is then a table per OBJECT,
     ``each(out, dt)`` yields one image per object, and ``edt(out)`` is the transform of the instances."""
-    from . import _connectivity
-    labels, nd, code, ext = _label_op_tensor(labels, "connected_components")
+    labels, code, nd, ext, _ = _input(labels, None, "connected_components")
     c = _connectivity(connectivity, nd)
     out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
     if labels.numel() == 0:
         return out, torch.zeros((), dtype=torch.int64, device=labels.device)
     n = torch.empty((), dtype=torch.int64, device=labels.device)
-    labels = labels.contiguous()
-    ws = _workspace("edt_hip_components_workspace_bytes", code, nd, *ext, device=labels.device)
+    ws = _workspace("edt_hip_components_workspace_bytes", code, nd, *ext, device=labels.device, keep=True)
     _lib.check(_lib.load().edt_hip_connected_components_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, _vp(out),
                                                                _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
@@ -637,15 +567,13 @@ def fill_holes(labels: torch.Tensor, connectivity=None, binary=False):
     (4 bytes per voxel) is cached per shape and stream.
 
     ``edt(fill_holes(x)[0])`` is then the transform of the filled segmentation without a trip to the host."""
-    from . import _connectivity
-    labels, nd, code, ext = _label_op_tensor(labels, "fill_holes")
+    labels, code, nd, ext, _ = _input(labels, None, "fill_holes")
     c = _connectivity(connectivity, nd, default=1, who="fill_holes")
     if labels.numel() == 0:
         return labels.clone(), torch.zeros((), dtype=torch.int64, device=labels.device)
-    labels = labels.contiguous()
     out = torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
     n = torch.empty((), dtype=torch.int64, device=labels.device)
-    ws = _workspace("edt_hip_fill_holes_workspace_bytes", code, nd, *ext, device=labels.device)
+    ws = _workspace("edt_hip_fill_holes_workspace_bytes", code, nd, *ext, device=labels.device, keep=True)
     _lib.check(_lib.load().edt_hip_fill_holes_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, _vp(out), _vp(n),
                                                      _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
@@ -661,18 +589,17 @@ def dust(labels: torch.Tensor, threshold, connectivity=None, binary=False, inver
     and stream, together with fill_holes'.
 
     ``edt(fill_holes(dust(x, t)[0])[0])`` is then the transform of the cleaned segmentation without a trip to the host."""
-    from . import _connectivity, _dust_bounds
-    labels, nd, code, ext = _label_op_tensor(labels, "dust")
+    raw = as_device_tensor(labels)
+    labels, code, nd, ext, _ = _input(raw, None, "dust")
     lo, hi = _dust_bounds(threshold)
     c = _connectivity(connectivity, nd, who="dust")
-    if in_place and not labels.is_contiguous():
+    if in_place and not raw.is_contiguous():
         raise ValueError("dust: in_place needs a contiguous tensor")
     if labels.numel() == 0:
         return (labels if in_place else labels.clone()), torch.zeros(3, dtype=torch.int64, device=labels.device)
-    labels = labels.contiguous()
     out = labels if in_place else torch.empty(labels.shape, dtype=labels.dtype, device=labels.device)
     counts = torch.empty(3, dtype=torch.int64, device=labels.device)
-    ws = _workspace("edt_hip_fill_holes_workspace_bytes", code, nd, *ext, device=labels.device)
+    ws = _workspace("edt_hip_fill_holes_workspace_bytes", code, nd, *ext, device=labels.device, keep=True)
     _lib.check(_lib.load().edt_hip_dust_device(_vp(labels), code, nd, *ext, c, 1 if binary else 0, lo, hi, 1 if invert else 0,
                                                _vp(out), _vp(counts), _vp(ws), ws.numel(), _stream_ptr()))
     return out, counts
@@ -695,8 +622,7 @@ def watershed(labels: torch.Tensor, field: torch.Tensor = None, min_saliency=0.0
     back and nothing waits.  The scratch (4 bytes per voxel, the size of fill_holes') is cached per shape and stream.
 
     ``label_stats(watershed(x)[0], dt)`` is then a table per SPLIT object, without leaving the device."""
-    from . import _connectivity, _min_saliency
-    labels, nd, code, ext = _label_op_tensor(labels, "watershed")
+    labels, code, nd, ext, _ = _input(labels, None, "watershed")
     c = _connectivity(connectivity, nd, who="watershed")
     h = _min_saliency(min_saliency)
     if field is not None:
@@ -706,12 +632,11 @@ def watershed(labels: torch.Tensor, field: torch.Tensor = None, min_saliency=0.0
     out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
     if labels.numel() == 0:
         return out, torch.zeros((), dtype=torch.int64, device=labels.device)
-    labels = labels.contiguous()
     if field is None:
         field = edt(labels != 0 if binary and labels.dtype != torch.bool else labels, anisotropy, black_border)
     field = field.contiguous()
     n = torch.empty((), dtype=torch.int64, device=labels.device)
-    ws = _workspace("edt_hip_watershed_workspace_bytes", code, nd, *ext, device=labels.device)
+    ws = _workspace("edt_hip_watershed_workspace_bytes", code, nd, *ext, device=labels.device, keep=True)
     _lib.check(_lib.load().edt_hip_watershed_device(_vp(labels), code, nd, *ext, _vp(field), c, 1 if binary else 0, h, _vp(out),
                                                     _vp(n), _vp(ws), ws.numel(), _stream_ptr()))
     return out, n
@@ -725,21 +650,19 @@ def _morph_select(code, values, field, radius, rule, out=None, mask=None, guard=
 
 
 def _morph_input(labels, radius, anisotropy, who, in_place=False, inf_allowed=False):
-    from . import _morph_radius
     raw = as_device_tensor(labels)
     r = _morph_radius(radius, who, inf_allowed)
     if in_place and not raw.is_contiguous():
         raise ValueError(f"{who}: in_place needs a contiguous tensor")
-    labels, nd, ext, w = _ft_tensor(raw, anisotropy, who)
-    return labels, nd, dtype_code(labels.dtype), ext, w, r
+    return (*_input(raw, anisotropy, who), r)
 
 
 def _morphology(who, op, labels, radius, anisotropy, flags=0, in_place=False):
     """One call of edt_hip_morphology_device on the current stream, on the cached workspace of its size."""
-    labels, nd, code, ext, w, r = _morph_input(labels, radius, anisotropy, who, in_place)
+    labels, code, nd, ext, w, r = _morph_input(labels, radius, anisotropy, who, in_place)
     if labels.numel() == 0:
         return labels if in_place else labels.clone()
-    ws = _workspace("edt_hip_morphology_workspace_bytes", code, nd, *ext, op, flags, device=labels.device)
+    ws = _workspace("edt_hip_morphology_workspace_bytes", code, nd, *ext, op, flags, device=labels.device, keep=True)
     out = labels if in_place else torch.empty_like(labels)
     _lib.check(_lib.load().edt_hip_morphology_device(_vp(labels), code, nd, *ext, *w, op, r, flags, _vp(out), _vp(ws), ws.numel(),
                                                      _stream_ptr()))
@@ -750,13 +673,12 @@ def erode(labels: torch.Tensor, radius=1.0, anisotropy=None, black_border=False,
     """:func:`edt.erode` on a device array (semantics of a C-ordered array; anisotropy in tensor axis order; contract:
     include/edt_hip.h, "morphology"): one transform and one streaming select on the current stream, nothing read back.
     ``in_place=True`` writes the result into the (contiguous) input tensor and returns it."""
-    from . import _morph_flags
     return _morphology("erode", _lib.MORPH_ERODE, labels, radius, anisotropy, _morph_flags(black_border, binary), in_place)
 
 
 def dilate(labels: torch.Tensor, radius=1.0, anisotropy=None) -> torch.Tensor:
     """:func:`edt.dilate` on a device array: exactly :func:`expand_labels`."""
-    labels, nd, code, ext, w, r = _morph_input(labels, radius, anisotropy, "dilate", inf_allowed=True)
+    labels, *_, r = _morph_input(labels, radius, anisotropy, "dilate", inf_allowed=True)
     return expand_labels(labels, r, anisotropy)
 
 
@@ -764,7 +686,6 @@ def opening(labels: torch.Tensor, radius=1.0, anisotropy=None, black_border=Fals
     """:func:`edt.opening` on a device array: the transform of the labels, the mask of what the erosion removes, its
     binary transform, and the select of the voxels within ``radius`` of what survived -- two transforms and two streaming
     kernels on the current stream.  ``in_place=True`` writes the result into the (contiguous) input tensor and returns it."""
-    from . import _morph_flags
     return _morphology("opening", _lib.MORPH_OPEN, labels, radius, anisotropy, _morph_flags(black_border, binary), in_place)
 
 
@@ -783,18 +704,16 @@ def local_thickness(labels: torch.Tensor, radii=None, anisotropy=None, black_bor
     ``radii`` the call only enqueues kernels on the current stream -- nothing is read back, and it can be captured into a graph.
     ``radii=None`` SYNCHRONISES once: the largest finite squared distance (4 bytes) is read back to build the ladder; on a
     stream that is being captured it is refused (``EdtHipError``)."""
-    from . import ThicknessSizes, _ladder_room, _morph_flags, _thickness_radii
     raw = as_device_tensor(labels)
     r = None if radii is None else _thickness_radii(radii)
-    labels, nd, ext, w = _ft_tensor(raw, anisotropy, "local_thickness")
-    code = dtype_code(labels.dtype)
+    labels, code, nd, ext, w = _input(raw, anisotropy, "local_thickness")
     if labels.numel() == 0:
         T = torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)
         used = np.zeros(0, dtype=np.float64) if r is None else r
         return (T, ThicknessSizes(used, torch.zeros(used.size, dtype=torch.int64, device=labels.device))) if return_sizes else T
     step, room = (0.0, r.size) if r is not None else _ladder_room(ext[:nd], w[:nd])
     flags = _morph_flags(black_border, binary)
-    ws = _workspace("edt_hip_local_thickness_workspace_bytes", code, nd, *ext, flags, device=labels.device)
+    ws = _workspace("edt_hip_local_thickness_workspace_bytes", code, nd, *ext, flags, device=labels.device, keep=True)
     T = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
     sizes = torch.empty(room, dtype=torch.int64, device=labels.device)
     n = ctypes.c_int64(0)
@@ -815,16 +734,15 @@ def medial_axis(labels: torch.Tensor, gamma=None, min_angle=0.0, anisotropy=None
     read back.  The workspace is cached by its size and stream: a second call of one shape allocates only what it returns.
     Returns a new tensor of the labels' dtype and shape; with ``return_distance=True`` the pair ``(axis, distance)``, distance
     float32."""
-    from . import _medial_gamma, _medial_ratio, _morph_flags
     raw = as_device_tensor(labels)
     ratio = _medial_ratio(min_angle)
-    labels, nd, ext, w = _ft_tensor(raw, anisotropy, "medial_axis")
-    code = dtype_code(labels.dtype)
+    labels, code, nd, ext, w = _input(raw, anisotropy, "medial_axis")
     g = _medial_gamma(gamma, w[:nd])
     if labels.numel() == 0:
         return (labels.clone(), torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)) if return_distance else labels.clone()
     flags = _morph_flags(black_border, binary)
-    ws = _workspace("edt_hip_medial_axis_workspace_bytes", code, nd, *ext, flags, 1 if return_distance else 0, device=labels.device)
+    ws = _workspace("edt_hip_medial_axis_workspace_bytes", code, nd, *ext, flags, 1 if return_distance else 0, device=labels.device,
+                    keep=True)
     out = torch.empty_like(labels)
     radius = torch.empty(labels.shape, dtype=torch.float32, device=labels.device) if return_distance else None
     _lib.check(_lib.load().edt_hip_medial_axis_device(
