@@ -217,6 +217,23 @@ static int run_on_current_device(const void *labels, int dtype, int ndim, int64_
   return rc != EDT_OK ? rc : st.down(output, kOut, obytes);
 }
 
+// first touch of the whole output, then the transform Z-sharded over `devices` (edt_multi.hip)
+static int run_on_devices(const void *labels, int dtype, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz, int flags,
+                          float *output, const int *devices, int n_devices) {
+  Prefault touch;
+  touch.start(output, (size_t)(sx * sy * sz) * sizeof(float));
+  touch.join();
+  return run_multi(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devices, n_devices);
+}
+
+// every ordinal of a device list names a device of this host (the caller has refused a bad list in its own words)
+static int check_device_ordinals(const int *devices, int n_devices) {
+  const int have = edt_hip_device_count();
+  for (int i = 0; i < n_devices; ++i)
+    if (devices[i] < 0 || devices[i] >= have) { set_error("device ordinal out of range"); return EDT_ERR_BAD_ARG; }
+  return EDT_OK;
+}
+
 static int run_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t sy, int64_t sz,
                     float wx, float wy, float wz, int flags, float *output) {
   float *const w[3] = {&wx, &wy, &wz};
@@ -233,12 +250,8 @@ static int run_host(const void *labels, int dtype, int ndim, int64_t sx, int64_t
   }
   const bool shardable = ndim == 3 && !env_force_generic() &&
                          !(flags & (EDT_FLAG_FORCE_GENERIC | EDT_FLAG_BATCH_2D | EDT_FLAG_BINARY_YZ)) && devs.size() >= 2;
-  if (shardable && multi_supported(dtype, sx, sy, sz, (int)devs.size())) {
-    Prefault touch;
-    touch.start(output, (size_t)(sx * sy * sz) * sizeof(float));
-    touch.join();
-    return run_multi(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devs.data(), (int)devs.size());
-  }
+  if (shardable && multi_supported(dtype, sx, sy, sz, (int)devs.size()))
+    return run_on_devices(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devs.data(), (int)devs.size());
   // a one-entry list, or a call the slab-record form does not cover: the FIRST listed device does it alone
   if (shardable) {
     static std::atomic<bool> said{false};
@@ -550,9 +563,7 @@ int edt_hip_edt2dsq_batch(const void *labels, int dtype, int64_t sx, int64_t sy,
 
 int edt_hip_set_devices(const int *devices, int n_devices) {
   if (n_devices < 0 || (n_devices > 0 && !devices)) { set_error("bad device list"); return EDT_ERR_BAD_ARG; }
-  const int have = edt_hip_device_count();
-  for (int i = 0; i < n_devices; ++i)
-    if (devices[i] < 0 || devices[i] >= have) { set_error("device ordinal out of range"); return EDT_ERR_BAD_ARG; }
+  if (const int rc = check_device_ordinals(devices, n_devices)) return rc;
   std::lock_guard<std::mutex> lock(g_devices_mutex);
   g_devices.assign(devices, devices + n_devices);
   return EDT_OK;
@@ -566,10 +577,7 @@ int edt_hip_edt3dsq_multi(const void *labels, int dtype, int64_t sx, int64_t sy,
   if ((rc = check_voxel_sizes(3, wx, wy, wz)) != EDT_OK) return rc;
   if (sx == 0 || sy == 0 || sz == 0) return EDT_OK;
   if (!labels || !output || !devices || n_devices < 1) { set_error("null pointer / empty device list"); return EDT_ERR_BAD_ARG; }
-  if ((rc = require_device()) != EDT_OK) return rc;
-  const int have = edt_hip_device_count();
-  for (int i = 0; i < n_devices; ++i)
-    if (devices[i] < 0 || devices[i] >= have) { set_error("device ordinal out of range"); return EDT_ERR_BAD_ARG; }
+  if ((rc = require_device()) != EDT_OK || (rc = check_device_ordinals(devices, n_devices)) != EDT_OK) return rc;
   const int flags = (black_border ? EDT_FLAG_BLACK_BORDER : 0) | (take_sqrt ? EDT_FLAG_SQRT : 0);
   if (n_devices >= 2 && !multi_supported(dtype, sx, sy, sz, n_devices)) {
     set_error("this volume cannot be Z-sharded over " + std::to_string(n_devices) + " devices (slab records: sx, sy "
@@ -581,10 +589,7 @@ int edt_hip_edt3dsq_multi(const void *labels, int dtype, int64_t sx, int64_t sy,
     if (on_that_device.rc != EDT_OK) return on_that_device.rc;
     return run_on_current_device(labels, dtype, 3, sx, sy, sz, wx, wy, wz, flags, output);
   }
-  Prefault touch;
-  touch.start(output, (size_t)(sx * sy * sz) * sizeof(float));
-  touch.join();
-  return run_multi(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devices, n_devices);
+  return run_on_devices(labels, dtype, sx, sy, sz, wx, wy, wz, flags, output, devices, n_devices);
 }
 
 int edt_hip_multi_supported(int dtype, int64_t sx, int64_t sy, int64_t sz, int n_devices) {

@@ -36,6 +36,7 @@ from __future__ import annotations
 
 import ctypes
 import json
+import os
 import time
 
 import numpy as np
@@ -95,33 +96,38 @@ class HipOps:
     def record_floats(self, sx, ylen):
         return int(self.lib.edt_hip_shard_record_floats(sx, ylen))
 
+    def _records_tail(self, code, sx, sy, sz, device, slot=0):
+        """How every record phase's argument list ends: the workspace of `slot` for these extents, its size, the stream."""
+        ws = self._workspace(self.lib.edt_hip_shard_records_workspace_bytes(code, sx, sy, sz), device, slot)
+        return ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream()
+
+    def _xy_records_args(self, labels, halo, code, y_splits, blocks, slot):
+        """The arguments the two XY record phases share, as ctypes: (labels, halo, dtype code, extents), (parts, splits, block
+        pointers) and the tail; their voxel sizes, flags and counter go in between."""
+        szl, sy, sx = labels.shape
+        head = (ctypes.c_void_p(labels.data_ptr()), ctypes.c_void_p(halo.data_ptr()) if halo is not None else None,
+                code, sx, sy, szl)
+        parts = (len(blocks), (ctypes.c_int64 * len(y_splits))(*y_splits),
+                 (ctypes.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks]))
+        return head, parts, self._records_tail(code, sx, sy, szl, labels.device, slot)
+
     def xy_records(self, labels, halo, code, weights, flags, y_splits, blocks, slot=0):
         """X and Y passes of a z-chunk; block h receives chunk-many records of destination h."""
-        szl, sy, sx = labels.shape
-        ws = self._workspace(self.lib.edt_hip_shard_records_workspace_bytes(code, sx, sy, szl), labels.device,
-                             slot)
-        splits = (ctypes.c_int64 * len(y_splits))(*y_splits)
-        ptrs = (ctypes.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
-        _lib.check(self.lib.edt_hip_shard_xy_records_device(
-            ctypes.c_void_p(labels.data_ptr()),
-            ctypes.c_void_p(halo.data_ptr()) if halo is not None else None, code, sx, sy, szl,
-            weights[0], weights[1], flags, len(blocks), splits, ptrs, ctypes.c_void_p(ws.data_ptr()),
-            ws.numel(), self._stream()))
+        head, parts, tail = self._xy_records_args(labels, halo, code, y_splits, blocks, slot)
+        _lib.check(self.lib.edt_hip_shard_xy_records_device(*head, weights[0], weights[1], flags, *parts, *tail))
 
     def z_records(self, records, sx, syl, wz, flags, wxy=None):
         """Z pass in place over the gathered (sz, record_floats) buffer.  wxy = (wx, wy) of the XY phase that produced the
         records, where the caller knows them (an argument of THIS call, never remembered): the Z pass may then run on the
         integer column kernel and form fp32 candidates -- the same bits either way (edt_hip.h)."""
         sz = records.shape[0]
-        ws = self._workspace(self.lib.edt_hip_shard_records_workspace_bytes(_lib.U8, sx, syl, sz), records.device)
+        tail = self._records_tail(_lib.U8, sx, syl, sz, records.device)
         if wxy is not None:
             _lib.check(self.lib.edt_hip_shard_z_records_device_w(
-                ctypes.c_void_p(records.data_ptr()), sx, syl, sz, wxy[0], wxy[1], wz, flags, ctypes.c_void_p(ws.data_ptr()),
-                ws.numel(), self._stream()))
+                ctypes.c_void_p(records.data_ptr()), sx, syl, sz, wxy[0], wxy[1], wz, flags, *tail))
         else:
             _lib.check(self.lib.edt_hip_shard_z_records_device_ex(
-                ctypes.c_void_p(records.data_ptr()), sx, syl, sz, wz, 0.0, flags, ctypes.c_void_p(ws.data_ptr()),
-                ws.numel(), self._stream()))
+                ctypes.c_void_p(records.data_ptr()), sx, syl, sz, wz, 0.0, flags, *tail))
 
     # -- slab records of 16-bit values (edt_hip.h): 2.25 bytes per voxel where the integer column kernel takes both passes --
     def records16_supported(self, code, sx, sy, sz, weights):
@@ -133,23 +139,16 @@ class HipOps:
     def xy_records16(self, labels, halo, code, weights, flags, y_splits, blocks, refused, slot=0):
         """X and Y passes of a z-chunk into records of 16-bit rows (int32 tensors of record16_words columns); `refused`
         (int32[1], zeroed by the caller) counts the tiles that have no 16-bit form."""
-        szl, sy, sx = labels.shape
-        ws = self._workspace(self.lib.edt_hip_shard_records_workspace_bytes(code, sx, sy, szl), labels.device, slot)
-        splits = (ctypes.c_int64 * len(y_splits))(*y_splits)
-        ptrs = (ctypes.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
+        head, parts, tail = self._xy_records_args(labels, halo, code, y_splits, blocks, slot)
         _lib.check(self.lib.edt_hip_shard_xy_records16_device(
-            ctypes.c_void_p(labels.data_ptr()),
-            ctypes.c_void_p(halo.data_ptr()) if halo is not None else None, code, sx, sy, szl,
-            weights[0], weights[1], weights[2], flags, len(blocks), splits, ptrs, ctypes.c_void_p(refused.data_ptr()),
-            ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
+            *head, weights[0], weights[1], weights[2], flags, *parts, ctypes.c_void_p(refused.data_ptr()), *tail))
 
     def z_records16(self, records, out, weights, flags):
         """Z pass over the gathered (sz, record16_words) records into the dense (sz, syl, sx) fp32 tensor `out`."""
         sz, syl, sx = out.shape
-        ws = self._workspace(self.lib.edt_hip_shard_records_workspace_bytes(_lib.U8, sx, syl, sz), records.device)
         _lib.check(self.lib.edt_hip_shard_z_records16_device(
             ctypes.c_void_p(records.data_ptr()), ctypes.c_void_p(out.data_ptr()), sx, syl, sz, weights[0], weights[1],
-            weights[2], flags, ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
+            weights[2], flags, *self._records_tail(_lib.U8, sx, syl, sz, records.device)))
 
     def z(self, partial, zflags, wz, flags, wxy=None):
         sz, syl, sx = partial.shape
@@ -192,8 +191,7 @@ class ShardedEDT:
         # records16: None = 16-bit records whenever the extents and the voxel sizes of a run() allow them (edt_hip.h; a run
         # that meets a tile without a 16-bit form is repeated with fp32 records and the plan stays on those), False = never
         # (EDT_SHARD_RECORDS16=0 likewise).  `last_records16` says what the last run() used.
-        import os as _os
-        self._allow16 = records16 is not False and _os.environ.get("EDT_SHARD_RECORDS16", "1") != "0"
+        self._allow16 = records16 is not False and os.environ.get("EDT_SHARD_RECORDS16", "1") != "0"
         self.last_records16 = False
         self.fallbacks16 = 0
         # After a step that had to be repeated with fp32 records the plan stays on those for `_backoff16` steps, then tries
@@ -204,13 +202,10 @@ class ShardedEDT:
         self.retry16 = True
         self._backoff16 = 0      # fp32 steps still to run before the next 16-bit attempt
         self._backoff16_next = 8
-        self._dst16 = None
-        self._out16 = None
         self._refused = None
         self._refused_host = None
         self.reuse_output = bool(reuse_output)
-        self._dst = None
-        self._halo_buf = None
+        self._cache = {}         # tensors kept between calls (_cached): the halo, the send blocks, the receive buffers
         self.sx, self.sy, self.sz = (int(e) for e in extents_xyz)
         self.code = code
         self.group = group
@@ -230,12 +225,10 @@ class ShardedEDT:
         if self.records:
             # y is cut at multiples of 32 rows: a bit word never straddles two ranks
             self.yparts = [(32 * a, min(32 * b, self.sy)) for a, b in balanced_partition(words, self.world)]
-            import os
             if chunks is None and os.environ.get("EDT_SHARD_CHUNKS"):
                 chunks = int(os.environ["EDT_SHARD_CHUNKS"])
             want = chunks if chunks is not None else (4 if self.world > 1 else 1)
             self.nchunks = max(1, min(int(want), min(e - s for s, e in self.zparts)))
-            self._send = {}
             self._streams = None
             self._nstreams = int(os.environ.get("EDT_SHARD_STREAMS", "2"))
             # how a chunk travels: "alltoall" = one dist.all_to_all per chunk (RCCL), "p2p" = a batch
@@ -253,6 +246,16 @@ class ShardedEDT:
 
     def local_y(self):
         return self.yparts[self.rank]
+
+    def _cached(self, key, shape, dtype, device, keep=True):
+        """The tensor kept under `key` between calls, allocated anew when its shape, dtype or device are not these.
+        keep=False: a fresh tensor that is not kept (what run() hands out without `reuse_output`)."""
+        t = self._cache.get(key) if keep else None
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device:
+            t = torch.empty(tuple(shape), dtype=dtype, device=device)
+            if keep:
+                self._cache[key] = t
+        return t
 
     def _global_rank(self, r):
         return r if self.group is None else dist.get_global_rank(self.group, r)
@@ -282,9 +285,7 @@ class ShardedEDT:
         if self.rank + 1 < self.world:
             sends.append((labels[-1], self.rank + 1))
         if self.rank > 0:
-            halo = self._halo_buf
-            if halo is None or halo.shape != labels[0].shape or halo.dtype != labels.dtype or halo.device != labels.device:
-                halo = self._halo_buf = torch.empty_like(labels[0])
+            halo = self._cached("halo", labels[0].shape, labels.dtype, labels.device)
             recvs.append((halo, self.rank - 1))
         return halo, self._p2p(sends, recvs)
 
@@ -373,20 +374,11 @@ class ShardedEDT:
         have been enqueued (nothing of it is needed before the last chunk; the host reaches its first launch sooner)."""
         zs, ze = self.local_z()
         ys, ye = self.local_y()
-        if use16:
-            rec = [self.ops.record16_words(self.sx, b - a) for a, b in self.yparts]
-            rdtype = torch.int32
-        else:
-            rec = [self.ops.record_floats(self.sx, b - a) for a, b in self.yparts]
-            rdtype = torch.float32
+        words = self.ops.record16_words if use16 else self.ops.record_floats
+        rec = [words(self.sx, b - a) for a, b in self.yparts]
+        rdtype = torch.int32 if use16 else torch.float32
         y_splits = [a for a, _ in self.yparts] + [self.sy]
-        dst = (self._dst16 if use16 else self._dst) if self.reuse_output else None
-        if dst is None or tuple(dst.shape) != (self.sz, rec[self.rank]) or dst.device != labels.device:
-            dst = torch.empty((self.sz, rec[self.rank]), dtype=rdtype, device=labels.device)
-            if self.reuse_output and use16:
-                self._dst16 = dst
-            elif self.reuse_output:
-                self._dst = dst
+        dst = self._cached(("dst", use16), (self.sz, rec[self.rank]), rdtype, labels.device, keep=self.reuse_output)
         if use16:
             if self._refused is None or self._refused.device != labels.device:
                 self._refused = torch.zeros(1, dtype=torch.int32, device=labels.device)
@@ -443,11 +435,7 @@ class ShardedEDT:
         if timed:
             self._ev[1].record()
         if use16:
-            out = self._out16 if self.reuse_output else None
-            if out is None or tuple(out.shape) != (self.sz, ye - ys, self.sx) or out.device != labels.device:
-                out = torch.empty((self.sz, ye - ys, self.sx), dtype=torch.float32, device=labels.device)
-                if self.reuse_output:
-                    self._out16 = out
+            out = self._cached("out16", (self.sz, ye - ys, self.sx), torch.float32, labels.device, keep=self.reuse_output)
             self.ops.z_records16(dst, out, w, flags | (_lib.FLAG_SQRT if sqrt else 0))
             self._last_halo = halo
             if self._agree_finish(agreed) != 0:
@@ -494,11 +482,7 @@ class ShardedEDT:
             if h == self.rank:
                 blocks.append(dst[c0:c1])  # own part: straight into the receive buffer
                 continue
-            key = (k, h, use16)
-            buf = self._send.get(key)
-            if buf is None or buf.shape != (c1 - c0, rec[h]) or buf.device != labels.device:
-                buf = self._send[key] = torch.empty((c1 - c0, rec[h]), dtype=dst.dtype, device=labels.device)
-            blocks.append(buf)
+            blocks.append(self._cached(("send", k, h, use16), (c1 - c0, rec[h]), dst.dtype, labels.device))
         kw = {} if slot is None else {"slot": slot}
         if use16:
             self.ops.xy_records16(labels[c0 - zs:c1 - zs], halo, self.code, w, flags, y_splits, blocks, self._refused, **kw)

@@ -132,7 +132,8 @@ def test_uneven_1024_world8_virtual_ranks_against_compiled_reference(edt_gpu, or
     """sz % 8 != 0 and sy % 8 != 0 at cfg4 size: ceil-sized leading slabs, y cut at multiples of 32 rows."""
     import torch
     from edt import _lib
-    from edt.distributed import HipOps, balanced_partition
+    from edt.distributed import HipOps
+    from virtual_ranks import record_phases
 
     shape = (1024, 1000, 1016)
     sx, sy, sz = shape
@@ -146,50 +147,15 @@ def test_uneven_1024_world8_virtual_ranks_against_compiled_reference(edt_gpu, or
     assert ops.records_supported(_lib.U32, sx, sy, sz)
     t = torch.from_numpy(np.ascontiguousarray(lab.T).view(np.int32)).to(dev)  # (sz, sy, sx), x fastest
     del lab
-    words = -(-sy // 32)
-    zparts = balanced_partition(sz, world)
-    yparts = [(32 * a, min(32 * b, sy)) for a, b in balanced_partition(words, world)]
-    y_splits = [a for a, _ in yparts] + [sy]
-    rec = [ops.record_floats(sx, b - a) for a, b in yparts]
-    dst = [torch.full((sz, rec[h]), float("nan"), dtype=torch.float32, device=dev) for h in range(world)]
-    for r, (zs, ze) in enumerate(zparts):
-        halo = t[zs - 1] if r > 0 else None  # the previous rank's last slice
-        for c0, c1 in balanced_partition(ze - zs, chunks):
-            blocks = [dst[h][zs + c0:zs + c1] if h == r else
-                      torch.empty((c1 - c0, rec[h]), dtype=torch.float32, device=dev) for h in range(world)]
-            ops.xy_records(t[zs + c0:zs + c1], halo, _lib.U32, an, 0, y_splits, blocks)
-            for h in range(world):
-                if h != r:
-                    dst[h][zs + c0:zs + c1].copy_(blocks[h])  # the exchange
-            halo = t[zs + c1 - 1]
-    got = np.empty((sz, sy, sx), dtype=np.float32)
-    for h, (ys, ye) in enumerate(yparts):
-        ops.z_records(dst[h], sx, ye - ys, an[2], 0, wxy=(an[0], an[1]))
-        got[:, ys:ye, :] = dst[h][:, :(ye - ys) * sx].reshape(sz, ye - ys, sx).cpu().numpy()
-    assert np.array_equal(got.T, want)
-    del dst
+    got, _ = record_phases(ops, t, _lib.U32, world, chunks, an, 0, fill=float("nan"))
+    assert np.array_equal(got.cpu().numpy().T, want)
+    del got
     # the same ranks with records of 16-bit rows (2.25 bytes per voxel: what an 8-GPU run of this volume exchanges)
     assert ops.records16_supported(_lib.U32, sx, sy, sz, an)
-    rec16 = [ops.record16_words(sx, b - a) for a, b in yparts]
-    dst16 = [torch.full((sz, rec16[h]), -1, dtype=torch.int32, device=dev) for h in range(world)]
-    refused = torch.zeros(1, dtype=torch.int32, device=dev)
-    for r, (zs, ze) in enumerate(zparts):
-        halo = t[zs - 1] if r > 0 else None
-        for c0, c1 in balanced_partition(ze - zs, chunks):
-            blocks = [dst16[h][zs + c0:zs + c1] if h == r else
-                      torch.empty((c1 - c0, rec16[h]), dtype=torch.int32, device=dev) for h in range(world)]
-            ops.xy_records16(t[zs + c0:zs + c1], halo, _lib.U32, an, 0, y_splits, blocks, refused)
-            for h in range(world):
-                if h != r:
-                    dst16[h][zs + c0:zs + c1].copy_(blocks[h])
-            halo = t[zs + c1 - 1]
+    got, refused = record_phases(ops, t, _lib.U32, world, chunks, an, 0, rows16=True, fill=-1)
     del t
-    assert int(refused.item()) == 0
-    for h, (ys, ye) in enumerate(yparts):
-        out = torch.empty((sz, ye - ys, sx), dtype=torch.float32, device=dev)
-        ops.z_records16(dst16[h], out, an, 0)
-        got[:, ys:ye, :] = out.cpu().numpy()
-    assert np.array_equal(got.T, want)
+    assert refused == 0
+    assert np.array_equal(got.cpu().numpy().T, want)
 
 
 def test_two_threads_two_streams_stay_bit_exact(edt_gpu, oracle_port):

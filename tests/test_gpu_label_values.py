@@ -187,6 +187,7 @@ def test_shard_phases_as_virtual_ranks(edt_gpu, oracle_port):
     import torch
     from edt import _lib
     from edt.distributed import HipOps, balanced_partition
+    from virtual_ranks import flag_phases, record_phases
     dev = torch.device("cuda", 0)
     ops = HipOps()
     rng = np.random.default_rng(1500)
@@ -196,21 +197,9 @@ def test_shard_phases_as_virtual_ranks(edt_gpu, oracle_port):
         shape = (96, 80, 72)
         lab = _pair_across_z(dt, shape, 36, rng)
         t = _as_tensor(lab, dev)
-        sx, sy, sz = shape
-        zparts, yparts = balanced_partition(sz, world), balanced_partition(sy, world)
-        assert zparts[1][0] == 36
+        assert balanced_partition(shape[2], world)[1][0] == 36
         for an, bb in (((6.0, 6.0, 30.0), True), ((1.0, 1.5, 0.5), False)):
-            flags = _lib.FLAG_BLACK_BORDER if bb else 0
-            partial, zflags = [], []
-            for r, (zs, ze) in enumerate(zparts):
-                halo = t[zs - 1].contiguous() if r > 0 else None
-                p, f = ops.xy(t[zs:ze].contiguous(), halo, code, an, flags)
-                partial.append(p)
-                zflags.append(f)
-            partial, zflags = torch.cat(partial, 0), torch.cat(zflags, 0)
-            outs = [ops.z(partial[:, ys:ye, :].contiguous(), zflags[:, ys:ye, :].contiguous(), an[2], flags,
-                          wxy=(an[0], an[1])).clone() for ys, ye in yparts]
-            got = torch.cat(outs, 1).cpu().numpy().T
+            got = flag_phases(ops, t, code, world, an, _lib.FLAG_BLACK_BORDER if bb else 0).cpu().numpy().T
             want = oracle_port.edtsq(lab, an, bb)
             assert same(got, want), (dt, an, bb, explain(got, want))
 
@@ -219,31 +208,12 @@ def test_shard_phases_as_virtual_ranks(edt_gpu, oracle_port):
         sx, sy, sz = shape
         lab = _pair_across_z(dt, shape, 50, rng)
         t = _as_tensor(lab, dev)
-        zparts = balanced_partition(sz, world)
-        assert zparts[1][0] == 50
-        words = -(-sy // 32)
-        yparts = [(32 * a, min(32 * b, sy)) for a, b in balanced_partition(words, world)]
-        y_splits = [a for a, _ in yparts] + [sy]
-        rec = [ops.record16_words(sx, b - a) for a, b in yparts]
+        assert balanced_partition(sz, world)[1][0] == 50
         for an, bb in (((1.0, 1.0, 1.0), True), ((2.0, 1.0, 3.0), True)):
             assert ops.records16_supported(code, sx, sy, sz, an)
-            flags = _lib.FLAG_BLACK_BORDER if bb else 0
-            refused = torch.zeros(1, dtype=torch.int32, device=dev)
-            dst = [torch.full((sz, rec[h]), -1, dtype=torch.int32, device=dev) for h in range(world)]
-            for r, (zs, ze) in enumerate(zparts):
-                halo = t[zs - 1] if r > 0 else None
-                blocks = [dst[h][zs:ze] if h == r else torch.empty((ze - zs, rec[h]), dtype=torch.int32, device=dev)
-                          for h in range(world)]
-                ops.xy_records16(t[zs:ze], halo, code, an, flags, y_splits, blocks, refused)
-                for h in range(world):
-                    if h != r:
-                        dst[h][zs:ze].copy_(blocks[h])
-            outs = []
-            for h, (ys, ye) in enumerate(yparts):
-                out = torch.full((sz, ye - ys, sx), float("nan"), dtype=torch.float32, device=dev)
-                ops.z_records16(dst[h], out, an, flags)
-                outs.append(out)
-            got = torch.cat(outs, 1).cpu().numpy().T
+            got, refused = record_phases(ops, t, code, world, 1, an, _lib.FLAG_BLACK_BORDER if bb else 0, rows16=True, fill=-1)
+            assert refused == 0   # (the rows of a refused tile are unspecified: nothing to compare)
+            got = got.cpu().numpy().T
             want = oracle_port.edtsq(lab, an, bb)
             assert same(got, want), (dt, "records16", an, bb, explain(got, want))
 

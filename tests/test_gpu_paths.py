@@ -69,7 +69,8 @@ def test_axes_beyond_the_wave_kernels(edt_gpu, oracle_port):
 def test_shard_phases_as_virtual_ranks(edt_gpu, oracle_port, world, shape):
     import torch
     from edt import _lib
-    from edt.distributed import HipOps, balanced_partition
+    from edt.distributed import HipOps
+    from virtual_ranks import flag_phases
 
     sx, sy, sz = shape
     if sz < world or sy < world:
@@ -78,25 +79,10 @@ def test_shard_phases_as_virtual_ranks(edt_gpu, oracle_port, world, shape):
     ops = HipOps()
     lab = voronoi_labels(shape, nseeds=40, seed=world, upsample=4, membrane=0.04)
     t = torch.from_numpy(np.ascontiguousarray(lab.T).view(np.int32)).to(dev)  # (sz, sy, sx), x fastest
-    zparts, yparts = balanced_partition(sz, world), balanced_partition(sy, world)
     # (the third: voxel sizes whose multiples are not exact in fp32, the Z phase told what the XY phase guarantees --
     # edt_hip_shard_z_device_ex's field_floor, fp32 fma candidates)
     for an, bb, sqrt in (((6.0, 6.0, 30.0), True, False), ((1.0, 1.5, 0.5), False, True), ((1.1, 0.7, 1.3), False, False)):
-        flags = _lib.FLAG_BLACK_BORDER if bb else 0
-        partial, zflags = [], []
-        for r, (zs, ze) in enumerate(zparts):
-            halo = t[zs - 1].contiguous() if r > 0 else None  # the previous rank's last slice
-            p, f = ops.xy(t[zs:ze].contiguous(), halo, _lib.U32, an, flags)
-            partial.append(p)
-            zflags.append(f)
-        torch.cuda.synchronize()
-        partial, zflags = torch.cat(partial, 0), torch.cat(zflags, 0)
-        outs = []
-        for (ys, ye) in yparts:  # the all-to-all: rank h receives (all z, its y range)
-            o = ops.z(partial[:, ys:ye, :].contiguous(), zflags[:, ys:ye, :].contiguous(), an[2],
-                      flags | (_lib.FLAG_SQRT if sqrt else 0), wxy=(an[0], an[1]))
-            outs.append(o.clone())
-        got = torch.cat(outs, 1).cpu().numpy().T
+        got = flag_phases(ops, t, _lib.U32, world, an, _lib.FLAG_BLACK_BORDER if bb else 0, sqrt).cpu().numpy().T
         want = oracle_port.edtsq(lab, an, bb)
         if sqrt:
             want = np.sqrt(want)
@@ -129,7 +115,8 @@ def test_shard_records_as_virtual_ranks(edt_gpu, oracle_port, world, chunks, sha
     blocks, and each destination runs the Z pass over the gathered records."""
     import torch
     from edt import _lib
-    from edt.distributed import HipOps, balanced_partition
+    from edt.distributed import HipOps
+    from virtual_ranks import record_phases
 
     sx, sy, sz = shape
     words = -(-sy // 32)
@@ -140,32 +127,12 @@ def test_shard_records_as_virtual_ranks(edt_gpu, oracle_port, world, chunks, sha
     assert ops.records_supported(_lib.U32, sx, sy, sz)
     lab, runs, wants = _record_case(shape, oracle_port)
     t = torch.from_numpy(np.ascontiguousarray(lab.T).view(np.int32)).to(dev)  # (sz, sy, sx), x fastest
-    zparts = balanced_partition(sz, world)
-    yparts = [(32 * a, min(32 * b, sy)) for a, b in balanced_partition(words, world)]
-    y_splits = [a for a, _ in yparts] + [sy]
-    rec = [ops.record_floats(sx, b - a) for a, b in yparts]
     for (an, bb, sqrt), want in zip(runs, wants):
-        flags = _lib.FLAG_BLACK_BORDER if bb else 0
-        dst = [torch.full((sz, rec[h]), float("nan"), dtype=torch.float32, device=dev) for h in range(world)]
-        for r, (zs, ze) in enumerate(zparts):
-            halo = t[zs - 1] if r > 0 else None  # the previous rank's last slice
-            for c0, c1 in balanced_partition(ze - zs, min(chunks, ze - zs)):
-                blocks = [dst[h][zs + c0:zs + c1] if h == r else
-                          torch.empty((c1 - c0, rec[h]), dtype=torch.float32, device=dev) for h in range(world)]
-                ops.xy_records(t[zs + c0:zs + c1], halo, _lib.U32, an, flags, y_splits, blocks)
-                for h in range(world):
-                    if h != r:
-                        dst[h][zs + c0:zs + c1].copy_(blocks[h])  # the exchange
-                halo = t[zs + c1 - 1]
-        outs = []
-        for h, (ys, ye) in enumerate(yparts):
-            # (the Z phase is told the voxel sizes of the XY phase: integer column kernel / fp32 fma candidates, edt_hip.h;
-            # every other rank without them -- the fp32 kernels with fp64 candidates: the same bits)
-            ops.z_records(dst[h], sx, ye - ys, an[2], flags | (_lib.FLAG_SQRT if sqrt else 0),
-                          wxy=(an[0], an[1]) if h % 2 == 0 else None)
-            outs.append(dst[h][:, :(ye - ys) * sx].reshape(sz, ye - ys, sx))
-        got = torch.cat(outs, 1).cpu().numpy().T
-        assert same(got, want), (world, shape, an, bb)
+        # (the Z phase is told the voxel sizes of the XY phase: integer column kernel / fp32 fma candidates, edt_hip.h;
+        # every other rank without them -- the fp32 kernels with fp64 candidates: the same bits)
+        got, _ = record_phases(ops, t, _lib.U32, world, chunks, an, _lib.FLAG_BLACK_BORDER if bb else 0, sqrt,
+                               fill=float("nan"), wxy_every=2)
+        assert same(got.cpu().numpy().T, want), (world, shape, an, bb)
 
 
 @pytest.mark.parametrize("world,chunks", [(1, 1), (2, 2), (3, 1), (8, 3)])
@@ -177,6 +144,7 @@ def test_shard_records16_as_virtual_ranks(edt_gpu, oracle_port, world, chunks, s
     import torch
     from edt import _lib
     from edt.distributed import HipOps, balanced_partition
+    from virtual_ranks import record_phases
 
     sx, sy, sz = shape
     words = -(-sy // 32)
@@ -186,35 +154,15 @@ def test_shard_records16_as_virtual_ranks(edt_gpu, oracle_port, world, chunks, s
     ops = HipOps()
     lab = voronoi_labels(shape, nseeds=60, seed=sum(shape), upsample=4, membrane=0.04)
     t = torch.from_numpy(np.ascontiguousarray(lab.T).view(np.int32)).to(dev)
-    zparts = balanced_partition(sz, world)
-    yparts = [(32 * a, min(32 * b, sy)) for a, b in balanced_partition(words, world)]
-    y_splits = [a for a, _ in yparts] + [sy]
-    rec = [ops.record16_words(sx, b - a) for a, b in yparts]
-    assert rec[0] < ops.record_floats(sx, yparts[0][1] - yparts[0][0]) * 0.55
+    rows0 = min(32 * balanced_partition(words, world)[0][1], sy)  # (the rows of the first destination)
+    assert ops.record16_words(sx, rows0) < ops.record_floats(sx, rows0) * 0.55
     for an, bb, sqrt in (((6.0, 6.0, 30.0), True, False), ((1.0, 1.0, 1.0), True, True), ((2.0, 1.0, 3.0), True, False)):
         assert ops.records16_supported(_lib.U32, sx, sy, sz, an)
-        flags = _lib.FLAG_BLACK_BORDER if bb else 0
-        refused = torch.zeros(1, dtype=torch.int32, device=dev)
-        dst = [torch.full((sz, rec[h]), -1, dtype=torch.int32, device=dev) for h in range(world)]
-        for r, (zs, ze) in enumerate(zparts):
-            halo = t[zs - 1] if r > 0 else None
-            for c0, c1 in balanced_partition(ze - zs, min(chunks, ze - zs)):
-                blocks = [dst[h][zs + c0:zs + c1] if h == r else
-                          torch.empty((c1 - c0, rec[h]), dtype=torch.int32, device=dev) for h in range(world)]
-                ops.xy_records16(t[zs + c0:zs + c1], halo, _lib.U32, an, flags, y_splits, blocks, refused)
-                for h in range(world):
-                    if h != r:
-                        dst[h][zs + c0:zs + c1].copy_(blocks[h])  # the exchange
-                halo = t[zs + c1 - 1]
-        assert int(refused.item()) == 0
-        outs = []
-        for h, (ys, ye) in enumerate(yparts):
-            out = torch.full((sz, ye - ys, sx), float("nan"), dtype=torch.float32, device=dev)
-            ops.z_records16(dst[h], out, an, flags | (_lib.FLAG_SQRT if sqrt else 0))
-            outs.append(out)
-        got = torch.cat(outs, 1).cpu().numpy().T
+        got, refused = record_phases(ops, t, _lib.U32, world, chunks, an, _lib.FLAG_BLACK_BORDER if bb else 0, sqrt, rows16=True,
+                                     fill=-1)
+        assert refused == 0
         want = oracle_port.edtsq(lab, an, bb)
-        assert same(got, np.sqrt(want) if sqrt else want), (world, shape, an, bb)
+        assert same(got.cpu().numpy().T, np.sqrt(want) if sqrt else want), (world, shape, an, bb)
 
 
 def test_shard_records16_count_the_tiles_without_a_16_bit_form(edt_gpu, oracle_port):
